@@ -6,11 +6,20 @@ One step = one full controller solve of the whole per-GPU batch: mhpc_initialize
 `value` = problems solved by all ranks / max-over-ranks wall time of the K timed steps.
 Weak scaling: every rank owns `--batch-per-gpu` independent problems (contiguous shard of
 the global x0 stream); there is no collective in the solve itself, only the barrier and
-max-reduction of the timing contract and, after the timed region, the all-gather of the
-per-problem summaries (RCCL) that rank 0 checks against a 1-GPU solve of the global batch.
+max-reduction of the timing contract.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-per-gpu B]
+  python bench.py --full ...                                   (every secondary figure too)
+  python bench.py --dump-outputs DIR ...                       (outputs of the last timed step)
   python bench.py --batch-sweep 1,16,64,256,1024,4096,8192     (1 GPU, one line per batch)
+
+A plain run sets up, warms up, times the K steps, writes its outputs when asked and prints
+the result line; everything beyond the headline figure -- per-kernel HIP-event times and the
+roofline (profiled steps of their own), the CPU baseline, the batch-4096 / serial-handle /
+float-sweep comparisons and, with N ranks, the all-gather of the per-problem summaries (RCCL)
+that rank 0 checks bitwise against a 1-GPU solve of the global batch -- runs with --full only.
+--batch-sweep is a mode of its own: each of its lines includes profiled steps (kernel times,
+roofline) with or without --full.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N ranks itself
 (one process per GPU, before anything touches the GPU); under torch.distributed.run it is
@@ -271,6 +280,27 @@ def workload_text(name: str) -> str:
     return head + ", HSDDP max_AL=2 max_DDP=3; step = initialization + solve of the whole batch"
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together stay under 64 MB
+DUMP_SEED = 0x4D485043
+
+
+def dump_sample(B: int, row_bytes: int) -> np.ndarray:
+    """Problems whose outputs --dump-outputs writes: every one when they fit the budget, else
+    a fixed (seeded) sorted sample, the same for every run with the same arguments."""
+    n = max(1, min(B, DUMP_BUDGET_BYTES // max(row_bytes, 1)))
+    if n >= B:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=n, replace=False))
+
+
+def write_dump(dirname: str, arrays: dict, rank: int, world: int):
+    """DIR/<name>.npy (rank r of N > 1: DIR/<name>_rank<r>.npy), float64."""
+    os.makedirs(dirname, exist_ok=True)
+    tail = f"_rank{rank}" if world > 1 else ""
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, f"{k}{tail}.npy"), np.asarray(v, dtype=np.float64))
+
+
 class Solver:
     """One handle on this rank's GPU, stepping init + solve of its batch."""
 
@@ -302,6 +332,32 @@ class Solver:
         status = np.where(aborted, 1, np.where(np.isfinite(sc["J"]), 0, 2)).astype(np.int32)
         return sharding.make_summary(offset, sc["J"], sc["viol"], status, sc["V"], sc["trace"])
 
+    def outputs(self) -> dict:
+        """What a caller of the step receives after it, for the problems of dump_sample:
+        the phase-concatenated trajectories / gains / cost-to-go (MHPCLocomotion.
+        problem_concatenated; rows of shorter layouts zero-padded) and the per-problem
+        scalars, with `problems` = the rows' indices in this rank's batch."""
+        loco = self.loco
+        ds = loco.descs or [loco.desc]
+        row = 0
+        for d in {bytes(d): d for d in ds}.values():
+            lx, lu, lk = d.lens()
+            row = max(row, 2 * lx + 3 * lu + lk)
+        P = loco.max_phases()
+        row_bytes = 8 * (row + 4 + 2 * P + self.capi.MHPC_TRACE_LEN)
+        idx = dump_sample(loco.batch, row_bytes)
+        rows = [loco.problem_concatenated(int(b)) for b in idx]
+        out = {"problems": idx}
+        for k in ("X", "U", "Y", "K", "DU", "G"):
+            a = np.zeros((len(idx), max(len(r[k]) for r in rows)))
+            for i, r in enumerate(rows):
+                a[i, :len(r[k])] = r[k]
+            out[k] = a
+        sc = loco.get_scalars()
+        for k in ("J", "dV_exp", "viol", "V", "dV", "trace"):
+            out[k] = sc[k][idx]
+        return out
+
     def close(self):
         self.loco.close()
 
@@ -326,12 +382,18 @@ def run_c2(args, desc, opt, x0, B, rank, world, local_rank, dist, torch):
         torch.cuda.synchronize()
 
     dev_ms = 0.0
+    last = None
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        dev_ms += loco.rollout_costs(eps)["ms"]
+        last = loco.rollout_costs(eps)
+        dev_ms += last["ms"]
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and last is not None:
+        idx = dump_sample(B, 16 * len(eps) + 8)
+        write_dump(args.dump_outputs, {"problems": idx, "J": last["J"][idx],
+                                       "viol": last["viol"][idx]}, rank, world)
     tens = torch.tensor([dt], dtype=torch.float64, device=f"cuda:{local_rank}")
     if dist is not None:
         dist.all_reduce(tens, op=dist.ReduceOp.MAX)
@@ -345,7 +407,7 @@ def run_c2(args, desc, opt, x0, B, rank, world, local_rank, dist, torch):
         per_launch_s = dev_ms / 1e3 / args.steps
         achieved = alg / per_launch_s / 1e9 if per_launch_s > 0 else 0.0
         cpu = {"value": None, "reason": "disabled"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import oracle as O
             if O.available():
@@ -361,7 +423,7 @@ def run_c2(args, desc, opt, x0, B, rank, world, local_rank, dist, torch):
         line = {
             "metric": "C2 trial rollouts/sec (1 WB phase N=120, 256 step sizes per nominal)",
             "value": n / dt, "unit": "rollouts/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "full": bool(args.full),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
             "data": "synthetic (x0 = reference default + splitmix64 perturbation)",
             "config": {"workload": "C2: WB mode 1, dt=(float)(0.08f/120), N=120; step = 256 "
@@ -372,8 +434,9 @@ def run_c2(args, desc, opt, x0, B, rank, world, local_rank, dist, torch):
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": None, "alg_bytes_per_launch": alg,
                          "avg_launch_ms": per_launch_s * 1e3},
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            line["cpu_baseline"] = cpu
         print(json.dumps(line), file=_LINE_OUT or sys.stdout, flush=True)
     loco.close()
     if dist is not None:
@@ -456,6 +519,16 @@ def main():
                          "(BASELINE configs[4]); c2: 256 trial rollouts of one nominal per problem; "
                          "mixed: per-problem gait schedules (C3 / C5 layouts at several gait "
                          "points in one batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary measurement and check: "
+                         "profiled steps (kernel times, roofline), CPU baseline, north star / "
+                         "serial-handle / float-sweep comparisons, summary all-gather and the "
+                         "1-GPU shard check (the --no-* options below trim a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (trajectories, "
+                         "gains, cost-to-go, per-problem scalars; c2: trial costs) as "
+                         "DIR/<name>.npy, float64, under 64 MB in all (a fixed seeded sample of "
+                         "the problems, DIR/problems.npy, when the batch is larger)")
     ap.add_argument("--no-north-star", action="store_true",
                     help="c3 at N=1: skip the extra batch-4096 measurement (north_star_b4096)")
     ap.add_argument("--cpu-sample", type=int, default=None,
@@ -490,7 +563,8 @@ def main():
     ap.add_argument("--sub-batches", type=int, default=0,
                     help="concurrently scheduled sub-batches per GPU, 1..4 (0 = automatic; tuning only)")
     ap.add_argument("--batch-sweep", default=None,
-                    help="comma-separated batch sizes: one JSON line each (1 GPU)")
+                    help="comma-separated batch sizes: one JSON line each (1 GPU), always with "
+                         "profiled steps (kernel times, roofline); --full changes nothing here")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -506,6 +580,9 @@ def main():
     if args.batch_sweep:
         if world != 1:
             print("bench.py: --batch-sweep runs on one GPU", file=sys.stderr)
+            sys.exit(2)
+        if args.dump_outputs:
+            print("bench.py: --dump-outputs does not go with --batch-sweep", file=sys.stderr)
             sys.exit(2)
         return run_sweep(args, torch)
     dist = None
@@ -562,17 +639,20 @@ def main():
         knot_steps += c["bws_knots"] + (c["fwd_sweeps"] + c["ddp_iters"]) * kroll
     barrier()
     dt = time.perf_counter() - t0
-    # per-kernel HIP-event timing (an event pair around every launch) in separate steps after
-    # the timed region, so the events do not sit between the timed kernels
-    s.loco.set_profiling(True)
-    s.loco.reset_kernel_stats()
-    prof_steps = args.profile_steps if args.profile_steps is not None else args.steps
-    for _ in range(prof_steps):
-        s.step()
-    torch.cuda.synchronize()
-    s.loco.set_profiling(False)
-
-    stats = s.loco.kernel_stats()
+    if args.dump_outputs:  # the last timed step's outputs, before anything else steps the handle
+        write_dump(args.dump_outputs, s.outputs(), rank, world)
+    # --full: per-kernel HIP-event timing (an event pair around every launch) in separate steps
+    # after the timed region, so the events do not sit between the timed kernels
+    stats, prof_steps = None, 0
+    if args.full:
+        s.loco.set_profiling(True)
+        s.loco.reset_kernel_stats()
+        prof_steps = args.profile_steps if args.profile_steps is not None else args.steps
+        for _ in range(prof_steps):
+            s.step()
+        torch.cuda.synchronize()
+        s.loco.set_profiling(False)
+        stats = s.loco.kernel_stats()
     tens = torch.tensor([dt, solve_ms / 1e3, float(ddp_iters), float(knot_steps)],
                         dtype=torch.float64, device=tdev)
     shard = None
@@ -582,17 +662,18 @@ def main():
         tsum = tens[2:].clone()
         dist.all_reduce(tsum, op=dist.ReduceOp.SUM)
         dt, solve_s, ddp_total, knot_total = float(tmax[0]), float(tmax[1]), float(tsum[0]), float(tsum[1])
-        # per-problem summaries of every rank (RCCL all-gather; outside the timed region)
-        allp = sharding.gather_summaries(s.summary(rank * B),
-                                         device=tdev if args.backend == "nccl" else None)
-        shard = {"ranks": dist.get_world_size(), "backend": dist.get_backend(),
-                 "gathered_problems": int(len(allp))}
+        shard = {"ranks": dist.get_world_size(), "backend": dist.get_backend()}
+        if args.full:
+            # per-problem summaries of every rank (RCCL all-gather; outside the timed region)
+            allp = sharding.gather_summaries(s.summary(rank * B),
+                                             device=tdev if args.backend == "nccl" else None)
+            shard["gathered_problems"] = int(len(allp))
     else:
         solve_s, ddp_total, knot_total = solve_ms / 1e3, float(ddp_iters), float(knot_steps)
     s.close()
 
     if rank == 0:
-        if shard is not None and not args.no_shard_check:
+        if shard is not None and args.full and not args.no_shard_check:
             # the same global x0 stream solved on one GPU: every gathered summary must be
             # bitwise identical
             one = Solver(desc, opt, x0_of(args.workload, desc, world * B), local_rank,
@@ -609,8 +690,8 @@ def main():
         # north star (BASELINE.json: solves/s at batch 4096 on one GPU): the same init + solve
         # step at 4096 problems, measured in this run after the headline's timed region
         ns = None
-        if (world == 1 and args.workload == "c3" and B != 4096 and not args.no_north_star
-                and dist is None):
+        if (args.full and world == 1 and args.workload == "c3" and B != 4096
+                and not args.no_north_star and dist is None):
             n4 = 4096
             s4 = Solver(desc, opt, x0_of("c3", desc, n4), local_rank)
             for _ in range(args.warmup):
@@ -630,7 +711,7 @@ def main():
         # per layout holding that layout's problems (same x0 rows), stepped one after the other
         # (each step = init + solve of every handle), timed in this run after the headline
         serial = None
-        if world == 1 and args.workload == "mixed" and dist is None:
+        if args.full and world == 1 and args.workload == "mixed" and dist is None:
             descs, lop = layouts_of("mixed", B)
             hs = [Solver(descs[l], opt, x0[lop == l], local_rank) for l in range(len(descs))
                   if (lop == l).any()]
@@ -654,7 +735,8 @@ def main():
         # c5f32: the same step with the float backward sweep (MHPC_VARIANT_SWEEP_BITS = 32; the
         # default fp32 sweep computes in double), timed after the headline
         fsw = None
-        if world == 1 and args.workload == "c5f32" and args.sweep_bits == 0 and dist is None:
+        if (args.full and world == 1 and args.workload == "c5f32" and args.sweep_bits == 0
+                and dist is None):
             sf = Solver(desc, opt, x0, local_rank, variants, sweep_bits=32)
             for _ in range(args.warmup):
                 sf.step()
@@ -669,7 +751,7 @@ def main():
                    "note": "same step with the float backward sweep (sweep_bits 32), timed after the "
                            "headline's timed region"}
         cpu, why = (None, "disabled" if world == 1 else "reported at N=1 only")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = args.cpu_threads or usable_cpus()
             if args.workload == "mixed":
                 cpu, why = cpu_baseline_mixed(args, opt, threads)
@@ -684,6 +766,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3,
+            "full": bool(args.full),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -699,11 +782,12 @@ def main():
             "ddp_iters_per_s": ddp_total / dt,
             "knot_steps_per_s": knot_total / dt if kroll else None,
             "solve_only_per_s": total / solve_s if solve_s > 0 else None,
-            "kernel_ms_per_step": {k: v["ms"] / max(prof_steps, 1) for k, v in stats.items()},
-            "profiled_steps": prof_steps,
-            "roofline": roofline_of(stats, B, args.workload),
-            "cpu_baseline": cpu if cpu is not None else {"value": None, "reason": why},
         }
+        if args.full:
+            line["kernel_ms_per_step"] = {k: v["ms"] / max(prof_steps, 1) for k, v in stats.items()}
+            line["profiled_steps"] = prof_steps
+            line["roofline"] = roofline_of(stats, B, args.workload)
+            line["cpu_baseline"] = cpu if cpu is not None else {"value": None, "reason": why}
         if ns is not None:
             line["north_star_b4096"] = ns
         if serial is not None:

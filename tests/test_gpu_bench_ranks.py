@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_two_ranks_shard_and_gather(need_gpu):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
            "--share-gpu", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "61",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -36,7 +36,7 @@ def test_rccl_group_world_one(need_gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", "29533",
            os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist", "--steps", "2",
-           "--warmup", "1", "--batch-per-gpu", "37", "--no-cpu-baseline"]
+           "--warmup", "1", "--batch-per-gpu", "37", "--full", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -18,13 +18,13 @@ run() {  # name, args...
   timeout -k 10 400 python bench.py "$@" > gpurun_out/bench_${TAG}_$n.json 2> gpurun_out/bench_${TAG}_$n.err || { echo "bench $n failed"; tail gpurun_out/bench_${TAG}_$n.err; exit 1; }
   python -c "import json;d=json.load(open('gpurun_out/bench_${TAG}_$n.json'));print('$n', round(d['value']), d['unit'], round(d['ms_per_step'],3), 'cpu', (d.get('cpu_baseline') or {}).get('value'))"
 }
-run b1024
-run b4096 --batch-per-gpu 4096 --no-cpu-baseline --no-north-star
-run c2_b1 --workload c2 --no-north-star
-run c2_b1024 --workload c2 --batch-per-gpu 1024 --no-cpu-baseline --no-north-star
-run c5_b4096 --workload c5 --cpu-sample 2048 --no-north-star
-run c5f32_b4096 --workload c5f32 --no-cpu-baseline --no-north-star
-run mixed_b4096 --workload mixed --no-north-star
+run b1024 --full
+run b4096 --full --batch-per-gpu 4096 --no-cpu-baseline --no-north-star
+run c2_b1 --full --workload c2 --no-north-star
+run c2_b1024 --full --workload c2 --batch-per-gpu 1024 --no-cpu-baseline --no-north-star
+run c5_b4096 --full --workload c5 --cpu-sample 2048 --no-north-star
+run c5f32_b4096 --full --workload c5f32 --no-cpu-baseline --no-north-star
+run mixed_b4096 --full --workload mixed --no-north-star
 timeout -k 10 400 python bench.py --batch-sweep 1,16,64,256,512,1024,2048,4096,8192 --steps 5 --warmup 2 > gpurun_out/sweep_${TAG}.jsonl 2> gpurun_out/sweep_${TAG}.err || { echo "sweep failed"; tail gpurun_out/sweep_${TAG}.err; exit 1; }
 python -c "
 import json
