@@ -34,6 +34,12 @@
  *   mhpc_set_layouts     one MHPCLocomotion per controller, each built from its own Gait
  *                        (MHPCLocomotion.cpp:63-104): per-problem phase layouts in one batch
  *   mhpc_update_problems update_problem of every controller with its own gait and step count
+ *   mhpc_set_commands    MHPCUserParameters::usrcmd of every controller (vel, height), which
+ *                        build_problem / update_problem hand to ReferenceGen
+ *                        (MHPCLocomotion.cpp:98-103): per-problem user commands in one batch;
+ *                        mhpc_get_commands reads them back
+ *   mhpc_get_reference_problems  ReferenceGen::generate_ref's ms_ref_*[p][k].x
+ *                        (ReferenceGen.h:53-109): the tracking reference the costs use
  */
 #ifndef MHPC_CAPI_H
 #define MHPC_CAPI_H
@@ -195,6 +201,25 @@ int mhpc_get_problem_desc(mhpc_handle* h, int problem, mhpc_problem_desc* desc);
  * mhpc_update_problem).  n_gaits in 1..MHPC_MAX_LAYOUTS. */
 int mhpc_update_problems(mhpc_handle* h, int n_gaits, const mhpc_gait* gaits,
                          const int32_t* gait_of_problem, const int32_t* steps);
+/* ---- per-problem user commands: the batch axis over speed / height commands -----------
+ * Per-problem user command (the reference's MHPCUserParameters::usrcmd of each controller,
+ * MHPCLocomotion.cpp:98-103).  vel, height: host arrays [batch]; either may be NULL = unchanged.
+ * A handle starts with vel_cmd / height_cmd of mhpc_create's descriptor for every problem.
+ * Every entry must be finite (no sign or range restriction: the reference has none); the fp32
+ * build rounds to float.  Commands belong to the problem number: they survive
+ * mhpc_set_layouts and mhpc_update_problem(s), and mhpc_get_problem_desc(b) reports problem
+ * b's (mhpc_get_desc: problem 0's).  New values take effect at the next mhpc_initialize or
+ * mhpc_update_problem(s), which regenerate every problem's references; set on an initialized
+ * handle they make mhpc_solve and mhpc_rollout_costs return MHPC_ERR_STATE until one of those
+ * has run (the position references would otherwise belong to the old speed).  A call whose
+ * values all equal the current ones changes nothing. */
+int mhpc_set_commands(mhpc_handle* h, const double* vel, const double* height);
+int mhpc_get_commands(mhpc_handle* h, double* vel, double* height);   /* either may be NULL */
+/* The tracking reference x of `phase` for problems [first, first+count): [count][N][xsize],
+ * the reference's ms_ref_*[p][k].x as ReferenceGen::generate_ref leaves it
+ * (ReferenceGen.h:53-109).  The range's phase must have one shape (as mhpc_get_phase_problems). */
+int mhpc_get_reference_problems(mhpc_handle* h, int phase, int first, int count, double* xref);
+
 /* Distinct phase layouts currently in use (1 for a homogeneous batch). */
 int mhpc_num_layouts(mhpc_handle* h, int* n);
 /* The largest phase count over the problems' current layouts: the row length of
@@ -322,8 +347,9 @@ void mhpc_destroy(mhpc_handle* h);
                                          and writes float gains but sums, factors and carries the
                                          value function in double) or, fp32 handles only, 32
                                          (the sweep in float, its 4x4 control block in double:
-                                         faster, 10-70x larger typical error vs the fp64 oracle,
-                                         DESIGN.md §5); 0 = default */
+                                         no faster -- within 1 % of the double sweep -- and 10-70x
+                                         larger typical error vs the fp64 oracle, DESIGN.md §3,
+                                         §5); 0 = default */
 int mhpc_set_kernel_variant(mhpc_handle* h, int which, int variant);
 
 /* ---- batched model evaluation on the device (kernel-level parity hooks) -----------

@@ -309,6 +309,35 @@ class MHPCLocomotion {
           "mhpc_update_problems");
     refresh_descs();
   }
+  // extension: per-problem user commands in one batch -- the usrcmd (float vel, height) of one
+  // controller per problem, which build_problem hands to ReferenceGen (MHPCLocomotion.cpp
+  // :98-103).  One entry per problem, an empty vector keeps the current values; they take
+  // effect at the next initialization() / update_problem(s), and an initialised object refuses
+  // to solve until then.
+  void set_commands(const std::vector<float>& vel, const std::vector<float>& height = {}) {
+    if ((!vel.empty() && (int)vel.size() != batch_) ||
+        (!height.empty() && (int)height.size() != batch_))
+      throw std::runtime_error("set_commands: one entry per problem expected");
+    const std::vector<double> v(vel.begin(), vel.end()), hg(height.begin(), height.end());
+    check(mhpc_set_commands(h_, v.empty() ? nullptr : v.data(), hg.empty() ? nullptr : hg.data()),
+          "mhpc_set_commands");
+  }
+  void get_commands(std::vector<double>& vel, std::vector<double>& height) {
+    vel.assign(batch_, 0.0);
+    height.assign(batch_, 0.0);
+    check(mhpc_get_commands(h_, vel.data(), height.data()), "mhpc_get_commands");
+  }
+  // the tracking reference x of phase p for problems [first, first + count): [count][N][xsize]
+  // (ReferenceGen.h:53-109; the range's phase must have one shape)
+  std::vector<double> get_reference_problems(int p, int first, int count) {
+    const mhpc_problem_desc d = problem_desc(first);
+    int n = 0, N = 0;
+    check(mhpc_phase_dims(&d, p, &n, &N), "mhpc_phase_dims");
+    std::vector<double> xref((size_t)count * N * n);
+    check(mhpc_get_reference_problems(h_, p, first, count, xref.data()),
+          "mhpc_get_reference_problems");
+    return xref;
+  }
   mhpc_problem_desc problem_desc(int b) {
     mhpc_problem_desc d{};
     check(mhpc_get_problem_desc(h_, b, &d), "mhpc_get_problem_desc");

@@ -200,6 +200,10 @@ SIGNATURES = [
                                         _IP]),
     ("mhpc_get_problem_desc", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int,
                                              ctypes.POINTER(ProblemDesc)]),
+    ("mhpc_set_commands", ctypes.c_int, [ctypes.c_void_p, _DP, _DP]),
+    ("mhpc_get_commands", ctypes.c_int, [ctypes.c_void_p, _DP, _DP]),
+    ("mhpc_get_reference_problems", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_int, _DP]),
     ("mhpc_num_layouts", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     ("mhpc_max_phases", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     ("mhpc_rollout_costs", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _DP, _DP, _DP,

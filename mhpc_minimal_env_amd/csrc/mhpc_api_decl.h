@@ -21,6 +21,9 @@ int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const in
                         const int32_t* steps);
 int api_set_layouts(Handle* h, int n_desc, const mhpc_problem_desc* descs, const int32_t* lop);
 int api_get_problem_desc(Handle* h, int b, mhpc_problem_desc* desc);
+int api_set_commands(Handle* h, const double* vel, const double* height);
+int api_get_commands(Handle* h, double* vel, double* height);
+int api_get_reference(Handle* h, int phase, int first, int count, double* xref);
 int api_num_layouts(Handle* h, int* n);
 int api_max_phases(Handle* h, int* n);
 int api_get_desc(Handle* h, mhpc_problem_desc* desc);

@@ -365,6 +365,9 @@ struct RowCtx {
   breal reg;    // regularisation of the attempt
   acc dV;      // expected cost change (row-uniform)
   int64_t kn, kn_wb, px_reads;
+  // the problem's user command, loaded once per launch where the row picks up its problem's
+  // state; every phase folds it into its lanes' fixed reference (rxc) at phase start
+  Cmd cm;
 };
 
 __device__ __forceinline__ bool go(const RowCtx& r) { return r.live && !r.failed; }
@@ -431,8 +434,8 @@ __device__ int sweep_wb(const SolveParams& sp, const DevBufs& d, const Layout& L
   // running-cost weight and fixed reference of state rho (CostBase.cpp:28-31)
   const int xi = xl ? rho : 0;
   const breal w2 = 2 * dt * sp.cw.wQ[mode - 1][xi];
-  const breal rxc = xi == 1 ? sp.height : xi == 2 ? breal(0.0)
-                   : (xi >= 3 && xi < 7) ? cQjointBias[xi - 3] : xi == 7 ? sp.vel : breal(0.0);
+  const breal rxc = xi == 1 ? rc.cm.height : xi == 2 ? breal(0.0)
+                   : (xi >= 3 && xi < 7) ? cQjointBias[xi - 3] : xi == 7 ? rc.cm.vel : breal(0.0);
   // lxx + reg on the diagonal of Qxx (Ixx * regularisation): added twice to the transposed
   // copy in LDS, so that (Qxx + Qxx') / 2 carries it once
   const breal dg2 = xl ? 2 * (w2 + rc.reg) : breal(0.0);
@@ -708,8 +711,8 @@ __device__ int sweep_wb2(const SolveParams& sp, const DevBufs& d, const Layout& 
   }
   const int xi = xl ? rho : 0;
   const breal w2 = 2 * dt * sp.cw.wQ[mode - 1][xi];
-  const breal rxc = xi == 1 ? sp.height : xi == 2 ? breal(0.0)
-                   : (xi >= 3 && xi < 7) ? cQjointBias[xi - 3] : xi == 7 ? sp.vel : breal(0.0);
+  const breal rxc = xi == 1 ? rc.cm.height : xi == 2 ? breal(0.0)
+                   : (xi >= 3 && xi < 7) ? cQjointBias[xi - 3] : xi == 7 ? rc.cm.vel : breal(0.0);
   // lxx + reg on the diagonal, added by the row that owns the diagonal's column
   const bool own_diag = xl && ((rho < 7) == (rp == 0));
   const breal dg2 = own_diag ? 2 * (w2 + rc.reg) : breal(0.0);
@@ -1026,7 +1029,7 @@ __device__ int sweep_srb(const SolveParams& sp, const DevBufs& d, const Layout& 
   breal w2, rxc;
   if (cj < 6) {
     w2 = 2 * dt * sp.cw.fQ[m][cj];
-    rxc = cj == 1 ? sp.height : cj == 3 ? sp.vel : breal(0.0);
+    rxc = cj == 1 ? rc.cm.height : cj == 3 ? rc.cm.vel : breal(0.0);
   } else {
     const int c = cj - 6;
     w2 = 2 * dt * sp.cw.fR[m][c];
@@ -1236,6 +1239,7 @@ __device__ void terminal_value(const SolveParams& sp, const DevBufs& d, const La
   constexpr bool wb = NX == 14;
   const int mode = L.mode[p], N = L.N[p], ko = L.ko[p];
   const breal pos = d.refpos[(size_t)rc.b * sp.NK + ko + N - 1];
+  const breal cvel = rc.cm.vel, chgt = rc.cm.height;  // (the sweep's arithmetic type)
   const real* xe = traj_ptr(sp, d, rc.b, rc.nom, ko + N - 1);
   const bool al = wb && ntc_of(mode, true) && sp.AL_active && st->al_partials;
   if (al && rc.lt == 0) {
@@ -1269,8 +1273,8 @@ __device__ void terminal_value(const SolveParams& sp, const DevBufs& d, const La
     } else {
       const int i = e - NX * NX;
       breal rxi;
-      if (wb) rxi = i == 0 ? pos : (i == 7 ? sp.vel : cXtermWB[mode - 1][i]);
-      else rxi = i == 0 ? pos : (i == 1 ? sp.height : (i == 3 ? sp.vel : breal(0.0)));
+      if (wb) rxi = i == 0 ? pos : (i == 7 ? cvel : cXtermWB[mode - 1][i]);
+      else rxi = i == 0 ? pos : (i == 1 ? chgt : (i == 3 ? cvel : breal(0.0)));
       breal v = (wb ? sp.cw.wQf[mode - 1][i] : sp.cw.fQf[mode - 1][i]) * (xe[i] - rxi);
       if (al) v += 50 * (s * s / 2 * rl.hx[i] * h + lam * rl.hx[i]);
       const breal g = v + rl.Gs[i];
@@ -1453,6 +1457,7 @@ __global__ __launch_bounds__(64, PART == 1 ? MHPC_BWS_SRB_WAVES : 1) void k_bws(
   RowLds& rl = sh.r[q];
   rc.nom = st->nom_slot;
   rc.reg = st->reg;
+  rc.cm = cmd_of(d, rc.b);
   rc.kn = rc.kn_wb = rc.px_reads = 0;
   rc.dV = acc(0.0);
   int bws_iter = 1;

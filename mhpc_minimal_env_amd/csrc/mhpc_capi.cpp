@@ -149,6 +149,16 @@ extern "C" int mhpc_set_layouts(mhpc_handle* h, int n_desc, const mhpc_problem_d
 extern "C" int mhpc_get_problem_desc(mhpc_handle* h, int problem, mhpc_problem_desc* desc) {
   FWD(get_problem_desc, problem, desc);
 }
+extern "C" int mhpc_set_commands(mhpc_handle* h, const double* vel, const double* height) {
+  FWD(set_commands, vel, height);
+}
+extern "C" int mhpc_get_commands(mhpc_handle* h, double* vel, double* height) {
+  FWD(get_commands, vel, height);
+}
+extern "C" int mhpc_get_reference_problems(mhpc_handle* h, int phase, int first, int count,
+                                           double* xref) {
+  FWD(get_reference, phase, first, count, xref);
+}
 extern "C" int mhpc_num_layouts(mhpc_handle* h, int* n) { FWD(num_layouts, n); }
 extern "C" int mhpc_max_phases(mhpc_handle* h, int* n) { FWD(max_phases, n); }
 extern "C" int mhpc_get_counters(mhpc_handle* h, mhpc_counters* c) { FWD(get_counters, c); }

@@ -75,6 +75,10 @@ static __device__ __forceinline__ const Layout& layout_of(const DevBufs& d, int 
   return *(const Layout*)((CLayout*)d.lay + g);
 }
 
+// User command of problem b: loaded once per problem where a kernel picks up its state (the
+// cost code and the sweep fold it into their per-lane references, never a load per knot).
+static __device__ __forceinline__ Cmd cmd_of(const DevBufs& d, int b) { return d.cmd[b]; }
+
 // Natural log of a positive argument (the barrier's g > delta > 0 and delta itself).  fp64:
 // the fdlibm algorithm (e_log.c: x = 2^k (1 + f) with sqrt(2)/2 <= 1 + f < sqrt(2),
 // s = f / (2 + f), a degree-14 odd polynomial in s), < 1 ulp -- about a third of the
@@ -132,15 +136,30 @@ static __device__ __forceinline__ void reduced_barrier(real g, real delta, real*
   }
 }
 
+// Running state reference of a WB / SRB knot (ReferenceGen.h:53-92: forward position, commanded
+// height and speed, nominal joint angles), built in registers.
+static __device__ __forceinline__ void wb_run_ref(const Cmd& cm, real pos, real* rx) {
+  MHPC_NO_FMA_COST
+  rx[0] = pos; rx[1] = cm.height; rx[2] = 0;
+  rx[3] = cQjointBias[0]; rx[4] = cQjointBias[1]; rx[5] = cQjointBias[2]; rx[6] = cQjointBias[3];
+  rx[7] = cm.vel;
+#pragma unroll
+  for (int i = 8; i < 14; ++i) rx[i] = 0;
+}
+static __device__ __forceinline__ void fb_run_ref(const Cmd& cm, real pos, real* rx) {
+  MHPC_NO_FMA_COST
+  rx[0] = pos; rx[1] = cm.height; rx[2] = 0; rx[3] = cm.vel; rx[4] = 0; rx[5] = 0;
+}
+
 // Running cost value incl. the ReB barrier of WB phases (CostBase.cpp:4-16,
 // SinglePhase.cpp:219-249 in CALC_DYNAMICS_ONLY), reference of knot kk built in registers.
-static __device__ real wb_running_cost(const SolveParams& sp, int mode, real dt, real pos,
-                                  const real* x, const real* u, const real* y, bool reb,
+static __device__ real wb_running_cost(const SolveParams& sp, const Cmd& cm, int mode, real dt,
+                                  real pos, const real* x, const real* u, const real* y, bool reb,
                                   real delta, real eps_tq, real eps_grf) {
   MHPC_NO_FMA_COST
   const int m = mode - 1;
-  real rx[14] = {pos, sp.height, 0, cQjointBias[0], cQjointBias[1], cQjointBias[2],
-                   cQjointBias[3], sp.vel, 0, 0, 0, 0, 0, 0};
+  real rx[14];
+  wb_run_ref(cm, pos, rx);
   const real ry[4] = {0, kGRF, 0, kGRF};
   real l = 0, t = 0;
 #pragma unroll
@@ -176,11 +195,12 @@ static __device__ real wb_running_cost(const SolveParams& sp, int mode, real dt,
   return l;
 }
 
-static __device__ real fb_running_cost(const SolveParams& sp, int mode, real dt, real pos,
-                                  const real* x, const real* u) {
+static __device__ real fb_running_cost(const SolveParams& sp, const Cmd& cm, int mode, real dt,
+                                  real pos, const real* x, const real* u) {
   MHPC_NO_FMA_COST
   const int m = mode - 1;
-  const real rx[6] = {pos, sp.height, 0, sp.vel, 0, 0};
+  real rx[6];
+  fb_run_ref(cm, pos, rx);
   const real ru[4] = {0, kGRF, 0, kGRF};
   real l = 0, t = 0;
 #pragma unroll
@@ -245,17 +265,17 @@ static __device__ void wb_cost_uy_derivs(const SolveParams& sp, int mode, real d
   }
 }
 
-static __device__ void wb_term_ref(const SolveParams& sp, int mode, real pos, real* rx) {
+static __device__ void wb_term_ref(const Cmd& cm, int mode, real pos, real* rx) {
   MHPC_NO_FMA_F32
 #pragma unroll
   for (int i = 0; i < 14; ++i) rx[i] = cXtermWB[mode - 1][i];
-  rx[7] = sp.vel;
+  rx[7] = cm.vel;
   rx[0] = pos;
 }
 
-static __device__ void fb_term_ref(const SolveParams& sp, real pos, real* rx) {
+static __device__ void fb_term_ref(const Cmd& cm, real pos, real* rx) {
   MHPC_NO_FMA_F32
-  rx[0] = pos; rx[1] = sp.height; rx[2] = 0; rx[3] = sp.vel; rx[4] = 0; rx[5] = 0;
+  rx[0] = pos; rx[1] = cm.height; rx[2] = 0; rx[3] = cm.vel; rx[4] = 0; rx[5] = 0;
 }
 
 // FootholdPlanner::get_foothold_location (FootholdPlan.h:26-50), velcmd 1.5 / ground

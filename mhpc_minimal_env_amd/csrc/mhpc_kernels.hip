@@ -229,6 +229,7 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
   const Layout& L = layout_of(d, gb.g);
   const bool in = lp < ppw && gb.p0 + lp < gb.p1;
   const int b = in ? prob_at(sp, d, gb.p0 + lp) : 0;
+  const Cmd cm = cmd_of(d, b);  // the problem's user command (cost side)
 
   // ring of RD knot records; the waves meet at a barrier every RD / 2 records
   constexpr int RD = PIPE ? (PAIR ? RO_RING_PAIR : 2) : 1;
@@ -542,8 +543,8 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
     constexpr bool wb = decltype(WBc)::value;
     const real pos = ST ? sRef[lp][kk] : c.refpos[kk];
     if (full != 2)  // (a re-roll only writes the records)
-      V += wb ? wb_running_cost(sp, mode, dt, pos, r, r + 14, r + 18, reb, c.delta, c.etq, c.egr)
-              : fb_running_cost(sp, mode, dt, pos, r, r + 6);
+      V += wb ? wb_running_cost(sp, cm, mode, dt, pos, r, r + 14, r + 18, reb, c.delta, c.etq, c.egr)
+              : fb_running_cost(sp, cm, mode, dt, pos, r, r + 6);
     store_rec(r, wb ? RING_W : 14, ko + kk, true);
   };
   auto ring_rec = [&](int sl, real* r, int n) __attribute__((always_inline)) {
@@ -554,7 +555,7 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
   auto srb_terminal_cost = [&](int mode, real refT, const real* xe) __attribute__((always_inline)) {
     MHPC_NO_FMA_COST
     real rx[6];
-    fb_term_ref(sp, refT, rx);
+    fb_term_ref(cm, refT, rx);
     acc Phi = 0;
     for (int i = 0; i < 6; ++i) { const real e = xe[i] - rx[i]; Phi += e * sp.cw.fQf[mode - 1][i] * e; }
     return Phi * acc(0.5);
@@ -572,7 +573,7 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
     real h = 0;
     if (wb) {
       real rx[14];
-      wb_term_ref(sp, mode, c.refT, rx);
+      wb_term_ref(cm, mode, c.refT, rx);
       acc Phi = 0;
       for (int i = 0; i < 14; ++i) { const real e = xe[i] - rx[i]; Phi += e * sp.cw.wQf[mode - 1][i] * e; }
       Phi = Phi * acc(0.5);
@@ -858,6 +859,7 @@ __global__ __launch_bounds__(64) void k_eps_rollout(SolveParams sp, DevBufs d, i
   const int b = prob_at(sp, d, pos);
   const long t = (long)b * n_eps + e;  // output index [problem][step size]
   const ProbState* st = &d.st[b];
+  const Cmd cm = cmd_of(d, b);
   const int nom = st->nom_slot;
   const real eps = eps_v[e];
   const bool reb = st->reb_active != 0;
@@ -885,14 +887,14 @@ __global__ __launch_bounds__(64) void k_eps_rollout(SolveParams sp, DevBufs d, i
         }
         real xd[14], y[4];
         wb_dynamics<real>(x, u, mode, xd, y);
-        V += wb_running_cost(sp, mode, dt, refpos[k], x, u, y, reb, delta, etq, egr);
+        V += wb_running_cost(sp, cm, mode, dt, refpos[k], x, u, y, reb, delta, etq, egr);
 #pragma unroll
         for (int i = 0; i < 14; ++i) x[i] = x[i] + xd[i] * dt;
       }
       {
         MHPC_NO_FMA_COST
         real rx[14];
-        wb_term_ref(sp, mode, refpos[N - 1], rx);
+        wb_term_ref(cm, mode, refpos[N - 1], rx);
         acc Phi = 0;
         for (int i = 0; i < 14; ++i) { const real ee = x[i] - rx[i]; Phi += ee * sp.cw.wQf[mode - 1][i] * ee; }
         Phi = Phi * acc(0.5);
@@ -933,12 +935,12 @@ __global__ __launch_bounds__(64) void k_eps_rollout(SolveParams sp, DevBufs d, i
         }
         real xd[6];
         srb_dynamics(x, u, f, sc, xd);
-        V += fb_running_cost(sp, mode, dt, refpos[k], x, u);
+        V += fb_running_cost(sp, cm, mode, dt, refpos[k], x, u);
 #pragma unroll
         for (int i = 0; i < 6; ++i) x[i] = x[i] + xd[i] * dt;
       }
       real rx[6];
-      fb_term_ref(sp, refpos[N - 1], rx);
+      fb_term_ref(cm, refpos[N - 1], rx);
       acc Phi = 0;
       for (int i = 0; i < 6; ++i) { const real ee = x[i] - rx[i]; Phi += ee * sp.cw.fQf[mode - 1][i] * ee; }
       V += Phi * acc(0.5);
@@ -966,6 +968,7 @@ __global__ void k_cost_grad(SolveParams sp, DevBufs d, int g, int p, int b0, int
   if (t >= (long)nb * N) return;
   const int i0 = (int)(t / N), k = (int)(t - (long)i0 * N), b = b0 + i0;
   const ProbState* st = &d.st[b];
+  const Cmd cm = cmd_of(d, b);
   const bool wb = p < L.n_wb;
   const int n = wb ? 14 : 6;
   const real dt = L.dt[p];
@@ -976,11 +979,11 @@ __global__ void k_cost_grad(SolveParams sp, DevBufs d, int g, int p, int b0, int
     for (int i = 0; i < n; ++i) {
       real rxi, w2;
       if (wb) {
-        rxi = i == 0 ? pos : i == 1 ? sp.height : i == 2 ? real(0.0)
-              : i < 7 ? cQjointBias[i - 3] : i == 7 ? sp.vel : real(0.0);
+        rxi = i == 0 ? pos : i == 1 ? cm.height : i == 2 ? real(0.0)
+              : i < 7 ? cQjointBias[i - 3] : i == 7 ? cm.vel : real(0.0);
         w2 = 2 * dt * sp.cw.wQ[mode - 1][i];
       } else {
-        rxi = i == 0 ? pos : i == 1 ? sp.height : i == 3 ? sp.vel : real(0.0);
+        rxi = i == 0 ? pos : i == 1 ? cm.height : i == 3 ? cm.vel : real(0.0);
         w2 = 2 * dt * sp.cw.fQ[mode - 1][i];
       }
       o[i] = w2 * (x[i] - rxi);
@@ -989,7 +992,7 @@ __global__ void k_cost_grad(SolveParams sp, DevBufs d, int g, int p, int b0, int
     real* o = phix + (size_t)i0 * n;
     if (wb) {
       real rx[14];
-      wb_term_ref(sp, mode, pos, rx);
+      wb_term_ref(cm, mode, pos, rx);
       const bool al = ntc_of(mode, true) && st->par_al;
       real h = 0, hx[14], Hs[3][3];
       if (al) {
@@ -1016,7 +1019,7 @@ __global__ void k_cost_grad(SolveParams sp, DevBufs d, int g, int p, int b0, int
       for (int i = 0; i < 14; ++i) o[i] = v[i];
     } else {
       real rx[6];
-      fb_term_ref(sp, pos, rx);
+      fb_term_ref(cm, pos, rx);
       for (int i = 0; i < 6; ++i) o[i] = sp.cw.fQf[mode - 1][i] * (x[i] - rx[i]);
     }
   }
@@ -1266,10 +1269,11 @@ __device__ void k_init_state(const SolveParams& sp, const DevBufs& d, const Layo
                              int warm) {
   const real* x0 = d.x0 + (size_t)b * 14;
   real* pos = d.refpos + (size_t)b * sp.NK;
+  const real vel = cmd_of(d, b).vel;
   for (int p = 0; p < L.P; ++p) {
     const int ko = L.ko[p];
     pos[ko] = p == 0 ? x0[0] : pos[L.ko[p - 1] + L.N[p - 1] - 1];
-    for (int k = 1; k < L.N[p]; ++k) pos[ko + k] = pos[ko + k - 1] + sp.vel * L.dt[p];
+    for (int k = 1; k < L.N[p]; ++k) pos[ko + k] = pos[ko + k - 1] + vel * L.dt[p];
   }
   ProbState* st = &d.st[b];
   st->J = 0; st->viol = 0; st->dV_exp = 0; st->reg = 0; st->cost_prev = 0;
@@ -1485,6 +1489,7 @@ __global__ __launch_bounds__(64) void k_cost(SolveParams sp, DevBufs d, int al_i
   const int b = prob_at(sp, d, gb.p0);
   ProbState* st = &d.st[b];
   if (!st->active) return;
+  const Cmd cm = cmd_of(d, b);
   const int lane = threadIdx.x;
   __shared__ real sc[MHPC_MAX_KNOTS];
   __shared__ acc sV[MAXP];
@@ -1503,10 +1508,10 @@ __global__ __launch_bounds__(64) void k_cost(SolveParams sp, DevBufs d, int al_i
     if (k < L.N[p] - 1) {
       const real* r = traj_ptr(sp, d, b, nom, kk);
       if (p < L.n_wb)
-        c = wb_running_cost(sp, mode, L.dt[p], refpos[kk], r, r + 14, r + 18, reb, st->delta[p],
+        c = wb_running_cost(sp, cm, mode, L.dt[p], refpos[kk], r, r + 14, r + 18, reb, st->delta[p],
                             st->eps_tq[p], st->eps_grf[p]);
       else
-        c = fb_running_cost(sp, mode, L.dt[p], refpos[kk], r, r + 6);
+        c = fb_running_cost(sp, cm, mode, L.dt[p], refpos[kk], r, r + 6);
     }
     sc[kk] = c;
   }
@@ -1520,7 +1525,7 @@ __global__ __launch_bounds__(64) void k_cost(SolveParams sp, DevBufs d, int al_i
     const real* x = traj_ptr(sp, d, b, nom, ko + N - 1);
     if (p < L.n_wb) {
       real rx[14];
-      wb_term_ref(sp, mode, refpos[ko + N - 1], rx);
+      wb_term_ref(cm, mode, refpos[ko + N - 1], rx);
       acc Phi = 0;
       for (int i = 0; i < 14; ++i) { const real e = x[i] - rx[i]; Phi += e * sp.cw.wQf[mode - 1][i] * e; }
       Phi = Phi * acc(0.5);
@@ -1535,7 +1540,7 @@ __global__ __launch_bounds__(64) void k_cost(SolveParams sp, DevBufs d, int al_i
       V += Phi;
     } else {
       real rx[6];
-      fb_term_ref(sp, refpos[ko + N - 1], rx);
+      fb_term_ref(cm, refpos[ko + N - 1], rx);
       acc Phi = 0;
       for (int i = 0; i < 6; ++i) { const real e = x[i] - rx[i]; Phi += e * sp.cw.fQf[mode - 1][i] * e; }
       V += Phi * acc(0.5);
@@ -1579,6 +1584,36 @@ __global__ void k_export(SolveParams sp, DevBufs d) {
   const long r = t - (long)b * per;
   const int nom = d.st[b].nom_slot;
   d.out[(size_t)b * per + r] = d.traj[(((size_t)b * sp.nslot + nom) * sp.NK) * KS + r];
+}
+
+// The tracking reference x of every knot of problems [b0, b0 + nb) into the staging buffer
+// (mhpc_get_reference_problems): the reference's ms_ref_*[p][k].x as ReferenceGen::generate_ref
+// leaves it (ReferenceGen.h:53-109), built by the helpers the cost kernels use.  Lane =
+// (problem, knot of the knot stride); a record's entries past the phase's state size are zero.
+__global__ void k_export_ref(SolveParams sp, DevBufs d, int b0, int nb) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)nb * sp.NK) return;
+  const int b = b0 + (int)(t / sp.NK), kk = (int)(t % sp.NK);
+  const Layout& L = d.lay[d.lid[b]];  // the problem's layout (per lane: not a hot kernel)
+  if (kk >= L.NK) return;
+  int p = 0;
+  while (p + 1 < L.P && kk >= L.ko[p + 1]) ++p;
+  const bool wb = p < L.n_wb, last = kk - L.ko[p] == L.N[p] - 1;
+  const Cmd cm = cmd_of(d, b);
+  const real pos = d.refpos[(size_t)b * sp.NK + kk];
+  real rx[14];
+#pragma unroll
+  for (int i = 0; i < 14; ++i) rx[i] = real(0.0);
+  if (wb) {
+    if (last) wb_term_ref(cm, L.mode[p], pos, rx);
+    else wb_run_ref(cm, pos, rx);
+  } else {
+    if (last) fb_term_ref(cm, pos, rx);
+    else fb_run_ref(cm, pos, rx);
+  }
+  real* o = d.out + ((size_t)b * sp.NK + kk) * KS;
+#pragma unroll
+  for (int i = 0; i < 14; ++i) o[i] = rx[i];
 }
 
 // ---- kernel-level parity hooks (batched CasADi replacements) -----------------------------
@@ -1876,6 +1911,12 @@ hipError_t launch_al_end(const SolveParams& sp, const DevBufs& d, int last, hipS
 hipError_t launch_export(const SolveParams& sp, const DevBufs& d, hipStream_t s) {
   const long total = (long)sp.B * sp.NK * KS;
   hipLaunchKernelGGL(k_export, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sp, d);
+  return hipGetLastError();
+}
+hipError_t launch_export_ref(const SolveParams& sp, const DevBufs& d, int b0, int nb, hipStream_t s) {
+  const long total = (long)nb * sp.NK;
+  hipLaunchKernelGGL(k_export_ref, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sp, d, b0,
+                     nb);
   return hipGetLastError();
 }
 hipError_t launch_eval_wb_dyn(int n, int mode, const real* x, const real* u, real* xd,

@@ -43,6 +43,7 @@ hipError_t launch_eps_rollout(const SolveParams&, const DevBufs&, int, const rea
                               real*, hipStream_t);
 hipError_t launch_al_end(const SolveParams&, const DevBufs&, int, hipStream_t);
 hipError_t launch_export(const SolveParams&, const DevBufs&, hipStream_t);
+hipError_t launch_export_ref(const SolveParams&, const DevBufs&, int, int, hipStream_t);
 hipError_t launch_reduce_counters(const SolveParams&, const DevBufs&, unsigned long long*,
                                   hipStream_t);
 hipError_t launch_eval_wb_dyn(int, int, const real*, const real*, real*, real*, hipStream_t);
@@ -112,6 +113,12 @@ struct Handle {
   // initial values reach the problems' state only there, so a solve in between
   // would mix new limits with old initial values -- refused until then
   bool params_changed = false;
+  // per-problem user commands [B] (vel, height) as the caller gave them (the device copy is
+  // cast to real), indexed by problem number; changed after the last initialize /
+  // update_problem: the position references still belong to the old speed, so a solve in
+  // between is refused like one after new constraint parameters
+  std::vector<double> cmd;
+  bool cmd_changed = false;
   float solve_ms = 0;
   unsigned long long* dcnt = nullptr;  // reduced counters per layout group [MAXL][NCNT]
   unsigned long long cnt[NCNT] = {};   // their sum over the groups
@@ -130,6 +137,7 @@ struct Handle {
   std::vector<int> lid, gidx;
   Layout* dlay = nullptr;
   int *dgidx = nullptr, *dlid = nullptr;
+  Cmd* dcmd = nullptr;
   // algorithmic byte model per problem of each layout
   std::vector<ByteModel> bym;
   // receding horizon (MHPCLocomotion::update_problem): each problem's current mode, the
@@ -271,12 +279,13 @@ static int validate(const mhpc_problem_desc* d) {
 static void free_bufs(Handle* h) {
   DevBufs& d = h->d;
   void* ptrs[] = {d.traj, d.refpos, d.K, d.du, d.G, d.par, d.px, d.x0, d.st, d.out, d.carry,
-                  h->dlay, h->dgidx, h->dlid};
+                  h->dlay, h->dgidx, h->dlid, h->dcmd};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   memset(&d, 0, sizeof d);
   h->dlay = nullptr;
   h->dgidx = h->dlid = nullptr;
+  h->dcmd = nullptr;
 }
 
 // A descriptor normalised for comparison (entries past its phases and reserved fields zero)
@@ -413,6 +422,7 @@ static int rebuild_groups(Handle* h) {
   h->d.lay = h->dlay;
   h->d.gidx = h->dgidx;
   h->d.lid = h->dlid;
+  h->d.cmd = h->dcmd;
   HIPCHK(hipMemcpyAsync(h->dlay, h->lays.data(), L * sizeof(Layout), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->dgidx, h->gidx.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->dlid, h->lid.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -541,8 +551,6 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
   if (hipDeviceGetAttribute(&sp.ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
       sp.ncu < 1)
     sp.ncu = 256;
-  sp.vel = desc->vel_cmd;
-  sp.height = desc->height_cmd;
   // line-search grid exactly as MultiPhaseDDP::forward_iteration generates it (:130-151)
   int nc = 0;
   for (double eps = 1; eps > pow(0.1, 10); eps *= opt->alpha) {
@@ -603,9 +611,25 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
   // zero x0 on the handle's own (non-blocking) stream: a null-stream memset would not be
   // ordered before mhpc_set_x0's copy on this stream
   if (e == hipSuccess) e = hipMemsetAsync(d.x0, 0, B * 14 * sizeof(real), h->stream);
+  // every problem starts with the descriptor's command
+  h->cmd.resize(2 * B);
+  for (size_t b = 0; b < B; ++b) {
+    h->cmd[2 * b] = desc->vel_cmd;
+    h->cmd[2 * b + 1] = desc->height_cmd;
+  }
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   int rc2 = e == hipSuccess ? MHPC_OK : fail(MHPC_ERR_DEVICE, std::string("allocation failed: ") + hipGetErrorString(e));
   if (!rc2) rc2 = rebuild_groups(h);  // one layout group; allocates the packed arrays
+  if (!rc2) {  // the command array (after the packed arrays: their placement stays as it was)
+    const std::vector<Cmd> hcmd(B, Cmd{(real)desc->vel_cmd, (real)desc->height_cmd});
+    e = hipMalloc((void**)&h->dcmd, B * sizeof(Cmd));
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(h->dcmd, hcmd.data(), B * sizeof(Cmd), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess)
+      rc2 = fail(MHPC_ERR_DEVICE, std::string("allocation failed: ") + hipGetErrorString(e));
+    h->d.cmd = h->dcmd;
+  }
   if (rc2) {
     api_destroy(h);
     return rc2;
@@ -728,6 +752,7 @@ int api_initialize(Handle* h) {
   h->initialized = true;
   h->x0_changed = false;
   h->params_changed = false;
+  h->cmd_changed = false;
   h->solved = false;
   return MHPC_OK;
 }
@@ -771,6 +796,7 @@ static DevBufs block_bufs(const DevBufs& d, const SolveParams& sp, size_t b0) {
   o.st += b0;
   o.out += b0 * NK * KS;
   o.carry += b0;
+  o.cmd += b0;
   return o;
 }
 
@@ -967,6 +993,8 @@ int api_solve(Handle* h, int32_t* status) {
   if (h->params_changed)
     return fail(MHPC_ERR_STATE,
                 "constraint parameters changed: call mhpc_initialize or mhpc_update_problem first");
+  if (h->cmd_changed)
+    return fail(MHPC_ERR_STATE, "commands changed: call mhpc_initialize or mhpc_update_problem first");
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipEventRecord(h->ev0, h->stream));
   int rc = solve_async(h);
@@ -1137,6 +1165,8 @@ int api_rollout_costs(Handle* h, int n_eps, const double* eps, double* J,
   if (!h || !eps || !J) return fail(MHPC_ERR_INVALID, "null argument");
   if (!h->initialized) return fail(MHPC_ERR_STATE, "not initialized");
   if (n_eps < 1 || n_eps > MHPC_MAX_ROLLOUT_EPS) return fail(MHPC_ERR_INVALID, "n_eps out of range");
+  if (h->cmd_changed)
+    return fail(MHPC_ERR_STATE, "commands changed: call mhpc_initialize or mhpc_update_problem first");
   HIPCHK(hipSetDevice(h->device));
   const size_t B = h->sp.B, n = B * (size_t)n_eps;
   real *deps = nullptr, *dJ = nullptr, *dv = nullptr;
@@ -1305,6 +1335,7 @@ int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const in
   h->solved = false;
   h->x0_changed = false;
   h->params_changed = false;
+  h->cmd_changed = false;
   return MHPC_OK;
 }
 
@@ -1353,6 +1384,65 @@ int api_get_problem_desc(Handle* h, int b, mhpc_problem_desc* desc) {
   if (!h || !desc) return fail(MHPC_ERR_INVALID, "null argument");
   if (b < 0 || b >= h->sp.B) return fail(MHPC_ERR_INVALID, "problem out of range");
   *desc = h->pl[b].desc;
+  desc->vel_cmd = h->cmd[2 * (size_t)b];
+  desc->height_cmd = h->cmd[2 * (size_t)b + 1];
+  return MHPC_OK;
+}
+
+// Per-problem user commands (the batch axis over MHPCUserParameters::usrcmd).  New values reach
+// the references at the next mhpc_initialize / mhpc_update_problem(s); until then an
+// initialised handle refuses to solve (cmd_changed).
+int api_set_commands(Handle* h, const double* vel, const double* height) {
+  if (!h) return fail(MHPC_ERR_INVALID, "null handle");
+  const size_t B = h->sp.B;
+  for (size_t b = 0; b < B; ++b)
+    if ((vel && !std::isfinite(vel[b])) || (height && !std::isfinite(height[b])))
+      return fail(MHPC_ERR_INVALID, "commands must be finite");
+  std::vector<double> nc = h->cmd;
+  for (size_t b = 0; b < B; ++b) {
+    if (vel) nc[2 * b] = vel[b];
+    if (height) nc[2 * b + 1] = height[b];
+  }
+  if (nc == h->cmd) return MHPC_OK;  // nothing changes: nothing pending
+  HIPCHK(hipSetDevice(h->device));
+  std::vector<Cmd> hc(B);
+  for (size_t b = 0; b < B; ++b) hc[b] = Cmd{(real)nc[2 * b], (real)nc[2 * b + 1]};
+  HIPCHK(hipMemcpyAsync(h->dcmd, hc.data(), B * sizeof(Cmd), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->cmd = nc;
+  if (h->initialized) h->cmd_changed = true;
+  return MHPC_OK;
+}
+int api_get_commands(Handle* h, double* vel, double* height) {
+  if (!h) return fail(MHPC_ERR_INVALID, "null handle");
+  for (size_t b = 0; b < (size_t)h->sp.B; ++b) {
+    if (vel) vel[b] = h->cmd[2 * b];
+    if (height) height[b] = h->cmd[2 * b + 1];
+  }
+  return MHPC_OK;
+}
+
+// The tracking reference x of one phase over a problem range, [count][N][xsize] (the cost
+// kernels' own reference helpers, k_export_ref, through the export staging buffer).
+int api_get_reference(Handle* h, int phase, int first, int count, double* xref) {
+  if (!h || !xref) return fail(MHPC_ERR_INVALID, "null argument");
+  if (!h->initialized) return fail(MHPC_ERR_STATE, "not initialized");
+  int n = 0, N = 0;
+  int rc = range_phase_shape(h, phase, first, count, &n, &N);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(launch_export_ref(h->sp, h->d, first, count, h->stream));
+  std::vector<real> buf;
+  for (int r0 = first; r0 < first + count;) {
+    const int ko = h->lays[h->lid[r0]].ko[phase];
+    int r1 = r0 + 1;
+    while (r1 < first + count && h->lays[h->lid[r1]].ko[phase] == ko) ++r1;
+    if ((rc = copy_rows(h, h->d.out, KS, ko, N, r0, r1 - r0, buf))) return rc;
+    double* o = xref + (size_t)(r0 - first) * N * n;
+    for (size_t i = 0; i < (size_t)(r1 - r0) * N; ++i)
+      for (int j = 0; j < n; ++j) o[i * n + j] = buf[i * KS + j];
+    r0 = r1;
+  }
   return MHPC_OK;
 }
 
@@ -1373,8 +1463,7 @@ int api_batch(Handle* h) { return h ? h->sp.B : 0; }
 
 int api_get_desc(Handle* h, mhpc_problem_desc* desc) {
   if (!h || !desc) return fail(MHPC_ERR_INVALID, "null argument");
-  *desc = h->pl[0].desc;
-  return MHPC_OK;
+  return api_get_problem_desc(h, 0, desc);
 }
 
 int api_get_counters(Handle* h, mhpc_counters* c) {

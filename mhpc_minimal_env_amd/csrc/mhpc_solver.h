@@ -22,6 +22,8 @@
 //   lay    [L]                 Layout table (read through the constant address space: scalar
 //          loads), gidx [B] the problems grouped by layout (group g = positions
 //          [go[g], go[g+1]) of gidx), lid [B] each problem's layout.
+//   cmd    [B][2]              user command (vel, height) of each problem (mhpc_set_commands),
+//          indexed by problem number: it follows a problem through every regrouping.
 #pragma once
 #include <stdint.h>
 
@@ -91,7 +93,6 @@ struct SolveParams {
   int go[MAXL + 1];
   int gpk[MAXL], gpi[MAXL];  // partials knot / impact work items per problem of each group
   int pmax;                  // most phases of any layout
-  real vel, height;
   int n_cand, nslot;
   real eps[MAXC];          // line-search grid 1, alpha, alpha^2, ... (host libm)
   real gamma, DDP_thresh, AL_thresh, update_penalty, update_relax, update_regularization,
@@ -111,6 +112,12 @@ struct SolveParams {
   // parameters (ConstraintsBase.h:11-50 / MHPCConstraints.cpp:14-88): mhpc_set_cost_weights /
   // mhpc_set_constraint_params; read by every kernel from its parameter block
   CostParams cw;
+};
+
+// User command of one problem (the reference's MHPCUserParameters::usrcmd of one controller,
+// handed to ReferenceGen by build_problem, MHPCLocomotion.cpp:98-103): DevBufs::cmd[b].
+struct Cmd {
+  real vel, height;
 };
 
 // Costs, their sums and the expected cost change are accumulated and compared in fp64 in
@@ -188,6 +195,7 @@ struct DevBufs {
   const Layout* lay;  // [ngrp] layout table
   const int* gidx;    // [B] problems grouped by layout
   const int* lid;     // [B] layout of each problem
+  const Cmd* cmd;     // [B] user command of each problem
 };
 
 }  // namespace MHPC_NS

@@ -341,6 +341,44 @@ class MHPCLocomotion:
                    "mhpc_update_problems")
         self._refresh_descs()
 
+    # -- per-problem user commands: the batch axis over USRCMD ------------------------------
+    def _command_array(self, v, name: str):
+        """None, a scalar (broadcast over the batch) or [batch] values, each rounded through
+        f32() as desc_from_params rounds USRCMD's float members."""
+        if v is None:
+            return None
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(self.batch, float(a))
+        if a.shape != (self.batch,):
+            raise ValueError(f"{name} must be a scalar or have one entry per problem")
+        return np.ascontiguousarray([f32(x) for x in a], dtype=np.float64)
+
+    def set_commands(self, vel=None, height=None):
+        """mhpc_set_commands: problem b tracks speed vel[b] at body height height[b] (each a
+        scalar or [batch]; None keeps the current values) -- the usrcmd of one controller per
+        problem (MHPCLocomotion.cpp:98-103).  Takes effect at the next initialization() /
+        update_problem(s); an initialised handle refuses to solve until then."""
+        v, hgt = self._command_array(vel, "vel"), self._command_array(height, "height")
+        capi.check(capi.lib().mhpc_set_commands(self._h, capi.dptr(v), capi.dptr(hgt)),
+                   "mhpc_set_commands")
+
+    def get_commands(self) -> dict:
+        out = {"vel": np.zeros(self.batch), "height": np.zeros(self.batch)}
+        capi.check(capi.lib().mhpc_get_commands(self._h, capi.dptr(out["vel"]),
+                                                capi.dptr(out["height"])), "mhpc_get_commands")
+        return out
+
+    def get_reference_problems(self, p: int, first: int, count: int) -> np.ndarray:
+        """The tracking reference x of phase p for problems [first, first + count),
+        [count][N][xsize] (ReferenceGen.h:53-109; one phase shape over the range)."""
+        d = self.descs[first] if self.descs else self.desc
+        xref = np.zeros((count, d.N[p], d.xsize(p)))
+        capi.check(capi.lib().mhpc_get_reference_problems(self._h, p, int(first), int(count),
+                                                          capi.dptr(xref)),
+                   "mhpc_get_reference_problems")
+        return xref
+
     def problem_desc(self, b: int) -> capi.ProblemDesc:
         import ctypes
         d = capi.ProblemDesc()

@@ -20,6 +20,14 @@ def shard_offsets(global_batch: int, world: int, rank: int) -> Tuple[int, int]:
     return offset, count
 
 
+def shard_rows(a, world: int, rank: int) -> np.ndarray:
+    """Rank's rows of a per-problem array of the global batch (x0, or the vel / height arrays
+    of set_commands): the block shard_offsets gives."""
+    a = np.asarray(a)
+    offset, count = shard_offsets(a.shape[0], world, rank)
+    return a[offset:offset + count]
+
+
 def summary_dtype(n_phases: int, trace_len: int):
     return np.dtype([("index", np.int64), ("J", np.float64), ("viol", np.float64),
                      ("status", np.int32), ("V", np.float64, (n_phases,)),
