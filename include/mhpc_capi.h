@@ -40,6 +40,11 @@
  *                        mhpc_get_commands reads them back
  *   mhpc_get_reference_problems  ReferenceGen::generate_ref's ms_ref_*[p][k].x
  *                        (ReferenceGen.h:53-109): the tracking reference the costs use
+ *   mhpc_rollout_policy  set_initial_condition(x) + forward_sweep_dynamics_only(0)
+ *                        (SinglePhase.cpp:117-144, chained over phases through phase_transition by
+ *                        MultiPhaseDDP.cpp:56-76): the solved feedback policy run from a measured
+ *                        state; mhpc_rollout_policy_phase its trajectories, mhpc_advance_x0 the
+ *                        same as the next tick's set_initial_condition, mhpc_get_x0 reads _x0
  */
 #ifndef MHPC_CAPI_H
 #define MHPC_CAPI_H
@@ -292,6 +297,47 @@ int mhpc_get_cost_gradients_problems(mhpc_handle* h, int phase, int first, int c
 #define MHPC_MAX_ROLLOUT_EPS 4096
 int mhpc_rollout_costs(mhpc_handle* h, int n_eps, const double* eps, double* J, double* viol,
                        float* ms);
+
+/* ---- policy rollouts: the batch axis over measured / perturbed start states ------------
+ * A solve leaves a feedback policy on the device: per knot a nominal x, u and a gain K, run as
+ * u = u_k + K_k (x - x_k) from the state the robot is actually in.  The reference spells this
+ * set_initial_condition(x) followed by forward_sweep_dynamics_only(0)
+ * (HSDDPSolver/source/SinglePhase.cpp:117-144; MultiPhaseDDP.cpp:56-76 chains it over phases
+ * through phase_transition).  Here every problem runs n_samples start states of the caller's
+ * choosing through its policy in one launch (lane = (problem, sample), the line search's own
+ * model, costs and transitions, bit for bit mhpc_rollout_costs at step size 0 from that state).
+ * Nothing the handle owns is modified, except x0 by mhpc_advance_x0.  All four return
+ * MHPC_ERR_STATE before mhpc_initialize (or after mhpc_set_layouts until the next one) and, but
+ * mhpc_get_x0, while commands or constraint parameters are pending (as mhpc_rollout_costs); a
+ * pending x0 does not block them, they do not read the handle's x0.  MHPC_ERR_INVALID: a null
+ * required pointer, n_samples outside 1..MHPC_MAX_POLICY_SAMPLES, n_phases out of range, a
+ * non-finite entry of xs / dx, a bad problem range or a ragged phase shape.  A refused call
+ * changes nothing. */
+#define MHPC_MAX_POLICY_SAMPLES 4096
+/* xs: [batch][n_samples][r], r = the x0 row length of mhpc_set_x0 (14 if any layout has a
+ * whole-body phase, else 6; an SRB-only problem reads the first 6).  n_phases: 1..the
+ * smallest phase count over the problems' layouts, or 0 = every phase of each problem.
+ * J, viol: [batch][n_samples]; x_end: [batch][n_samples][r]; viol, x_end, ms may be NULL.
+ * J sums the rolled phases' costs, viol = sqrt(sum h^2) over them.  x_end is the state after the
+ * last rolled phase's transition: after a whole-body phase the full 14-entry state after the
+ * impact, before the SRB projection (the robot's state, usable as the next x0); after an SRB
+ * phase 6 entries, the rest of the row zero; after a problem's last phase its terminal state. */
+int mhpc_rollout_policy(mhpc_handle* h, int n_samples, const double* xs, int n_phases,
+                        double* J, double* viol, double* x_end, float* ms);
+/* Trajectories of `phase` (rolled from phase 0) for problems [first, first+count), whose
+ * phase must have one shape (as mhpc_get_phase_problems).  xs: [count][n_samples][r];
+ * x: [count][n_samples][N][xsize], u, y: [count][n_samples][N][4] (last knot's u, y rows
+ * zero; SRB y zero); any output may be NULL. */
+int mhpc_rollout_policy_phase(mhpc_handle* h, int phase, int first, int count, int n_samples,
+                              const double* xs, double* x, double* u, double* y);
+/* Device-side closed loop: x0[b] <- x_end of one policy rollout of problem b over n_phases
+ * (>= 1) phases from x0[b] + dx[b] (dx [batch][r], NULL = zero), no host copy of states.
+ * Afterwards the handle is as after mhpc_set_x0 (mhpc_solve refuses until
+ * mhpc_update_problem(s) / mhpc_initialize).  MHPC_ERR_INVALID if, for a problem that has a
+ * whole-body phase, phase n_phases-1 is an SRB phase (its end state cannot start a
+ * whole-body horizon). */
+int mhpc_advance_x0(mhpc_handle* h, int n_phases, const double* dx);
+int mhpc_get_x0(mhpc_handle* h, double* x0);   /* [batch][r], the device's current rows */
 
 /* Per-kernel device timing (HIP events around every launch on the handle's stream) and the
  * algorithmic HBM bytes each kernel must move (model in DESIGN.md §Roofline), accumulated

@@ -327,6 +327,66 @@ class MHPCLocomotion {
     height.assign(batch_, 0.0);
     check(mhpc_get_commands(h_, vel.data(), height.data()), "mhpc_get_commands");
   }
+  // extension: the solved feedback policy u = u_nom + K (x - x_nom) run from measured or
+  // perturbed start states -- the reference's set_initial_condition(x) followed by
+  // forward_sweep_dynamics_only(0) (SinglePhase.cpp:117-144, MultiPhaseDDP.cpp:56-76), for
+  // n_samples states per problem in one launch.  xs [batch][n_samples][x0_width()]; n_phases
+  // phases are rolled (0: every phase of each problem).  J, viol [batch][n_samples], x_end
+  // [batch][n_samples][x0_width()]: the state after the last rolled phase's transition
+  // (post-impact whole-body state, usable as the next x0).  Nothing is modified.
+  struct PolicyRollout { int n_samples = 0; std::vector<double> J, viol, x_end; float ms = 0; };
+  PolicyRollout rollout_policy(const std::vector<double>& xs, int n_phases = 0) {
+    const size_t row = (size_t)batch_ * xw_;
+    if (xs.empty() || xs.size() % row != 0)
+      throw std::runtime_error("rollout_policy: xs must be [batch][n_samples][x0_width()]");
+    PolicyRollout r;
+    r.n_samples = (int)(xs.size() / row);
+    const size_t n = (size_t)batch_ * r.n_samples;
+    r.J.assign(n, 0.0);
+    r.viol.assign(n, 0.0);
+    r.x_end.assign(n * xw_, 0.0);
+    check(mhpc_rollout_policy(h_, r.n_samples, xs.data(), n_phases, r.J.data(), r.viol.data(),
+                              r.x_end.data(), &r.ms),
+          "mhpc_rollout_policy");
+    return r;
+  }
+  // trajectories of phase p under the policy (rolled from phase 0) for problems
+  // [first, first + count): x [count][n_samples][N][xsize], u, y [count][n_samples][N][4]
+  // (the range's phase must have one shape); xs [count][n_samples][x0_width()]
+  struct PolicyPhase { int n_samples = 0, N = 0, xsize = 0; std::vector<double> x, u, y; };
+  PolicyPhase rollout_policy_phase(int p, int first, int count, const std::vector<double>& xs) {
+    const size_t row = (size_t)count * xw_;
+    if (count < 1 || xs.empty() || xs.size() % row != 0)
+      throw std::runtime_error("rollout_policy_phase: xs must be [count][n_samples][x0_width()]");
+    PolicyPhase r;
+    r.n_samples = (int)(xs.size() / row);
+    const mhpc_problem_desc d = problem_desc(first);
+    check(mhpc_phase_dims(&d, p, &r.xsize, &r.N), "mhpc_phase_dims");
+    const size_t n = (size_t)count * r.n_samples * r.N;
+    r.x.assign(n * r.xsize, 0.0);
+    r.u.assign(n * 4, 0.0);
+    r.y.assign(n * 4, 0.0);
+    check(mhpc_rollout_policy_phase(h_, p, first, count, r.n_samples, xs.data(), r.x.data(),
+                                    r.u.data(), r.y.data()),
+          "mhpc_rollout_policy_phase");
+    return r;
+  }
+  // device-side closed loop: every problem's initial condition becomes the end state of one
+  // policy rollout over n_phases phases from x0 + dx (dx [batch][x0_width()], empty: zero), with
+  // no host copy of states; update_problem() / initialization() follow as after
+  // set_initial_conditions()
+  void advance_x0(int n_phases = 1, const std::vector<double>& dx = {}) {
+    if (!dx.empty() && dx.size() != (size_t)batch_ * xw_)
+      throw std::runtime_error("advance_x0: dx must be [batch][x0_width()]");
+    check(mhpc_advance_x0(h_, n_phases, dx.empty() ? nullptr : dx.data()), "mhpc_advance_x0");
+    x0_ = get_x0();  // what update_problem() / initialization() hand back
+  }
+  // the device's current initial states [batch][x0_width()]
+  std::vector<double> get_x0() {
+    std::vector<double> x0((size_t)batch_ * xw_);
+    check(mhpc_get_x0(h_, x0.data()), "mhpc_get_x0");
+    return x0;
+  }
   // the tracking reference x of phase p for problems [first, first + count): [count][N][xsize]
   // (ReferenceGen.h:53-109; the range's phase must have one shape)
   std::vector<double> get_reference_problems(int p, int first, int count) {

@@ -19,6 +19,7 @@ MHPC_MAX_LAYOUTS = 32
 MHPC_TRACE_LEN = 64
 MHPC_NUM_KERNELS = 7
 MHPC_MAX_ROLLOUT_EPS = 4096
+MHPC_MAX_POLICY_SAMPLES = 4096
 
 MHPC_OK = 0
 MHPC_ERR_INVALID = 1
@@ -208,6 +209,12 @@ SIGNATURES = [
     ("mhpc_max_phases", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     ("mhpc_rollout_costs", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _DP, _DP, _DP,
                                           ctypes.POINTER(ctypes.c_float)]),
+    ("mhpc_rollout_policy", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _DP, ctypes.c_int, _DP,
+                                           _DP, _DP, ctypes.POINTER(ctypes.c_float)]),
+    ("mhpc_rollout_policy_phase", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_int, _DP, _DP, _DP, _DP]),
+    ("mhpc_advance_x0", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _DP]),
+    ("mhpc_get_x0", ctypes.c_int, [ctypes.c_void_p, _DP]),
     ("mhpc_destroy", None, [ctypes.c_void_p]),
     ("mhpc_kernel_name", ctypes.c_char_p, [ctypes.c_int]),
     ("mhpc_set_profiling", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),

@@ -15,6 +15,12 @@ int api_batch(Handle* h);
 int api_get_scalars(Handle* h, double* J, double* dV_exp, double* viol, double* V_phase,
                     double* dV_phase, int32_t* trace);
 int api_rollout_costs(Handle* h, int n_eps, const double* eps, double* J, double* viol, float* ms);
+int api_rollout_policy(Handle* h, int n_samples, const double* xs, int n_phases, double* J,
+                       double* viol, double* x_end, float* ms);
+int api_rollout_policy_phase(Handle* h, int phase, int first, int count, int n_samples,
+                             const double* xs, double* x, double* u, double* y);
+int api_advance_x0(Handle* h, int n_phases, const double* dx);
+int api_get_x0(Handle* h, double* x0);
 int api_get_cost_gradients(Handle* h, int phase, int first, int count, double* lx, double* Phix);
 int api_update_problem(Handle* h, const mhpc_gait* gait);
 int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const int32_t* gait_of,

@@ -124,6 +124,19 @@ extern "C" int mhpc_rollout_costs(mhpc_handle* h, int n_eps, const double* eps, 
                                   double* viol, float* ms) {
   FWD(rollout_costs, n_eps, eps, J, viol, ms);
 }
+extern "C" int mhpc_rollout_policy(mhpc_handle* h, int n_samples, const double* xs, int n_phases,
+                                   double* J, double* viol, double* x_end, float* ms) {
+  FWD(rollout_policy, n_samples, xs, n_phases, J, viol, x_end, ms);
+}
+extern "C" int mhpc_rollout_policy_phase(mhpc_handle* h, int phase, int first, int count,
+                                         int n_samples, const double* xs, double* x, double* u,
+                                         double* y) {
+  FWD(rollout_policy_phase, phase, first, count, n_samples, xs, x, u, y);
+}
+extern "C" int mhpc_advance_x0(mhpc_handle* h, int n_phases, const double* dx) {
+  FWD(advance_x0, n_phases, dx);
+}
+extern "C" int mhpc_get_x0(mhpc_handle* h, double* x0) { FWD(get_x0, x0); }
 extern "C" int mhpc_get_cost_gradients(mhpc_handle* h, int phase, double* lx, double* Phix) {
   int B = 0;
   if (h) B = h->precision == 32 ? mhpc32::api_batch((mhpc32::Handle*)h->impl)

@@ -952,6 +952,169 @@ __global__ __launch_bounds__(64) void k_eps_rollout(SolveParams sp, DevBufs d, i
   vo[t] = real(sqrt(viol2));
 }
 
+constexpr int PREC_W = 22;  // k_policy_rollout's knot record: x 14, u 4, y 4
+// ============================================================================================
+// k_policy_rollout: the solved feedback policy u = u_nom + K (x - x_nom) run from start states
+// of the caller's choosing -- the reference's set_initial_condition(x) followed by
+// forward_sweep_dynamics_only(0) (SinglePhase.cpp:117-144, MultiPhaseDDP.cpp:56-76).  Lane =
+// (problem, sample), the sample index fastest: the lanes of a wave read one problem's nominal
+// record, K, du and refpos at wave-uniform addresses (a wave straddles two problems when
+// n_s is no multiple of 64); blocks by layout group as k_eps_rollout.  Problems outside
+// [b0, b0 + nb) are skipped.  xs [nb][n_s][14] start states, dx (double [nb][n_s][14], or null)
+// added to them in double; n_phases phases are rolled (0: every phase of the problem); eps
+// is 0 at run time, kept in the control so that it rounds as k_eps_rollout's (the sign of a
+// zero included): the per-knot body is k_eps_rollout's, device function for device function
+// and operation for operation, and J, viol equal mhpc_rollout_costs at step size 0 from the
+// same state bit for bit (tests/test_gpu_policy.py).  No memory index depends on a state
+// value: a diverged sample produces non-finite numbers and nothing worse.
+// Outputs, each optional: Jo, vo [nb][n_s] (sum of the rolled phases' costs, sqrt of the sum of
+// their h^2); xe [nb][n_s][14], the state after the last rolled phase's transition -- after a WB
+// phase the full state after wb_impact and before the SRB projection, after an SRB phase its 6
+// entries and zeros, after the problem's last phase (no transition) that phase's terminal
+// state; xe may alias xs (mhpc_advance_x0): a lane reads its row before it writes it.
+// REC: rec [nb][N][PREC_W][n_s], the records of phase rec_p, which is then the last phase
+// rolled -- entry j (x 0..13, u 14..17, y 18..21) of knot k, the sample fastest so that a
+// wave's stores of one entry coalesce; the last knot has no u, y (not written), nor have SRB
+// knots a y.
+// ============================================================================================
+template <bool REC>
+__global__ __launch_bounds__(64) void k_policy_rollout(SolveParams sp, DevBufs d, int n_s, int b0,
+                                                       int nb, const real* xs, const double* dx,
+                                                       real eps, int n_phases, int rec_p, real* Jo,
+                                                       real* vo, real* xe_v, real* rec_v) {
+  long t0 = 0;
+  const int g = block_group_items(sp, nullptr, n_s, blockIdx.x, 64, &t0);
+  if (g < 0) return;
+  const Layout& L = layout_of(d, g);
+  const long tg = t0 + threadIdx.x;  // item within the group
+  if (tg >= (long)(sp.go[g + 1] - sp.go[g]) * n_s) return;
+  const int pos = sp.go[g] + (int)(tg / n_s), e = (int)(tg % n_s);
+  const int b = prob_at(sp, d, pos);
+  if (b < b0 || b >= b0 + nb) return;
+  const size_t t = (size_t)(b - b0) * n_s + e;  // sample index [problem of the range][sample]
+  real x[14];
+  for (int i = 0; i < 14; ++i) x[i] = xs[t * 14 + i];
+  if (dx)
+    for (int i = 0; i < 14; ++i) x[i] = real((double)x[i] + dx[t * 14 + i]);
+  const int Pn = REC ? rec_p + 1 : (n_phases > 0 && n_phases < L.P ? n_phases : L.P);
+  const ProbState* st = &d.st[b];
+  const Cmd cm = cmd_of(d, b);
+  const int nom = st->nom_slot;
+  const bool reb = st->reb_active != 0;
+  real* const xe = xe_v ? xe_v + t * 14 : nullptr;
+  real* const rec = REC ? rec_v + (size_t)(b - b0) * L.N[rec_p] * PREC_W * n_s + e : nullptr;
+  const size_t rs = (size_t)n_s;  // stride of one record entry: the sample index is fastest
+  acc J = 0, viol2 = 0;
+  for (int p = 0; p < Pn; ++p) {
+    const int mode = L.mode[p], N = L.N[p], ko = L.ko[p];
+    const real dt = L.dt[p];
+    const real* refpos = d.refpos + (size_t)b * sp.NK + ko;
+    acc V = 0;
+    real h = 0;
+    if (p < L.n_wb) {
+      const real delta = st->delta[p], etq = st->eps_tq[p], egr = st->eps_grf[p];
+      for (int k = 0; k < N - 1; ++k) {
+        const real* nk = traj_ptr(sp, d, b, nom, ko + k);
+        const real* Kk = d.K + ((size_t)b * sp.NK + ko + k) * 56;
+        const real* duk = d.du + ((size_t)b * sp.NK + ko + k) * 4;
+        real u[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const real fb = fb_dot<14>(Kk + i * 14, x, nk);
+          u[i] = (nk[14 + i] + eps * duk[i]) + fb;
+        }
+        real xd[14], y[4];
+        wb_dynamics<real>(x, u, mode, xd, y);
+        if (REC && p == rec_p) {
+          real* r = rec + (size_t)k * PREC_W * rs;
+          for (int i = 0; i < 14; ++i) r[i * rs] = x[i];
+          for (int i = 0; i < 4; ++i) { r[(14 + i) * rs] = u[i]; r[(18 + i) * rs] = y[i]; }
+        }
+        V += wb_running_cost(sp, cm, mode, dt, refpos[k], x, u, y, reb, delta, etq, egr);
+#pragma unroll
+        for (int i = 0; i < 14; ++i) x[i] = x[i] + xd[i] * dt;
+      }
+      if (REC && p == rec_p) {
+        real* r = rec + (size_t)(N - 1) * PREC_W * rs;
+        for (int i = 0; i < 14; ++i) r[i * rs] = x[i];
+      }
+      {
+        MHPC_NO_FMA_COST
+        real rx[14];
+        wb_term_ref(cm, mode, refpos[N - 1], rx);
+        acc Phi = 0;
+        for (int i = 0; i < 14; ++i) { const real ee = x[i] - rx[i]; Phi += ee * sp.cw.wQf[mode - 1][i] * ee; }
+        Phi = Phi * acc(0.5);
+        if (ntc_of(mode, true)) {
+          h = mode == 2 ? wb_touchdown_value<kFront>(x) : wb_touchdown_value<kBack>(x);
+          if (sp.AL_active) {
+            const acc sg = st->sigma[p], lam = st->lambda[p];
+            const acc sh2 = sg * h / 2;
+            Phi += 50 * (sh2 * sh2 + lam * h);
+          }
+        }
+        V += Phi;
+      }
+      if (p + 1 < L.P) {
+        if (mode == 2 || mode == 4) {
+          real xp[14], lam[2];
+          wb_impact<real>(x, mode == 2 ? kFront : kBack, xp, lam);
+          for (int i = 0; i < 14; ++i) x[i] = xp[i];
+        }
+        // the robot's state after the last rolled phase: post-impact, before the SRB projection
+        if (xe && p == Pn - 1)
+          for (int i = 0; i < 14; ++i) xe[i] = x[i];
+        if (p + 1 >= L.n_wb) {
+          const real t0 = x[0], t1 = x[1], t2 = x[2], t7 = x[7], t8 = x[8], t9 = x[9];
+          x[0] = t0; x[1] = t1; x[2] = t2; x[3] = t7; x[4] = t8; x[5] = t9;
+        }
+      } else if (xe) {  // the problem's last phase: no transition
+        for (int i = 0; i < 14; ++i) xe[i] = x[i];
+      }
+    } else {
+      real f[4], sc[2];
+      plan_foothold(x, dt * N, mode, f);
+      srb_contact(mode, sc);
+      for (int k = 0; k < N - 1; ++k) {
+        const real* nk = traj_ptr(sp, d, b, nom, ko + k);
+        const real* Kk = d.K + ((size_t)b * sp.NK + ko + k) * 56;
+        const real* duk = d.du + ((size_t)b * sp.NK + ko + k) * 4;
+        real u[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const real fb = fb_dot<6>(Kk + i * 6, x, nk);
+          u[i] = (nk[6 + i] + eps * duk[i]) + fb;
+        }
+        real xd[6];
+        srb_dynamics(x, u, f, sc, xd);
+        if (REC && p == rec_p) {
+          real* r = rec + (size_t)k * PREC_W * rs;
+          for (int i = 0; i < 6; ++i) r[i * rs] = x[i];
+          for (int i = 0; i < 4; ++i) r[(14 + i) * rs] = u[i];
+        }
+        V += fb_running_cost(sp, cm, mode, dt, refpos[k], x, u);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) x[i] = x[i] + xd[i] * dt;
+      }
+      if (REC && p == rec_p) {
+        real* r = rec + (size_t)(N - 1) * PREC_W * rs;
+        for (int i = 0; i < 6; ++i) r[i * rs] = x[i];
+      }
+      if (xe && p == Pn - 1)
+        for (int i = 0; i < 14; ++i) xe[i] = i < 6 ? x[i] : real(0.0);
+      real rx[6];
+      fb_term_ref(cm, refpos[N - 1], rx);
+      acc Phi = 0;
+      for (int i = 0; i < 6; ++i) { const real ee = x[i] - rx[i]; Phi += ee * sp.cw.fQf[mode - 1][i] * ee; }
+      V += Phi * acc(0.5);
+    }
+    J += V;
+    viol2 += acc(h) * h;
+  }
+  if (Jo) Jo[t] = real(J);
+  if (vo) vo[t] = real(sqrt(viol2));
+}
+
 // ============================================================================================
 // k_cost_grad: the running-cost gradient lx of every knot and the terminal-cost gradient
 // Phix of phase p as the last partials evaluation left them (rcost[k].lx, tcost.Phix;
@@ -1855,6 +2018,20 @@ hipError_t launch_eps_rollout(const SolveParams& sp, const DevBufs& d, int n_eps
                               const real* eps, real* J, real* viol, hipStream_t s) {
   hipLaunchKernelGGL(k_eps_rollout, dim3(grid_items(sp, nullptr, n_eps, 64)), dim3(64), 0, s, sp, d,
                      n_eps, eps, J, viol);
+  return hipGetLastError();
+}
+// eps is the control's step size, 0 for the policy; rec != null: the recording instantiation
+hipError_t launch_policy_rollout(const SolveParams& sp, const DevBufs& d, int n_s, int b0, int nb,
+                                 const real* xs, const double* dx, int n_phases, int rec_p,
+                                 real* J, real* viol, real* xe, real* rec, hipStream_t s) {
+  const dim3 grid(grid_items(sp, nullptr, n_s, 64));
+  const real eps = 0;
+  if (rec)
+    hipLaunchKernelGGL(k_policy_rollout<true>, grid, dim3(64), 0, s, sp, d, n_s, b0, nb, xs, dx, eps,
+                       n_phases, rec_p, J, viol, xe, rec);
+  else
+    hipLaunchKernelGGL(k_policy_rollout<false>, grid, dim3(64), 0, s, sp, d, n_s, b0, nb, xs, dx,
+                       eps, n_phases, rec_p, J, viol, xe, rec);
   return hipGetLastError();
 }
 hipError_t launch_cost_grad(const SolveParams& sp, const DevBufs& d, int g, int p, int N, int b0,

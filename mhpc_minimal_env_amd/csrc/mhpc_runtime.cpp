@@ -37,10 +37,13 @@ hipError_t launch_store(const SolveParams&, const DevBufs&, real*, int, int, int
 // N_TIMESTEPS_MAX (MHPCLocomotion.h): knots per phase buffer; record = x,u,y + K + du + G
 constexpr int kPhaseBufKnots = 110;
 constexpr int kStoreRec = KS + 56 + 4 + 14;
+constexpr int PREC_W = 22;  // k_policy_rollout's knot record: x 14, u 4, y 4
 hipError_t launch_cost_grad(const SolveParams&, const DevBufs&, int, int, int, int, int, real*, real*,
                             hipStream_t);
 hipError_t launch_eps_rollout(const SolveParams&, const DevBufs&, int, const real*, real*,
                               real*, hipStream_t);
+hipError_t launch_policy_rollout(const SolveParams&, const DevBufs&, int, int, int, const real*,
+                                 const double*, int, int, real*, real*, real*, real*, hipStream_t);
 hipError_t launch_al_end(const SolveParams&, const DevBufs&, int, hipStream_t);
 hipError_t launch_export(const SolveParams&, const DevBufs&, hipStream_t);
 hipError_t launch_export_ref(const SolveParams&, const DevBufs&, int, int, hipStream_t);
@@ -1196,6 +1199,189 @@ int api_rollout_costs(Handle* h, int n_eps, const double* eps, double* J,
   cleanup();
   if (e != hipSuccess) return fail(MHPC_ERR_DEVICE, std::string("mhpc_rollout_costs: ") + hipGetErrorString(e));
   if (ms) *ms = t;
+  return MHPC_OK;
+}
+
+// ---- policy rollouts from states of the caller's choosing (k_policy_rollout) ---------------
+// Call-order rules shared by the policy entry points: an initialised handle (mhpc_set_layouts
+// un-initialises it) with no commands or constraint parameters pending, as mhpc_rollout_costs;
+// a pending x0 does not matter to the rollouts, which never read the handle's x0.
+static int policy_ready(const Handle* h) {
+  if (!h->initialized) return fail(MHPC_ERR_STATE, "not initialized");
+  if (h->cmd_changed)
+    return fail(MHPC_ERR_STATE, "commands changed: call mhpc_initialize or mhpc_update_problem first");
+  if (h->params_changed)
+    return fail(MHPC_ERR_STATE,
+                "constraint parameters changed: call mhpc_initialize or mhpc_update_problem first");
+  return MHPC_OK;
+}
+// Start states xs [count][n_s][r] of problems [first, first + count) as the device rows of 14
+// (mhpc_set_x0's padding and rounding); MHPC_ERR_INVALID for a non-finite entry.
+static int policy_pack(const Handle* h, int first, int count, int n_s, const double* xs,
+                       std::vector<real>& out) {
+  const int r = x0_row(h);
+  for (size_t i = 0; i < (size_t)count * n_s * r; ++i)
+    if (!std::isfinite(xs[i])) return fail(MHPC_ERR_INVALID, "start states must be finite");
+  out.assign((size_t)count * n_s * 14, real(0));
+  for (int b = 0; b < count; ++b) {
+    const int nb = h->lays[h->lid[first + b]].n_wb > 0 ? 14 : 6;
+    for (int e = 0; e < n_s; ++e) {
+      const size_t t = (size_t)b * n_s + e;
+      for (int i = 0; i < nb; ++i) out[t * 14 + i] = (real)xs[t * r + i];
+    }
+  }
+  return MHPC_OK;
+}
+static int min_phases(const Handle* h) {
+  int P = MAXP;
+  for (const Layout& L : h->lays) P = std::min(P, L.P);
+  return P;
+}
+
+int api_rollout_policy(Handle* h, int n_samples, const double* xs, int n_phases, double* J,
+                       double* viol, double* x_end, float* ms) {
+  if (!h || !xs || !J) return fail(MHPC_ERR_INVALID, "null argument");
+  int rc = policy_ready(h);
+  if (rc) return rc;
+  if (n_samples < 1 || n_samples > MHPC_MAX_POLICY_SAMPLES)
+    return fail(MHPC_ERR_INVALID, "n_samples out of range");
+  if (n_phases < 0 || n_phases > min_phases(h))
+    return fail(MHPC_ERR_INVALID, "n_phases out of range");
+  const int B = h->sp.B, r = x0_row(h);
+  const size_t n = (size_t)B * n_samples;
+  std::vector<real> hxs, hJ(n), hv(n), hxe(x_end ? n * 14 : 0);
+  if ((rc = policy_pack(h, 0, B, n_samples, xs, hxs))) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  real *dxs = nullptr, *dJ = nullptr, *dv = nullptr, *dxe = nullptr;
+  auto cleanup = [&]() {
+    if (dxs) (void)hipFree(dxs);
+    if (dJ) (void)hipFree(dJ);
+    if (dv) (void)hipFree(dv);
+    if (dxe) (void)hipFree(dxe);
+  };
+  hipError_t e = hipMalloc((void**)&dxs, n * 14 * sizeof(real));
+  if (e == hipSuccess) e = hipMalloc((void**)&dJ, n * sizeof(real));
+  if (e == hipSuccess) e = hipMalloc((void**)&dv, n * sizeof(real));
+  if (e == hipSuccess && x_end) e = hipMalloc((void**)&dxe, n * 14 * sizeof(real));
+  if (e == hipSuccess) e = hipMemcpyAsync(dxs, hxs.data(), n * 14 * sizeof(real), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipEventRecord(h->ev0, h->stream);
+  if (e == hipSuccess)
+    e = launch_policy_rollout(h->sp, h->d, n_samples, 0, B, dxs, nullptr, n_phases, 0, dJ, dv, dxe,
+                              nullptr, h->stream);
+  if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(hJ.data(), dJ, n * sizeof(real), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(hv.data(), dv, n * sizeof(real), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && x_end)
+    e = hipMemcpyAsync(hxe.data(), dxe, n * 14 * sizeof(real), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  float t = 0;
+  if (e == hipSuccess) e = hipEventElapsedTime(&t, h->ev0, h->ev1);
+  cleanup();
+  if (e != hipSuccess) return fail(MHPC_ERR_DEVICE, std::string("mhpc_rollout_policy: ") + hipGetErrorString(e));
+  for (size_t i = 0; i < n; ++i) {
+    J[i] = hJ[i];
+    if (viol) viol[i] = hv[i];
+    if (x_end)
+      for (int j = 0; j < r; ++j) x_end[i * r + j] = hxe[i * 14 + j];
+  }
+  if (ms) *ms = t;
+  return MHPC_OK;
+}
+
+int api_rollout_policy_phase(Handle* h, int phase, int first, int count, int n_samples,
+                             const double* xs, double* x, double* u, double* y) {
+  if (!h || !xs) return fail(MHPC_ERR_INVALID, "null argument");
+  int rc = policy_ready(h);
+  if (rc) return rc;
+  if (n_samples < 1 || n_samples > MHPC_MAX_POLICY_SAMPLES)
+    return fail(MHPC_ERR_INVALID, "n_samples out of range");
+  int nx = 0, N = 0;
+  if ((rc = range_phase_shape(h, phase, first, count, &nx, &N))) return rc;
+  const size_t S = n_samples, n = (size_t)count * S, nrec = n * N * PREC_W;
+  std::vector<real> hxs, hrec(nrec);
+  if ((rc = policy_pack(h, first, count, n_samples, xs, hxs))) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  real *dxs = nullptr, *drec = nullptr;
+  hipError_t e = hipMalloc((void**)&dxs, n * 14 * sizeof(real));
+  if (e == hipSuccess) e = hipMalloc((void**)&drec, nrec * sizeof(real));
+  if (e == hipSuccess) e = hipMemcpyAsync(dxs, hxs.data(), n * 14 * sizeof(real), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess)
+    e = launch_policy_rollout(h->sp, h->d, n_samples, first, count, dxs, nullptr, 0, phase, nullptr,
+                              nullptr, nullptr, drec, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(hrec.data(), drec, nrec * sizeof(real), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (dxs) (void)hipFree(dxs);
+  if (drec) (void)hipFree(drec);
+  if (e != hipSuccess)
+    return fail(MHPC_ERR_DEVICE, std::string("mhpc_rollout_policy_phase: ") + hipGetErrorString(e));
+  // device records [count][N][PREC_W][n_s] (the sample fastest: coalesced stores); the last
+  // knot has no u, y and an SRB knot no y: zero rows
+  const bool wb = nx == 14;
+  for (size_t b = 0; b < (size_t)count; ++b)
+    for (size_t s = 0; s < S; ++s)
+      for (int k = 0; k < N; ++k) {
+        const real* rk = &hrec[((b * N + k) * PREC_W) * S + s];
+        const size_t o = (b * S + s) * N + k;
+        for (int i = 0; i < nx; ++i)
+          if (x) x[o * nx + i] = rk[(size_t)i * S];
+        for (int i = 0; i < 4; ++i) {
+          if (u) u[o * 4 + i] = k < N - 1 ? (double)rk[(size_t)(14 + i) * S] : 0.0;
+          if (y) y[o * 4 + i] = (k < N - 1 && wb) ? (double)rk[(size_t)(18 + i) * S] : 0.0;
+        }
+      }
+  return MHPC_OK;
+}
+
+// Device-side closed loop: x0[b] <- the end state of one policy rollout of problem b over
+// n_phases phases from x0[b] + dx[b]; the kernel reads each x0 row before it writes it.
+int api_advance_x0(Handle* h, int n_phases, const double* dx) {
+  if (!h) return fail(MHPC_ERR_INVALID, "null handle");
+  int rc = policy_ready(h);
+  if (rc) return rc;
+  if (n_phases < 1 || n_phases > min_phases(h))
+    return fail(MHPC_ERR_INVALID, "n_phases out of range");
+  for (const Layout& L : h->lays)
+    if (L.n_wb > 0 && n_phases - 1 >= L.n_wb)
+      return fail(MHPC_ERR_INVALID,
+                  "phase n_phases-1 is an SRB phase: its end state cannot start a whole-body horizon");
+  const int B = h->sp.B, r = x0_row(h);
+  std::vector<double> hdx;
+  if (dx) {
+    for (size_t i = 0; i < (size_t)B * r; ++i)
+      if (!std::isfinite(dx[i])) return fail(MHPC_ERR_INVALID, "dx must be finite");
+    hdx.assign((size_t)B * 14, 0.0);
+    for (int b = 0; b < B; ++b) {
+      const int nb = h->lays[h->lid[b]].n_wb > 0 ? 14 : 6;
+      for (int i = 0; i < nb; ++i) hdx[(size_t)b * 14 + i] = dx[(size_t)b * r + i];
+    }
+  }
+  HIPCHK(hipSetDevice(h->device));
+  double* ddx = nullptr;
+  hipError_t e = hipSuccess;
+  if (dx) {
+    e = hipMalloc((void**)&ddx, hdx.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpyAsync(ddx, hdx.data(), hdx.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+  }
+  if (e == hipSuccess)
+    e = launch_policy_rollout(h->sp, h->d, 1, 0, B, h->d.x0, ddx, n_phases, 0, nullptr, nullptr,
+                              h->d.x0, nullptr, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (ddx) (void)hipFree(ddx);
+  if (e != hipSuccess) return fail(MHPC_ERR_DEVICE, std::string("mhpc_advance_x0: ") + hipGetErrorString(e));
+  h->x0_set = true;
+  h->x0_changed = true;  // as after mhpc_set_x0
+  return MHPC_OK;
+}
+
+int api_get_x0(Handle* h, double* x0) {
+  if (!h || !x0) return fail(MHPC_ERR_INVALID, "null argument");
+  if (!h->initialized) return fail(MHPC_ERR_STATE, "not initialized");
+  HIPCHK(hipSetDevice(h->device));
+  const int B = h->sp.B, r = x0_row(h);
+  std::vector<real> buf((size_t)B * 14);
+  D2H(buf.data(), h->d.x0, buf.size() * sizeof(real));
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < r; ++i) x0[(size_t)b * r + i] = buf[(size_t)b * 14 + i];
   return MHPC_OK;
 }
 

@@ -536,6 +536,68 @@ class MHPCLocomotion:
                    "mhpc_rollout_costs")
         return {"J": J, "viol": viol, "ms": ms.value}
 
+    # -- policy rollouts: the batch axis over measured / perturbed start states -------------
+    def _policy_states(self, xs, count: int) -> np.ndarray:
+        xs = np.ascontiguousarray(xs, dtype=np.float64)
+        if xs.ndim != 3 or xs.shape[0] != count or xs.shape[2] != self._x0_row():
+            raise ValueError("xs must be [problems][n_samples][x0 row length]")
+        return xs
+
+    def rollout_policy(self, xs, n_phases: int = 0) -> dict:
+        """The solved feedback policy u = u_nom + K (x - x_nom) run from the start states
+        xs [batch][n_samples][r] (r as set_initial_condition's rows) over the first n_phases
+        phases (0: every phase of each problem), nothing modified (mhpc_rollout_policy): J,
+        viol [batch][n_samples], x_end [batch][n_samples][r] (the state after the last rolled
+        phase's transition: post-impact whole-body state, usable as the next x0) and the
+        device ms."""
+        import ctypes
+        xs = self._policy_states(xs, self.batch)
+        S = xs.shape[1]
+        J = np.zeros((self.batch, S))
+        viol = np.zeros_like(J)
+        x_end = np.zeros_like(xs)
+        ms = ctypes.c_float(0)
+        capi.check(capi.lib().mhpc_rollout_policy(self._h, int(S), capi.dptr(xs), int(n_phases),
+                                                  capi.dptr(J), capi.dptr(viol), capi.dptr(x_end),
+                                                  ctypes.byref(ms)), "mhpc_rollout_policy")
+        return {"J": J, "viol": viol, "x_end": x_end, "ms": ms.value}
+
+    def rollout_policy_phase(self, p: int, first: int, count: int, xs) -> dict:
+        """Trajectories of phase p (rolled from phase 0 under the policy) for problems
+        [first, first + count) from xs [count][n_samples][r]: x [count][n_samples][N][xsize],
+        u, y [count][n_samples][N][4] (mhpc_rollout_policy_phase; one phase shape over the
+        range)."""
+        xs = self._policy_states(xs, count)
+        S = xs.shape[1]
+        d = self.descs[first] if self.descs else self.desc
+        n, N = d.xsize(p), d.N[p]
+        out = {"x": np.zeros((count, S, N, n)), "u": np.zeros((count, S, N, 4)),
+               "y": np.zeros((count, S, N, 4))}
+        capi.check(capi.lib().mhpc_rollout_policy_phase(
+            self._h, int(p), int(first), int(count), int(S), capi.dptr(xs),
+            capi.dptr(out["x"]), capi.dptr(out["u"]), capi.dptr(out["y"])),
+            "mhpc_rollout_policy_phase")
+        return out
+
+    def advance_x0(self, n_phases: int = 1, dx=None):
+        """Device-side closed loop (mhpc_advance_x0): every problem's x0 becomes the end state
+        of one policy rollout over n_phases phases from x0 + dx (dx [batch][r] or None), with
+        no host copy of states.  update_problem() / initialization() follow, as after
+        set_initial_condition."""
+        if dx is not None:
+            dx = np.ascontiguousarray(dx, dtype=np.float64)
+            if dx.shape != (self.batch, self._x0_row()):
+                raise ValueError("dx must be [batch][x0 row length]")
+        capi.check(capi.lib().mhpc_advance_x0(self._h, int(n_phases), capi.dptr(dx)),
+                   "mhpc_advance_x0")
+        self._x0 = self.get_x0()  # what update_problem() / initialization() hand back
+
+    def get_x0(self) -> np.ndarray:
+        """The device's current initial states [batch][r] (mhpc_get_x0)."""
+        x0 = np.zeros((self.batch, self._x0_row()))
+        capi.check(capi.lib().mhpc_get_x0(self._h, capi.dptr(x0)), "mhpc_get_x0")
+        return x0
+
     def set_profiling(self, on: bool = True):
         capi.check(capi.lib().mhpc_set_profiling(self._h, 1 if on else 0), "mhpc_set_profiling")
 
