@@ -236,8 +236,8 @@ int mhpc_max_phases(mhpc_handle* h, int* n);
  * (HSDDPSolver/header/CostBase.h:9-46: diagonal _Q, _R, _S, _Qf per mode) and its
  * inequality / AL parameters through Constraint (ConstraintsBase.h:11-50: AL_REB_PARAMETER per
  * mode), with the values MHPCCost.cpp:24-75 and MHPCConstraints.cpp:14-88 set.  A handle
- * starts from those values; mhpc_set_* replaces them for every later solve (they travel in
- * the kernels' parameter block).  Rows are modes 1..4. */
+ * starts from those values; mhpc_set_* replaces them for every later solve (the kernels read
+ * them from a device table, one record per group of problems).  Rows are modes 1..4. */
 typedef struct {
   double wb_Q[4][14];  /* WBCost _Q diagonal (0.01 * q) */
   double wb_R[4][4];   /* WBCost _R diagonal (0.5 * r[m]) */
@@ -275,6 +275,45 @@ int mhpc_set_cost_weights(mhpc_handle* h, const mhpc_cost_weights* w);
 int mhpc_get_cost_weights(mhpc_handle* h, mhpc_cost_weights* w);
 int mhpc_set_constraint_params(mhpc_handle* h, const mhpc_constraint_params* c);
 int mhpc_get_constraint_params(mhpc_handle* h, mhpc_constraint_params* c);
+
+/* ---- per-problem parameter sets: the batch axis over weights and constraint parameters --
+ * In the reference every MHPCLocomotion owns its WBCost / FBCost / WBConstraint objects
+ * (MHPCCost.cpp:24-75, MHPCConstraints.cpp:14-88), so a fleet of controllers is also a fleet of
+ * weight and limit sets.  Problem b solves with weights w[set_of_problem[b]] and constraint
+ * parameters c[set_of_problem[b]] (host arrays of n_sets entries, 1 <= n_sets <=
+ * MHPC_MAX_PARAM_SETS).  w == NULL / c == NULL: every set keeps, for that half, the values
+ * problem 0 has now.  set_of_problem == NULL: b % n_sets.  Every entry is validated as
+ * mhpc_set_cost_weights / mhpc_set_constraint_params validate theirs; the fp32 build rounds to
+ * float.  A handle starts with one set, the reference's values.
+ *  - Sets belong to the problem number: they survive mhpc_set_layouts and
+ *    mhpc_update_problem(s), as commands do.
+ *  - Merging: after the conversion to the solve's arithmetic type, sets that compare equal are
+ *    merged and sets no problem uses are dropped; mhpc_num_param_sets counts what is left.
+ *  - mhpc_set_cost_weights / mhpc_set_constraint_params keep their meaning (every problem gets
+ *    that value): after a mixed call one of them collapses that half of every set, so distinct
+ *    sets may merge.  mhpc_get_cost_weights / mhpc_get_constraint_params report problem 0's
+ *    values, as mhpc_get_desc does; mhpc_get_problem_params problem b's.
+ *  - Problems sharing a layout and a set are solved together (a group): a launch never mixes
+ *    groups inside a block, the group's parameters are read with scalar loads, and each
+ *    problem's arithmetic is the one it gets in a handle of its own set through the handle-wide
+ *    setters, bit for bit (tests/test_gpu_param_sets.py).  Distinct (layout, set) pairs in use
+ *    are at most MHPC_MAX_LAYOUTS: mhpc_set_param_sets, mhpc_set_layouts and
+ *    mhpc_update_problem(s) return MHPC_ERR_INVALID for a call that would exceed it.
+ *    mhpc_num_layouts keeps counting distinct layouts.
+ *  - New values take effect at the next mhpc_initialize / mhpc_update_problem(s) (AL / ReB
+ *    initial values) and at the next solve (weights, limits).  Set on an initialized handle,
+ *    mhpc_solve, mhpc_rollout_costs, the policy rollouts and mhpc_advance_x0 return
+ *    MHPC_ERR_STATE until one of those has run, as after mhpc_set_constraint_params.  A call
+ *    that changes no problem's values changes nothing and leaves nothing pending.
+ *  - A refused call changes nothing. */
+#define MHPC_MAX_PARAM_SETS 32
+int mhpc_set_param_sets(mhpc_handle* h, int n_sets, const mhpc_cost_weights* w,
+                        const mhpc_constraint_params* c, const int32_t* set_of_problem);
+/* Problem b's current values; either pointer may be NULL. */
+int mhpc_get_problem_params(mhpc_handle* h, int problem, mhpc_cost_weights* w,
+                            mhpc_constraint_params* c);
+/* Distinct sets in use (1 for a fresh handle). */
+int mhpc_num_param_sets(mhpc_handle* h, int* n);
 
 /* Running-cost gradient lx of knots 0..N-2 ([batch][N-1][n]) and terminal-cost gradient Phix
  * ([batch][n]) of `phase` as the last partials evaluation left them: the reference's

@@ -533,6 +533,34 @@ class MHPCLocomotion {
     check(mhpc_get_constraint_params(h_, &c), "mhpc_get_constraint_params");
     return c;
   }
+  // extension: the batch axis over weights and constraint parameters (one WBCost / FBCost /
+  // WBConstraint set per controller in the reference).  Problem b solves with
+  // weights[set_of_problem[b]] and constraints[set_of_problem[b]] (b % n_sets when empty); an
+  // empty weights / constraints keeps problem 0's current values for that half.  Takes effect
+  // at the next initialization() / update_problem(s) (mhpc_set_param_sets).
+  void set_param_sets(const std::vector<mhpc_cost_weights>& weights,
+                      const std::vector<mhpc_constraint_params>& constraints,
+                      const std::vector<int32_t>& set_of_problem = {}) {
+    if (weights.empty() && constraints.empty())
+      throw std::runtime_error("set_param_sets: give weights, constraints or both");
+    if (!weights.empty() && !constraints.empty() && weights.size() != constraints.size())
+      throw std::runtime_error("set_param_sets: one weights and one constraints entry per set");
+    if (!set_of_problem.empty() && (int)set_of_problem.size() != batch_)
+      throw std::runtime_error("set_param_sets: one set index per problem expected");
+    const int n = (int)(weights.empty() ? constraints.size() : weights.size());
+    check(mhpc_set_param_sets(h_, n, weights.empty() ? nullptr : weights.data(),
+                              constraints.empty() ? nullptr : constraints.data(),
+                              set_of_problem.empty() ? nullptr : set_of_problem.data()),
+          "mhpc_set_param_sets");
+  }
+  void get_problem_params(int b, mhpc_cost_weights* w, mhpc_constraint_params* c) {
+    check(mhpc_get_problem_params(h_, b, w, c), "mhpc_get_problem_params");
+  }
+  int num_param_sets() {
+    int n = 0;
+    check(mhpc_num_param_sets(h_, &n), "mhpc_num_param_sets");
+    return n;
+  }
 
   const std::vector<int32_t>& status() const { return status_; }
   const mhpc_problem_desc& desc() const { return desc_; }

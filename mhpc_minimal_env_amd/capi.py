@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("MHPC_AMD_LIB") or os.path.join(HERE, "libmhpc_amd.so"
 MHPC_MAX_PHASES = 16
 MHPC_MAX_KNOTS = 1024
 MHPC_MAX_LAYOUTS = 32
+MHPC_MAX_PARAM_SETS = 32
 MHPC_TRACE_LEN = 64
 MHPC_NUM_KERNELS = 7
 MHPC_MAX_ROLLOUT_EPS = 4096
@@ -229,6 +230,12 @@ SIGNATURES = [
     ("mhpc_get_cost_weights", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CostWeights)]),
     ("mhpc_set_constraint_params", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ConstraintParams)]),
     ("mhpc_get_constraint_params", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ConstraintParams)]),
+    ("mhpc_set_param_sets", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(CostWeights),
+                                           ctypes.POINTER(ConstraintParams), _IP]),
+    ("mhpc_get_problem_params", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int,
+                                               ctypes.POINTER(CostWeights),
+                                               ctypes.POINTER(ConstraintParams)]),
+    ("mhpc_num_param_sets", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     ("mhpc_eval_wb_dynamics", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _DP, _DP,
                                              _DP, _DP]),
     ("mhpc_eval_wb_dynamics_pair", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _DP,

@@ -43,5 +43,9 @@ int api_set_cost_weights(Handle* h, const mhpc_cost_weights* w);
 int api_get_cost_weights(Handle* h, mhpc_cost_weights* w);
 int api_set_constraint_params(Handle* h, const mhpc_constraint_params* c);
 int api_get_constraint_params(Handle* h, mhpc_constraint_params* c);
+int api_set_param_sets(Handle* h, int n_sets, const mhpc_cost_weights* w,
+                       const mhpc_constraint_params* c, const int32_t* set_of);
+int api_get_problem_params(Handle* h, int b, mhpc_cost_weights* w, mhpc_constraint_params* c);
+int api_num_param_sets(Handle* h, int* n);
 void api_destroy(Handle* h);
 }  // namespace API_NS

@@ -417,7 +417,7 @@ __device__ unsigned long long g_bws_cyc[16];
 #endif
 
 template <bool STANCE>
-__device__ int sweep_wb(const SolveParams& sp, const DevBufs& d, const Layout& L, const ProbState* st, RowLds& rl,
+__device__ int sweep_wb(const SolveParams& sp, const DevBufs& d, const Layout& L, const CostParams& cw, const ProbState* st, RowLds& rl,
                          RowCtx& rc, int p) {
   using R = Rows<7>;
   using wk = wreal;
@@ -433,7 +433,7 @@ __device__ int sweep_wb(const SolveParams& sp, const DevBufs& d, const Layout& L
   for (int r = 0; r < 7; ++r) base[r] = rho == 7 + r ? breal(1.0) : breal(0.0);
   // running-cost weight and fixed reference of state rho (CostBase.cpp:28-31)
   const int xi = xl ? rho : 0;
-  const breal w2 = 2 * dt * sp.cw.wQ[mode - 1][xi];
+  const breal w2 = 2 * dt * cw.wQ[mode - 1][xi];
   const breal rxc = xi == 1 ? rc.cm.height : xi == 2 ? breal(0.0)
                    : (xi >= 3 && xi < 7) ? cQjointBias[xi - 3] : xi == 7 ? rc.cm.vel : breal(0.0);
   // lxx + reg on the diagonal of Qxx (Ixx * regularisation): added twice to the transposed
@@ -689,7 +689,7 @@ __device__ int sweep_wb(const SolveParams& sp, const DevBufs& d, const Layout& L
 // entry is computed with the one-row sweep's operations in the same order, so the two
 // layouts agree bit for bit (tests/test_gpu_variants.py).
 template <bool STANCE>
-__device__ int sweep_wb2(const SolveParams& sp, const DevBufs& d, const Layout& L, const ProbState* st, RowLds& rl,
+__device__ int sweep_wb2(const SolveParams& sp, const DevBufs& d, const Layout& L, const CostParams& cw, const ProbState* st, RowLds& rl,
                           RowCtx& rc, int p) {
   using R = Rows<7>;
   using wk = wreal;
@@ -710,7 +710,7 @@ __device__ int sweep_wb2(const SolveParams& sp, const DevBufs& d, const Layout& 
     baseb[r] = cb == 7 + r ? breal(1.0) : breal(0.0);
   }
   const int xi = xl ? rho : 0;
-  const breal w2 = 2 * dt * sp.cw.wQ[mode - 1][xi];
+  const breal w2 = 2 * dt * cw.wQ[mode - 1][xi];
   const breal rxc = xi == 1 ? rc.cm.height : xi == 2 ? breal(0.0)
                    : (xi >= 3 && xi < 7) ? cQjointBias[xi - 3] : xi == 7 ? rc.cm.vel : breal(0.0);
   // lxx + reg on the diagonal, added by the row that owns the diagonal's column
@@ -1003,7 +1003,7 @@ constexpr int SRB_PF_HALF = MHPC_BWS_SRB_PF;
 // LANE_OPS: each lane loads only its row-5 operands (srb_w2_lane); otherwise x, z and u (the
 // whole-sweep kernels: their register allocation is the WB knots', measured slower with it)
 template <int SRB_PF, bool LANE_OPS>
-__device__ int sweep_srb(const SolveParams& sp, const DevBufs& d, const Layout& L, const ProbState* st, RowLds& rl,
+__device__ int sweep_srb(const SolveParams& sp, const DevBufs& d, const Layout& L, const CostParams& cw, const ProbState* st, RowLds& rl,
                           RowCtx& rc, int p) {
   using R = Rows<3>;
   const int t = rc.t, b = rc.b;
@@ -1028,16 +1028,16 @@ __device__ int sweep_srb(const SolveParams& sp, const DevBufs& d, const Layout& 
   // per-lane cost weight 2 dt Q / 2 dt R and fixed reference of row cj
   breal w2, rxc;
   if (cj < 6) {
-    w2 = 2 * dt * sp.cw.fQ[m][cj];
+    w2 = 2 * dt * cw.fQ[m][cj];
     rxc = cj == 1 ? rc.cm.height : cj == 3 ? rc.cm.vel : breal(0.0);
   } else {
     const int c = cj - 6;
-    w2 = 2 * dt * sp.cw.fR[m][c];
+    w2 = 2 * dt * cw.fR[m][c];
     rxc = (c == 1 || c == 3) ? breal(8.252) * breal(9.81) : breal(0.0);
   }
   breal luu[4];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) luu[c] = 2 * dt * sp.cw.fR[m][c];
+  for (int c = 0; c < 4; ++c) luu[c] = 2 * dt * cw.fR[m][c];
   // lxx + reg, see sweep_wb (two-row layout: both rows run this phase, row A adds)
   const breal dg2 = xl && rc.rp == 0 ? 2 * (w2 + rc.reg) : breal(0.0);
   // rows 3, 4 of W do not depend on the knot
@@ -1234,7 +1234,7 @@ __device__ int sweep_srb(const SolveParams& sp, const DevBufs& d, const Layout& 
 // H = Phixx + Hnext; AL partials only while st->al_partials (quirk B1).  G of knot N-1 is
 // an output of the phase.
 template <int NX>
-__device__ void terminal_value(const SolveParams& sp, const DevBufs& d, const Layout& L, const ProbState* st,
+__device__ void terminal_value(const SolveParams& sp, const DevBufs& d, const Layout& L, const CostParams& cw, const ProbState* st,
                                RowLds& rl, const RowCtx& rc, int p) {
   constexpr bool wb = NX == 14;
   const int mode = L.mode[p], N = L.N[p], ko = L.ko[p];
@@ -1262,7 +1262,7 @@ __device__ void terminal_value(const SolveParams& sp, const DevBufs& d, const La
   for (int e = rc.lt; e < NX * NX + NX; e += rc.nl) {
     if (e < NX * NX) {
       const int i = e / NX, j = e - i * NX;
-      breal v = i == j ? (wb ? sp.cw.wQf[mode - 1][i] : sp.cw.fQf[mode - 1][i]) : breal(0.0);
+      breal v = i == j ? (wb ? cw.wQf[mode - 1][i] : cw.fQf[mode - 1][i]) : breal(0.0);
       if (al) {
         const int ai = i == 2 ? 0 : (i == ih ? 1 : (i == ih + 1 ? 2 : -1));
         const int aj = j == 2 ? 0 : (j == ih ? 1 : (j == ih + 1 ? 2 : -1));
@@ -1275,7 +1275,7 @@ __device__ void terminal_value(const SolveParams& sp, const DevBufs& d, const La
       breal rxi;
       if (wb) rxi = i == 0 ? pos : (i == 7 ? cvel : cXtermWB[mode - 1][i]);
       else rxi = i == 0 ? pos : (i == 1 ? chgt : (i == 3 ? cvel : breal(0.0)));
-      breal v = (wb ? sp.cw.wQf[mode - 1][i] : sp.cw.fQf[mode - 1][i]) * (xe[i] - rxi);
+      breal v = (wb ? cw.wQf[mode - 1][i] : cw.fQf[mode - 1][i]) * (xe[i] - rxi);
       if (al) v += 50 * (s * s / 2 * rl.hx[i] * h + lam * rl.hx[i]);
       const breal g = v + rl.Gs[i];
       rl.Gs[i] = g;
@@ -1356,7 +1356,7 @@ __device__ void impact_step(const SolveParams& sp, const DevBufs& d, const Layou
 // kernel (its register allocation is the SRB knot's, so a partials wave fits beside it).
 // RPP: rows per problem (2: the whole-body phases run sweep_wb2, SRB phases on both rows).
 template <bool WB_CODE, int RPP>
-__device__ void sweep_phases(const SolveParams& sp, const DevBufs& d, const Layout& L, ProbState* st, RowLds& rl,
+__device__ void sweep_phases(const SolveParams& sp, const DevBufs& d, const Layout& L, const CostParams& cw, ProbState* st, RowLds& rl,
                              RowCtx& rc, int p_hi, int p_lo) {
   for (int p = p_hi; p >= p_lo; --p) {
     const bool wb = WB_CODE && p < L.n_wb;
@@ -1372,29 +1372,29 @@ __device__ void sweep_phases(const SolveParams& sp, const DevBufs& d, const Layo
     BWS_T(tt0);
     if (wb) {
       if constexpr (WB_CODE) {
-        terminal_value<14>(sp, d, L, st, rl, rc, p);
+        terminal_value<14>(sp, d, L, cw, st, rl, rc, p);
         BWS_ADD(4, clock64() - tt0);
         BWS_T(tw0);
         const int mode = L.mode[p];
         int nit;
         if (RPP == 2) {
-          if (mode == 1 || mode == 3) nit = sweep_wb2<true>(sp, d, L, st, rl, rc, p);
-          else nit = sweep_wb2<false>(sp, d, L, st, rl, rc, p);
+          if (mode == 1 || mode == 3) nit = sweep_wb2<true>(sp, d, L, cw, st, rl, rc, p);
+          else nit = sweep_wb2<false>(sp, d, L, cw, st, rl, rc, p);
         } else {
-          if (mode == 1 || mode == 3) nit = sweep_wb<true>(sp, d, L, st, rl, rc, p);
-          else nit = sweep_wb<false>(sp, d, L, st, rl, rc, p);
+          if (mode == 1 || mode == 3) nit = sweep_wb<true>(sp, d, L, cw, st, rl, rc, p);
+          else nit = sweep_wb<false>(sp, d, L, cw, st, rl, rc, p);
         }
         BWS_ADD(0, clock64() - tw0);
         BWS_ADD(1, nit);
         (void)nit;
       }
     } else {
-      terminal_value<6>(sp, d, L, st, rl, rc, p);
+      terminal_value<6>(sp, d, L, cw, st, rl, rc, p);
       BWS_ADD(4, clock64() - tt0);
       BWS_T(ts0);
       // (the whole-sweep kernels keep distance 1 and x, z, u operands: their registers go to
       // the WB knots)
-      const int nit = sweep_srb<WB_CODE ? 1 : SRB_PF_HALF, !WB_CODE>(sp, d, L, st, rl, rc, p);
+      const int nit = sweep_srb<WB_CODE ? 1 : SRB_PF_HALF, !WB_CODE>(sp, d, L, cw, st, rl, rc, p);
       BWS_ADD(2, clock64() - ts0);
       BWS_ADD(3, nit);
       (void)nit;
@@ -1445,10 +1445,11 @@ __global__ __launch_bounds__(64, PART == 1 ? MHPC_BWS_SRB_WAVES : 1) void k_bws(
   rc.rp = RPP == 2 ? row & 1 : 0;
   rc.lt = rc.t + 16 * rc.rp;
   rc.nl = 16 * RPP;
-  // the block's layout group and problems (a block never mixes layouts)
+  // the block's layout group and problems (a block never mixes groups: (layout, parameter set) pairs)
   const GrpBlk gb = block_group(sp, blockIdx.x, RPW);
   if (gb.g < 0) return;
   const Layout& L = layout_of(d, gb.g);
+  const CostParams& cw = params_of(d, gb.g);
   const bool inb = q < RPW && gb.p0 + q < gb.p1;
   rc.b = prob_at(sp, d, inb ? gb.p0 + q : gb.p0);  // a spare row shadows the block's first problem
   ProbState* st = &d.st[rc.b];
@@ -1471,7 +1472,7 @@ __global__ __launch_bounds__(64, PART == 1 ? MHPC_BWS_SRB_WAVES : 1) void k_bws(
     if (PART == 1) {
       zero_value(rl, rc);
       // (a layout without SRB phases passes with nothing swept; PART 2 sweeps it whole)
-      if (L.P > L.n_wb) sweep_phases<false, 1>(sp, d, L, st, rl, rc, L.P - 1, L.n_wb);
+      if (L.P > L.n_wb) sweep_phases<false, 1>(sp, d, L, cw, st, rl, rc, L.P - 1, L.n_wb);
       BwsCarry& c = d.carry[rc.b];
       __syncthreads();
       if (rc.live && !rc.failed) {  // (now: a later attempt of another row reuses rl)
@@ -1518,10 +1519,10 @@ __global__ __launch_bounds__(64, PART == 1 ? MHPC_BWS_SRB_WAVES : 1) void k_bws(
       }
       rc.failed = rc.live && aborted;
       rc.dV = st->dV[L.n_wb];
-      sweep_phases<true, RPP>(sp, d, L, st, rl, rc, L.n_wb - 1, 0);
+      sweep_phases<true, RPP>(sp, d, L, cw, st, rl, rc, L.n_wb - 1, 0);
     } else {
       zero_value(rl, rc);
-      sweep_phases<true, RPP>(sp, d, L, st, rl, rc, L.P - 1, 0);
+      sweep_phases<true, RPP>(sp, d, L, cw, st, rl, rc, L.P - 1, 0);
     }
     pending = rc.live && rc.failed && !aborted;
     if (pending) {
@@ -1570,7 +1571,7 @@ __global__ __launch_bounds__(64, PART == 1 ? MHPC_BWS_SRB_WAVES : 1) void k_bws(
 #ifndef MHPC_BWS_PAIRS_MAX_B
 #define MHPC_BWS_PAIRS_MAX_B 2048
 #endif
-// Blocks of `rpw` problems over the layout groups (block_group)
+// Blocks of `rpw` problems over the groups (block_group)
 static unsigned bws_grid(const SolveParams& sp, int rpw) {
   long n = 0;
   for (int g = 0; g < sp.ngrp; ++g) n += (sp.go[g + 1] - sp.go[g] + rpw - 1) / rpw;

@@ -248,6 +248,15 @@ extern "C" int mhpc_set_constraint_params(mhpc_handle* h, const mhpc_constraint_
 extern "C" int mhpc_get_constraint_params(mhpc_handle* h, mhpc_constraint_params* c) {
   FWD(get_constraint_params, c);
 }
+extern "C" int mhpc_set_param_sets(mhpc_handle* h, int n_sets, const mhpc_cost_weights* w,
+                                   const mhpc_constraint_params* c, const int32_t* set_of_problem) {
+  FWD(set_param_sets, n_sets, w, c, set_of_problem);
+}
+extern "C" int mhpc_get_problem_params(mhpc_handle* h, int problem, mhpc_cost_weights* w,
+                                       mhpc_constraint_params* c) {
+  FWD(get_problem_params, problem, w, c);
+}
+extern "C" int mhpc_num_param_sets(mhpc_handle* h, int* n) { FWD(num_param_sets, n); }
 extern "C" void mhpc_destroy(mhpc_handle* h) {
   if (!h) return;
   try {

@@ -10,8 +10,9 @@ namespace MHPC_NS {
 
 constexpr real PI = real(3.141592653589793238);  // MHPC_CPPTypes.h:18
 
-// Cost weights and constraint parameters live in SolveParams::cw (mhpc_set_cost_weights /
-// mhpc_set_constraint_params; defaults MHPCCost.cpp:24-75, MHPCConstraints.cpp:14-88).
+// Cost weights and constraint parameters are the block's group record (params_of below;
+// mhpc_set_cost_weights / mhpc_set_constraint_params / mhpc_set_param_sets; defaults
+// MHPCCost.cpp:24-75, MHPCConstraints.cpp:14-88).
 // terminal WB state references (ReferenceGen.cpp:45-52), velocity entry filled at run time
 static __constant__ real cXtermWB[4][14] = {
     {0, -real(0.1432), -PI / 25, real(0.35) * PI, -real(0.65) * PI, real(0.35) * PI, -real(0.6) * PI, 0, 1, 0, 0, 0, 0, 0},
@@ -28,12 +29,12 @@ static __device__ __forceinline__ real* traj_ptr(const SolveParams& sp, const De
 
 static __device__ __forceinline__ int ntc_of(int mode, bool wb) { return wb && (mode == 2 || mode == 4); }
 
-// ---- layout groups ----------------------------------------------------------------------
+// ---- groups: (layout, parameter set) pairs ------------------------------------------------
 // A launch over the batch enumerates its blocks group by group: group g (problems
-// gidx[go[g] .. go[g+1]), layout g) takes ceil(n_g / per) blocks of `per` problems, so every
+// gidx[go[g] .. go[g+1]), record grp[g]) takes ceil(n_g / per) blocks of `per` problems, so every
 // wave of a block runs one layout (uniform control flow, the layout in scalar registers).
 struct GrpBlk {
-  int g;       // layout group (-1: block past the last group)
+  int g;       // group (-1: block past the last group)
   int p0, p1;  // the block's first gidx position and the end of its group's positions
 };
 static __device__ __forceinline__ GrpBlk block_group(const SolveParams& sp, int blk, int per) {
@@ -67,12 +68,18 @@ static __device__ __forceinline__ int block_group_items(const SolveParams& sp, c
 static __device__ __forceinline__ int prob_at(const SolveParams& sp, const DevBufs& d, int pos) {
   return sp.ident ? pos : d.gidx[pos];
 }
-// Layout g, read through the constant address space: the table never changes during a launch,
-// so every field a wave-uniform index selects is a scalar load (s_load), as a parameter-block
-// field would be, never a vector load plus readfirstlane.
-typedef const __attribute__((address_space(4))) Layout CLayout;
+// Record of group g, read through the constant address space: the table never changes during a
+// launch, so every field a wave-uniform index selects is a scalar load (s_load), as a
+// parameter-block field would be, never a vector load plus readfirstlane.  layout_of / params_of
+// are its two halves, addressed from the one base; read them only once the block knows it has
+// a group.
+typedef const __attribute__((address_space(4))) Group CGroup;
 static __device__ __forceinline__ const Layout& layout_of(const DevBufs& d, int g) {
-  return *(const Layout*)((CLayout*)d.lay + g);
+  return *(const Layout*)&((CGroup*)d.grp + g)->lay;
+}
+// Cost weights and constraint parameters of group g (its parameter set).
+static __device__ __forceinline__ const CostParams& params_of(const DevBufs& d, int g) {
+  return *(const CostParams*)&((CGroup*)d.grp + g)->cw;
 }
 
 // User command of problem b: loaded once per problem where a kernel picks up its state (the
@@ -153,7 +160,7 @@ static __device__ __forceinline__ void fb_run_ref(const Cmd& cm, real pos, real*
 
 // Running cost value incl. the ReB barrier of WB phases (CostBase.cpp:4-16,
 // SinglePhase.cpp:219-249 in CALC_DYNAMICS_ONLY), reference of knot kk built in registers.
-static __device__ real wb_running_cost(const SolveParams& sp, const Cmd& cm, int mode, real dt,
+static __device__ __forceinline__ real wb_running_cost(const CostParams& cw, const Cmd& cm, int mode, real dt,
                                   real pos, const real* x, const real* u, const real* y, bool reb,
                                   real delta, real eps_tq, real eps_grf) {
   MHPC_NO_FMA_COST
@@ -163,27 +170,27 @@ static __device__ real wb_running_cost(const SolveParams& sp, const Cmd& cm, int
   const real ry[4] = {0, kGRF, 0, kGRF};
   real l = 0, t = 0;
 #pragma unroll
-  for (int i = 0; i < 14; ++i) { const real e = x[i] - rx[i]; l += e * sp.cw.wQ[m][i] * e; }
+  for (int i = 0; i < 14; ++i) { const real e = x[i] - rx[i]; l += e * cw.wQ[m][i] * e; }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) { const real e = u[i]; t += e * sp.cw.wR[m][i] * e; }
+  for (int i = 0; i < 4; ++i) { const real e = u[i]; t += e * cw.wR[m][i] * e; }
   l += t;
   t = 0;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) { const real e = y[i] - ry[i]; t += e * sp.cw.wS[m][i] * e; }
+  for (int i = 0; i < 4; ++i) { const real e = y[i] - ry[i]; t += e * cw.wS[m][i] * e; }
   l += t;
   l = l * dt;
   if (reb) {
     real B, Bz, Bzz;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {  // torque limits tq_lim -/+ u
-      const real g = (i < 4 ? -u[i] : u[i - 4]) + sp.cw.tq_lim;
+      const real g = (i < 4 ? -u[i] : u[i - 4]) + cw.tq_lim;
       reduced_barrier(g, delta, &B, &Bz, &Bzz);
       l += eps_tq * B * dt;
     }
     // joint limits carry eps_ReB = 0 (MHPCConstraints.cpp:64-84): contribution 0 * B * dt
     if (mode == 1 || mode == 3) {  // GRF: Fz >= 0, mu Fz -/+ Fx >= 0
       const int o = mode == 1 ? 2 : 0;
-      const real mu = sp.cw.mu;
+      const real mu = cw.mu;
       const real gs[3] = {y[o + 1], -y[o] + mu * y[o + 1], y[o] + mu * y[o + 1]};
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
@@ -195,7 +202,7 @@ static __device__ real wb_running_cost(const SolveParams& sp, const Cmd& cm, int
   return l;
 }
 
-static __device__ real fb_running_cost(const SolveParams& sp, const Cmd& cm, int mode, real dt,
+static __device__ __forceinline__ real fb_running_cost(const CostParams& cw, const Cmd& cm, int mode, real dt,
                                   real pos, const real* x, const real* u) {
   MHPC_NO_FMA_COST
   const int m = mode - 1;
@@ -204,9 +211,9 @@ static __device__ real fb_running_cost(const SolveParams& sp, const Cmd& cm, int
   const real ru[4] = {0, kGRF, 0, kGRF};
   real l = 0, t = 0;
 #pragma unroll
-  for (int i = 0; i < 6; ++i) { const real e = x[i] - rx[i]; l += e * sp.cw.fQ[m][i] * e; }
+  for (int i = 0; i < 6; ++i) { const real e = x[i] - rx[i]; l += e * cw.fQ[m][i] * e; }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) { const real e = u[i] - ru[i]; t += e * sp.cw.fR[m][i] * e; }
+  for (int i = 0; i < 4; ++i) { const real e = u[i] - ru[i]; t += e * cw.fR[m][i] * e; }
   l += t;
   l += real(0.0);  // S = 0 for the floating base (y = 0)
   return l * dt;
@@ -216,15 +223,15 @@ static __device__ real fb_running_cost(const SolveParams& sp, const Cmd& cm, int
 // the CALC_PARTIALS_ONLY branch of SinglePhase.cpp:219-249; joint limits carry eps_ReB = 0
 // and contribute exact zeros).  out = lu[4], luu[4] (diagonal), ly[2], lyy[4] where ly/lyy
 // are the entries of the stance foot's force slots (zero in flight).
-static __device__ void wb_cost_uy_derivs(const SolveParams& sp, int mode, real dt, const real* u,
+static __device__ __forceinline__ void wb_cost_uy_derivs(const CostParams& cw, int mode, real dt, const real* u,
                                          const real* y, bool reb, real delta, real eps_tq,
                                          real eps_grf, real* out) {
   const int m = mode - 1;
-  const real tq = sp.cw.tq_lim, mu = sp.cw.mu;
+  const real tq = cw.tq_lim, mu = cw.mu;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    real lu = (2 * dt * sp.cw.wR[m][c]) * (u[c] - real(0.0));
-    real luu = 2 * dt * sp.cw.wR[m][c];
+    real lu = (2 * dt * cw.wR[m][c]) * (u[c] - real(0.0));
+    real luu = 2 * dt * cw.wR[m][c];
     if (reb) {
       real B, Bz, Bzz;
       // constraint c: g = -u_c + tq (gu = -1); constraint 4 + c: g = u_c + tq (gu = +1)
@@ -242,7 +249,7 @@ static __device__ void wb_cost_uy_derivs(const SolveParams& sp, int mode, real d
   if (mode == 1 || mode == 3) {
     const int o = mode == 1 ? 2 : 0;
     const real fx = mode == 1 ? y[2] : y[0], fz = mode == 1 ? y[3] : y[1];
-    const real s0 = sp.cw.wS[m][o], s1 = sp.cw.wS[m][o + 1];
+    const real s0 = cw.wS[m][o], s1 = cw.wS[m][o + 1];
     real ly0 = (2 * dt * s0) * (fx - real(0.0));
     real ly1 = (2 * dt * s1) * (fz - kGRF);
     real l00 = 2 * dt * s0, l01 = real(0.0), l10 = real(0.0), l11 = 2 * dt * s1;

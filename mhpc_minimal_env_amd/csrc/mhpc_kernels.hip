@@ -223,10 +223,11 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
   const int cl = (PAIR && w0) ? (lane >> 1) : lane;
   const bool back = PAIR && (lane & 1);  // the dynamics lane's leg
   const int lp = cl / nc, j = cl - lp * nc;
-  // the block's layout group and problems (a block never mixes layouts)
+  // the block's layout group and problems (a block never mixes groups: (layout, parameter set) pairs)
   const GrpBlk gb = block_group(sp, blockIdx.x, ppw);
   if (gb.g < 0) return;  // (uniform; the grid has no such block)
   const Layout& L = layout_of(d, gb.g);
+  const CostParams& cw = params_of(d, gb.g);
   const bool in = lp < ppw && gb.p0 + lp < gb.p1;
   const int b = in ? prob_at(sp, d, gb.p0 + lp) : 0;
   const Cmd cm = cmd_of(d, b);  // the problem's user command (cost side)
@@ -543,8 +544,8 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
     constexpr bool wb = decltype(WBc)::value;
     const real pos = ST ? sRef[lp][kk] : c.refpos[kk];
     if (full != 2)  // (a re-roll only writes the records)
-      V += wb ? wb_running_cost(sp, cm, mode, dt, pos, r, r + 14, r + 18, reb, c.delta, c.etq, c.egr)
-              : fb_running_cost(sp, cm, mode, dt, pos, r, r + 6);
+      V += wb ? wb_running_cost(cw, cm, mode, dt, pos, r, r + 14, r + 18, reb, c.delta, c.etq, c.egr)
+              : fb_running_cost(cw, cm, mode, dt, pos, r, r + 6);
     store_rec(r, wb ? RING_W : 14, ko + kk, true);
   };
   auto ring_rec = [&](int sl, real* r, int n) __attribute__((always_inline)) {
@@ -557,7 +558,7 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
     real rx[6];
     fb_term_ref(cm, refT, rx);
     acc Phi = 0;
-    for (int i = 0; i < 6; ++i) { const real e = xe[i] - rx[i]; Phi += e * sp.cw.fQf[mode - 1][i] * e; }
+    for (int i = 0; i < 6; ++i) { const real e = xe[i] - rx[i]; Phi += e * cw.fQf[mode - 1][i] * e; }
     return Phi * acc(0.5);
   };
   // cost side, phase end: terminal cost, touchdown constraint, AL term (SinglePhase.cpp
@@ -575,7 +576,7 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
       real rx[14];
       wb_term_ref(cm, mode, c.refT, rx);
       acc Phi = 0;
-      for (int i = 0; i < 14; ++i) { const real e = xe[i] - rx[i]; Phi += e * sp.cw.wQf[mode - 1][i] * e; }
+      for (int i = 0; i < 14; ++i) { const real e = xe[i] - rx[i]; Phi += e * cw.wQf[mode - 1][i] * e; }
       Phi = Phi * acc(0.5);
       if (ntc_of(mode, true)) {
         h = mode == 2 ? wb_touchdown_value<kFront>(xe) : wb_touchdown_value<kBack>(xe);
@@ -848,11 +849,12 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
 __global__ __launch_bounds__(64) void k_eps_rollout(SolveParams sp, DevBufs d, int n_eps,
                                                     const real* eps_v, real* Jo,
                                                     real* vo) {
-  // blocks by layout group, lanes = (problem of the group, step size)
+  // blocks by group, lanes = (problem of the group, step size)
   long t0 = 0;
   const int g = block_group_items(sp, nullptr, n_eps, blockIdx.x, 64, &t0);
   if (g < 0) return;
   const Layout& L = layout_of(d, g);
+  const CostParams& cw = params_of(d, g);
   const long tg = t0 + threadIdx.x;  // item within the group
   if (tg >= (long)(sp.go[g + 1] - sp.go[g]) * n_eps) return;
   const int pos = sp.go[g] + (int)(tg / n_eps), e = (int)(tg % n_eps);
@@ -887,7 +889,7 @@ __global__ __launch_bounds__(64) void k_eps_rollout(SolveParams sp, DevBufs d, i
         }
         real xd[14], y[4];
         wb_dynamics<real>(x, u, mode, xd, y);
-        V += wb_running_cost(sp, cm, mode, dt, refpos[k], x, u, y, reb, delta, etq, egr);
+        V += wb_running_cost(cw, cm, mode, dt, refpos[k], x, u, y, reb, delta, etq, egr);
 #pragma unroll
         for (int i = 0; i < 14; ++i) x[i] = x[i] + xd[i] * dt;
       }
@@ -896,7 +898,7 @@ __global__ __launch_bounds__(64) void k_eps_rollout(SolveParams sp, DevBufs d, i
         real rx[14];
         wb_term_ref(cm, mode, refpos[N - 1], rx);
         acc Phi = 0;
-        for (int i = 0; i < 14; ++i) { const real ee = x[i] - rx[i]; Phi += ee * sp.cw.wQf[mode - 1][i] * ee; }
+        for (int i = 0; i < 14; ++i) { const real ee = x[i] - rx[i]; Phi += ee * cw.wQf[mode - 1][i] * ee; }
         Phi = Phi * acc(0.5);
         if (ntc_of(mode, true)) {
           h = mode == 2 ? wb_touchdown_value<kFront>(x) : wb_touchdown_value<kBack>(x);
@@ -935,14 +937,14 @@ __global__ __launch_bounds__(64) void k_eps_rollout(SolveParams sp, DevBufs d, i
         }
         real xd[6];
         srb_dynamics(x, u, f, sc, xd);
-        V += fb_running_cost(sp, cm, mode, dt, refpos[k], x, u);
+        V += fb_running_cost(cw, cm, mode, dt, refpos[k], x, u);
 #pragma unroll
         for (int i = 0; i < 6; ++i) x[i] = x[i] + xd[i] * dt;
       }
       real rx[6];
       fb_term_ref(cm, refpos[N - 1], rx);
       acc Phi = 0;
-      for (int i = 0; i < 6; ++i) { const real ee = x[i] - rx[i]; Phi += ee * sp.cw.fQf[mode - 1][i] * ee; }
+      for (int i = 0; i < 6; ++i) { const real ee = x[i] - rx[i]; Phi += ee * cw.fQf[mode - 1][i] * ee; }
       V += Phi * acc(0.5);
     }
     J += V;
@@ -959,7 +961,7 @@ constexpr int PREC_W = 22;  // k_policy_rollout's knot record: x 14, u 4, y 4
 // forward_sweep_dynamics_only(0) (SinglePhase.cpp:117-144, MultiPhaseDDP.cpp:56-76).  Lane =
 // (problem, sample), the sample index fastest: the lanes of a wave read one problem's nominal
 // record, K, du and refpos at wave-uniform addresses (a wave straddles two problems when
-// n_s is no multiple of 64); blocks by layout group as k_eps_rollout.  Problems outside
+// n_s is no multiple of 64); blocks by group as k_eps_rollout.  Problems outside
 // [b0, b0 + nb) are skipped.  xs [nb][n_s][14] start states, dx (double [nb][n_s][14], or null)
 // added to them in double; n_phases phases are rolled (0: every phase of the problem); eps
 // is 0 at run time, kept in the control so that it rounds as k_eps_rollout's (the sign of a
@@ -986,6 +988,7 @@ __global__ __launch_bounds__(64) void k_policy_rollout(SolveParams sp, DevBufs d
   const int g = block_group_items(sp, nullptr, n_s, blockIdx.x, 64, &t0);
   if (g < 0) return;
   const Layout& L = layout_of(d, g);
+  const CostParams& cw = params_of(d, g);
   const long tg = t0 + threadIdx.x;  // item within the group
   if (tg >= (long)(sp.go[g + 1] - sp.go[g]) * n_s) return;
   const int pos = sp.go[g] + (int)(tg / n_s), e = (int)(tg % n_s);
@@ -1030,7 +1033,7 @@ __global__ __launch_bounds__(64) void k_policy_rollout(SolveParams sp, DevBufs d
           for (int i = 0; i < 14; ++i) r[i * rs] = x[i];
           for (int i = 0; i < 4; ++i) { r[(14 + i) * rs] = u[i]; r[(18 + i) * rs] = y[i]; }
         }
-        V += wb_running_cost(sp, cm, mode, dt, refpos[k], x, u, y, reb, delta, etq, egr);
+        V += wb_running_cost(cw, cm, mode, dt, refpos[k], x, u, y, reb, delta, etq, egr);
 #pragma unroll
         for (int i = 0; i < 14; ++i) x[i] = x[i] + xd[i] * dt;
       }
@@ -1043,7 +1046,7 @@ __global__ __launch_bounds__(64) void k_policy_rollout(SolveParams sp, DevBufs d
         real rx[14];
         wb_term_ref(cm, mode, refpos[N - 1], rx);
         acc Phi = 0;
-        for (int i = 0; i < 14; ++i) { const real ee = x[i] - rx[i]; Phi += ee * sp.cw.wQf[mode - 1][i] * ee; }
+        for (int i = 0; i < 14; ++i) { const real ee = x[i] - rx[i]; Phi += ee * cw.wQf[mode - 1][i] * ee; }
         Phi = Phi * acc(0.5);
         if (ntc_of(mode, true)) {
           h = mode == 2 ? wb_touchdown_value<kFront>(x) : wb_touchdown_value<kBack>(x);
@@ -1092,7 +1095,7 @@ __global__ __launch_bounds__(64) void k_policy_rollout(SolveParams sp, DevBufs d
           for (int i = 0; i < 6; ++i) r[i * rs] = x[i];
           for (int i = 0; i < 4; ++i) r[(14 + i) * rs] = u[i];
         }
-        V += fb_running_cost(sp, cm, mode, dt, refpos[k], x, u);
+        V += fb_running_cost(cw, cm, mode, dt, refpos[k], x, u);
 #pragma unroll
         for (int i = 0; i < 6; ++i) x[i] = x[i] + xd[i] * dt;
       }
@@ -1105,7 +1108,7 @@ __global__ __launch_bounds__(64) void k_policy_rollout(SolveParams sp, DevBufs d
       real rx[6];
       fb_term_ref(cm, refpos[N - 1], rx);
       acc Phi = 0;
-      for (int i = 0; i < 6; ++i) { const real ee = x[i] - rx[i]; Phi += ee * sp.cw.fQf[mode - 1][i] * ee; }
+      for (int i = 0; i < 6; ++i) { const real ee = x[i] - rx[i]; Phi += ee * cw.fQf[mode - 1][i] * ee; }
       V += Phi * acc(0.5);
     }
     J += V;
@@ -1121,11 +1124,12 @@ __global__ __launch_bounds__(64) void k_policy_rollout(SolveParams sp, DevBufs d
 // CostBase.cpp:19-31,49-60 + the AL term of SinglePhase.cpp:257-275 when it was a
 // forward_sweep(0)), for print_debugInfo's cost.txt.  The constraint terms added to lx are
 // exact zeros (joint limits carry eps_ReB = 0; torque / GRF limits do not depend on x).
-// Problems [b0, b0 + nb), all of layout g; lane = (problem, knot); lx [nb][N-1][n], phix [nb][n].
+// Problems [b0, b0 + nb), all of group g; lane = (problem, knot); lx [nb][N-1][n], phix [nb][n].
 // ============================================================================================
 __global__ void k_cost_grad(SolveParams sp, DevBufs d, int g, int p, int b0, int nb, real* lx,
                             real* phix) {
   const Layout& L = layout_of(d, g);
+  const CostParams& cw = params_of(d, g);
   const int N = L.N[p], ko = L.ko[p], mode = L.mode[p];
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (long)nb * N) return;
@@ -1144,10 +1148,10 @@ __global__ void k_cost_grad(SolveParams sp, DevBufs d, int g, int p, int b0, int
       if (wb) {
         rxi = i == 0 ? pos : i == 1 ? cm.height : i == 2 ? real(0.0)
               : i < 7 ? cQjointBias[i - 3] : i == 7 ? cm.vel : real(0.0);
-        w2 = 2 * dt * sp.cw.wQ[mode - 1][i];
+        w2 = 2 * dt * cw.wQ[mode - 1][i];
       } else {
         rxi = i == 0 ? pos : i == 1 ? cm.height : i == 3 ? cm.vel : real(0.0);
-        w2 = 2 * dt * sp.cw.fQ[mode - 1][i];
+        w2 = 2 * dt * cw.fQ[mode - 1][i];
       }
       o[i] = w2 * (x[i] - rxi);
     }
@@ -1165,7 +1169,7 @@ __global__ void k_cost_grad(SolveParams sp, DevBufs d, int g, int p, int b0, int
       const real s = st->par_sigma[p], lam = st->par_lambda[p];
       real v[14];
       for (int i = 0; i < 14; ++i) {
-        v[i] = sp.cw.wQf[mode - 1][i] * (x[i] - rx[i]);
+        v[i] = cw.wQf[mode - 1][i] * (x[i] - rx[i]);
         if (al) v[i] += 50 * (s * s / 2 * hx[i] * h + lam * hx[i]);
       }
       if (ntc_of(mode, true) && sp.AL_active) {  // trials of the last line search
@@ -1183,7 +1187,7 @@ __global__ void k_cost_grad(SolveParams sp, DevBufs d, int g, int p, int b0, int
     } else {
       real rx[6];
       fb_term_ref(cm, pos, rx);
-      for (int i = 0; i < 6; ++i) o[i] = sp.cw.fQf[mode - 1][i] * (x[i] - rx[i]);
+      for (int i = 0; i < 6; ++i) o[i] = cw.fQf[mode - 1][i] * (x[i] - rx[i]);
     }
   }
 }
@@ -1202,7 +1206,7 @@ __global__ void k_store_save(SolveParams sp, DevBufs d, real* store, int nbk, in
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (long)sp.B * sp.NK) return;
   const int b = (int)(t / sp.NK), kk = (int)(t - (long)b * sp.NK);
-  const Layout& L = d.lay[d.lid[b]];  // the problem's layout (per lane: not a hot kernel)
+  const Layout& L = d.grp[d.lid[b]].lay;  // the problem's layout (per lane: not a hot kernel)
   if (kk >= L.NK) return;
   int p = 0;
   while (p + 1 < L.P && kk >= L.ko[p + 1]) ++p;
@@ -1220,7 +1224,7 @@ __global__ void k_store_load(SolveParams sp, DevBufs d, const real* store, int n
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (long)sp.B * sp.NK) return;
   const int b = (int)(t / sp.NK), kk = (int)(t - (long)b * sp.NK);
-  const Layout& L = d.lay[d.lid[b]];  // the problem's layout (per lane: not a hot kernel)
+  const Layout& L = d.grp[d.lid[b]].lay;  // the problem's layout (per lane: not a hot kernel)
   if (kk >= L.NK) return;
   int p = 0;
   while (p + 1 < L.P && kk >= L.ko[p + 1]) ++p;
@@ -1332,11 +1336,12 @@ __device__ __forceinline__ void partials_knot(const real* nk, real* rec, int NK)
 #endif
 template <int G>
 __global__ __launch_bounds__(MHPC_PAR_BLOCK, MHPC_PAR_MINB) void k_partials(SolveParams sp, DevBufs d) {
-  // blocks by layout group, lanes = (problem of the group, WB knot)
+  // blocks by group, lanes = (problem of the group, WB knot)
   long t0 = 0;
   const int g = block_group_items(sp, sp.gpk, 0, blockIdx.x, MHPC_PAR_BLOCK, &t0);
   if (g < 0) return;
   const Layout& L = layout_of(d, g);
+  const CostParams& cw = params_of(d, g);
   const long t = t0 + threadIdx.x;
   const int i0 = (int)(t / L.par_knots);
   if (i0 >= sp.go[g + 1] - sp.go[g]) return;
@@ -1357,7 +1362,7 @@ __global__ __launch_bounds__(MHPC_PAR_BLOCK, MHPC_PAR_MINB) void k_partials(Solv
     // running-cost derivatives of controls and contact forces at the nominal knot
     // (CostBase.cpp:19-34 + ReB barrier, SinglePhase.cpp:219-249 CALC_PARTIALS_ONLY)
     real c[14];
-    wb_cost_uy_derivs(sp, mode, L.dt[p], nk + 14, nk + 18, st->reb_active != 0, st->delta[p],
+    wb_cost_uy_derivs(cw, mode, L.dt[p], nk + 14, nk + 18, st->reb_active != 0, st->delta[p],
                       st->eps_tq[p], st->eps_grf[p], c);
 #pragma unroll
     for (int i = 0; i < 14; ++i) d.par[par_jac(sp.NK, b, ko + k) + i] = c[i];
@@ -1397,6 +1402,7 @@ __global__ void k_al_end(SolveParams sp, DevBufs d, int last) {
   const GrpBlk gb = block_group(sp, blockIdx.x, 64);
   if (gb.g < 0 || gb.p0 + (int)threadIdx.x >= gb.p1) return;
   const Layout& L = layout_of(d, gb.g);
+  const CostParams& cw = params_of(d, gb.g);
   const int b = prob_at(sp, d, gb.p0 + threadIdx.x);
   ProbState* st = &d.st[b];
   if (st->active) {
@@ -1409,7 +1415,7 @@ __global__ void k_al_end(SolveParams sp, DevBufs d, int last) {
       st->sigma[p] *= up;
       if (st->reb_active && wb) {
         st->delta[p] *= sp.update_relax;
-        const real dmin = sp.cw.delta_min[L.mode[p] - 1];
+        const real dmin = cw.delta_min[L.mode[p] - 1];
         if (st->delta[p] < dmin) st->delta[p] = dmin;
         st->eps_tq[p] *= sp.update_ReB;
         st->eps_grf[p] *= sp.update_ReB;
@@ -1428,6 +1434,16 @@ __global__ void k_al_end(SolveParams sp, DevBufs d, int last) {
 // every phase but keeps the (rotated) nominal trajectories and gains as the warm start.
 // References (ReferenceGen.h:94-109) and the per-problem solver state of one problem;
 // warm = 1 also resets the option fields a solve rewrites (see ProbState).
+// AL_REB_PARAMETER of phase p's mode (MHPCConstraints.cpp:43-88, mhpc_set_constraint_params)
+static __device__ __forceinline__ void init_al_reb(ProbState* st, const Layout& L,
+                                                   const CostParams& cw, int p) {
+  const bool wb = p < L.n_wb && p < L.P;
+  const int m = p < L.P ? L.mode[p] - 1 : 0;
+  st->sigma[p] = (wb && ntc_of(L.mode[p], true)) ? cw.sigma0[m] : real(0.0);
+  st->delta[p] = cw.delta0[m];
+  st->eps_tq[p] = cw.eps_tq0[m];
+  st->eps_grf[p] = cw.eps_grf0[m];
+}
 __device__ void k_init_state(const SolveParams& sp, const DevBufs& d, const Layout& L, int b,
                              int warm) {
   const real* x0 = d.x0 + (size_t)b * 14;
@@ -1442,13 +1458,7 @@ __device__ void k_init_state(const SolveParams& sp, const DevBufs& d, const Layo
   st->J = 0; st->viol = 0; st->dV_exp = 0; st->reg = 0; st->cost_prev = 0;
   for (int p = 0; p < MAXP; ++p) {
     st->V[p] = 0; st->dV[p] = 0; st->h[p] = 0; st->lambda[p] = 0;
-    const bool wb = p < L.n_wb && p < L.P;
-    // AL_REB_PARAMETER of the phase's mode (MHPCConstraints.cpp:43-88, mhpc_set_constraint_params)
-    const int m = p < L.P ? L.mode[p] - 1 : 0;
-    st->sigma[p] = (wb && ntc_of(L.mode[p], true)) ? sp.cw.sigma0[m] : real(0.0);
-    st->delta[p] = sp.cw.delta0[m];
-    st->eps_tq[p] = sp.cw.eps_tq0[m];
-    st->eps_grf[p] = sp.cw.eps_grf0[m];
+    init_al_reb(st, L, sp.cw, p);  // (problem 0's set: see k_init_params)
   }
   st->status = MHPC_SOLVE_OK;
   // ReB flag as the options set it (what a sweep right after initialization() sees); the
@@ -1496,7 +1506,7 @@ __device__ void init_reset_arrays(const SolveParams& sp, const DevBufs& d, long 
     const int p = (int)(i % sp.pmax);
     const long bs = i / sp.pmax;
     const int slot = (int)(bs % sp.nslot), b = (int)(bs / sp.nslot);
-    const Layout& L = d.lay[d.lid[b]];  // the problem's layout (per lane; hidden beside k_init)
+    const Layout& L = d.grp[d.lid[b]].lay;  // the problem's layout (per lane; hidden beside k_init)
     if (p >= L.P) continue;
     const int nx = p < L.n_wb ? 14 : 6;
     real* r = traj_ptr(sp, d, b, slot, L.ko[p] + L.N[p] - 1);
@@ -1508,8 +1518,24 @@ __global__ __launch_bounds__(256) void k_reset_arrays(SolveParams sp, DevBufs d)
   init_reset_arrays(sp, d, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256);
 }
 
+// The AL / ReB initial values of every problem from its group's parameter record, after k_init
+// (which wrote problem 0's set for all): launched only when the handle holds more than one set
+// (mhpc_set_param_sets).  k_init keeps its own read of the parameter block, SolveParams::cw:
+// with that read gone or moved to the table the fp32 build's SLP vectoriser packs the
+// warm-start rollout below differently, three of its multiply-adds no longer contract, and
+// every fp32 result changes in the last bits (k_init has no MHPC_NO_FMA_F32: its rounding is
+// part of the fp32 results as they stand).
+__global__ __launch_bounds__(64) void k_init_params(SolveParams sp, DevBufs d) {
+  const GrpBlk gb = block_group(sp, blockIdx.x, 64);
+  if (gb.g < 0 || gb.p0 + (int)threadIdx.x >= gb.p1) return;
+  const Layout& L = layout_of(d, gb.g);
+  const CostParams& cw = params_of(d, gb.g);
+  ProbState* st = &d.st[prob_at(sp, d, gb.p0 + threadIdx.x)];
+  for (int p = 0; p < MAXP; ++p) init_al_reb(st, L, cw, p);
+}
+
 __global__ __launch_bounds__(64) void k_init(SolveParams sp, DevBufs d, int warm) {
-  // blocks by layout group, 32 problems a block
+  // blocks by group, 32 problems a block
   const GrpBlk gb = block_group(sp, blockIdx.x, 32);
   const int i0 = threadIdx.x >> 1;
   const bool back = (threadIdx.x & 1) != 0;
@@ -1649,6 +1675,7 @@ __global__ __launch_bounds__(64) void k_cost(SolveParams sp, DevBufs d, int al_i
   const GrpBlk gb = block_group(sp, blockIdx.x, 1);  // one problem a block
   if (gb.g < 0) return;
   const Layout& L = layout_of(d, gb.g);
+  const CostParams& cw = params_of(d, gb.g);
   const int b = prob_at(sp, d, gb.p0);
   ProbState* st = &d.st[b];
   if (!st->active) return;
@@ -1671,10 +1698,10 @@ __global__ __launch_bounds__(64) void k_cost(SolveParams sp, DevBufs d, int al_i
     if (k < L.N[p] - 1) {
       const real* r = traj_ptr(sp, d, b, nom, kk);
       if (p < L.n_wb)
-        c = wb_running_cost(sp, cm, mode, L.dt[p], refpos[kk], r, r + 14, r + 18, reb, st->delta[p],
+        c = wb_running_cost(cw, cm, mode, L.dt[p], refpos[kk], r, r + 14, r + 18, reb, st->delta[p],
                             st->eps_tq[p], st->eps_grf[p]);
       else
-        c = fb_running_cost(sp, cm, mode, L.dt[p], refpos[kk], r, r + 6);
+        c = fb_running_cost(cw, cm, mode, L.dt[p], refpos[kk], r, r + 6);
     }
     sc[kk] = c;
   }
@@ -1690,7 +1717,7 @@ __global__ __launch_bounds__(64) void k_cost(SolveParams sp, DevBufs d, int al_i
       real rx[14];
       wb_term_ref(cm, mode, refpos[ko + N - 1], rx);
       acc Phi = 0;
-      for (int i = 0; i < 14; ++i) { const real e = x[i] - rx[i]; Phi += e * sp.cw.wQf[mode - 1][i] * e; }
+      for (int i = 0; i < 14; ++i) { const real e = x[i] - rx[i]; Phi += e * cw.wQf[mode - 1][i] * e; }
       Phi = Phi * acc(0.5);
       if (ntc_of(mode, true)) {
         h = mode == 2 ? wb_touchdown_value<kFront>(x) : wb_touchdown_value<kBack>(x);
@@ -1705,7 +1732,7 @@ __global__ __launch_bounds__(64) void k_cost(SolveParams sp, DevBufs d, int al_i
       real rx[6];
       fb_term_ref(cm, refpos[ko + N - 1], rx);
       acc Phi = 0;
-      for (int i = 0; i < 6; ++i) { const real e = x[i] - rx[i]; Phi += e * sp.cw.fQf[mode - 1][i] * e; }
+      for (int i = 0; i < 6; ++i) { const real e = x[i] - rx[i]; Phi += e * cw.fQf[mode - 1][i] * e; }
       V += Phi * acc(0.5);
     }
     sV[p] = V;
@@ -1757,7 +1784,7 @@ __global__ void k_export_ref(SolveParams sp, DevBufs d, int b0, int nb) {
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (long)nb * sp.NK) return;
   const int b = b0 + (int)(t / sp.NK), kk = (int)(t % sp.NK);
-  const Layout& L = d.lay[d.lid[b]];  // the problem's layout (per lane: not a hot kernel)
+  const Layout& L = d.grp[d.lid[b]].lay;  // the problem's layout (per lane: not a hot kernel)
   if (kk >= L.NK) return;
   int p = 0;
   while (p + 1 < L.P && kk >= L.ko[p + 1]) ++p;
@@ -1854,7 +1881,7 @@ __global__ void k_eval_srb(int n, const real* x, const real* u, const real* p,
   srb_jacobians(x + (size_t)i * 6, u + (size_t)i * 4, p + (size_t)i * 4, s + (size_t)i * 2, Ac + (size_t)i * 36, Bc + (size_t)i * 24);
 }
 
-// Sum the per-problem counters of each layout group (int64 atomics into NCNT slots per group).
+// Sum the per-problem counters of each group (int64 atomics into NCNT slots per group).
 // One block of 256 threads, strided over the batch, tree-reduced in LDS: NCNT atomics per
 // block instead of per problem (the per-problem atomics on NCNT words serialised, ~35 us).
 __global__ __launch_bounds__(256) void k_reduce_counters(SolveParams sp, DevBufs d,
@@ -1864,7 +1891,7 @@ __global__ __launch_bounds__(256) void k_reduce_counters(SolveParams sp, DevBufs
   unsigned long long acc[NCNT];
 #pragma unroll
   for (int i = 0; i < NCNT; ++i) acc[i] = 0;
-  const int g = blockIdx.y;  // layout group: its problems' totals go to out[g]
+  const int g = blockIdx.y;  // group: its problems' totals go to out[g]
   for (int pos = sp.go[g] + blockIdx.x * 256 + t; pos < sp.go[g + 1]; pos += gridDim.x * 256) {
     const int b = prob_at(sp, d, pos);
 #pragma unroll
@@ -1883,7 +1910,7 @@ __global__ __launch_bounds__(256) void k_reduce_counters(SolveParams sp, DevBufs
 }
 
 // ---- launchers (called by mhpc_runtime.cpp) ---------------------------------------------
-// Blocks of a launch over the layout groups with `per` problems a block (block_group)
+// Blocks of a launch over the groups with `per` problems a block (block_group)
 static unsigned grid_of(const SolveParams& sp, int per) {
   long n = 0;
   for (int g = 0; g < sp.ngrp; ++g) n += (sp.go[g + 1] - sp.go[g] + per - 1) / per;
@@ -1913,6 +1940,10 @@ hipError_t launch_reset_arrays(const SolveParams& sp, const DevBufs& d, hipStrea
   const long e = (long)sp.B * sp.NK * 74 + (long)sp.B * sp.nslot * sp.pmax;
   const long nb = std::min((e + 256 * 64 - 1) / (256 * 64), 2L * sp.ncu);
   hipLaunchKernelGGL(k_reset_arrays, dim3((unsigned)nb), dim3(256), 0, s, sp, d);
+  return hipGetLastError();
+}
+hipError_t launch_init_params(const SolveParams& sp, const DevBufs& d, hipStream_t s) {
+  hipLaunchKernelGGL(k_init_params, dim3(grid_of(sp, 64)), dim3(64), 0, s, sp, d);
   return hipGetLastError();
 }
 hipError_t launch_init(const SolveParams& sp, const DevBufs& d, hipStream_t s) {

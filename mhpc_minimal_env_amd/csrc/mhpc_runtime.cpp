@@ -18,6 +18,7 @@
 
 namespace MHPC_NS {
 hipError_t launch_init(const SolveParams&, const DevBufs&, hipStream_t);
+hipError_t launch_init_params(const SolveParams&, const DevBufs&, hipStream_t);
 hipError_t launch_reset_arrays(const SolveParams&, const DevBufs&, hipStream_t);
 hipError_t launch_rollout(const SolveParams&, const DevBufs&, int, int, int, int, hipStream_t);
 hipError_t launch_partials(const SolveParams&, const DevBufs&, hipStream_t, hipStream_t, hipEvent_t,
@@ -122,8 +123,17 @@ struct Handle {
   // between is refused like one after new constraint parameters
   std::vector<double> cmd;
   bool cmd_changed = false;
+  // parameter sets (mhpc_set_param_sets): the distinct sets in use, as the kernels read them
+  // (real), and each problem's set by problem number; psets[pset_of[0]] is what the handle-wide
+  // getters report.  sets_changed: a mixed call changed some problem's values on an initialised
+  // handle (set together with params_changed; mhpc_rollout_costs looks at this one alone)
+  std::vector<CostParams> psets;
+  std::vector<int> pset_of;
+  std::vector<int> gset;  // parameter set of each group
+  bool sets_changed = false;
+  int nlay = 1;  // distinct layouts in use (the groups are (layout, parameter set) pairs)
   float solve_ms = 0;
-  unsigned long long* dcnt = nullptr;  // reduced counters per layout group [MAXL][NCNT]
+  unsigned long long* dcnt = nullptr;  // reduced counters per group [MAXL][NCNT]
   unsigned long long cnt[NCNT] = {};   // their sum over the groups
   unsigned long long gcnt[MAXL][NCNT] = {};
   // profiling: one event pair per launch of a solve, accumulated per kernel id
@@ -132,16 +142,17 @@ struct Handle {
   std::vector<int> evkind;
   double kms[NKERN] = {}, kbytes[NKERN] = {}, kflops[NKERN] = {};
   int64_t klaunch[NKERN] = {};
-  // per-problem layouts and the layout groups built from them (rebuild_groups): the layout
-  // table (host / device), each problem's layout, the problems grouped by layout
+  // per-problem layouts and the groups built from them and the parameter sets (rebuild_groups):
+  // each group's layout (host; the device group table is dgrp), each problem's group, the
+  // problems grouped
   std::vector<ProbLayout> pl;
   std::vector<Layout> lays;
-  std::vector<mhpc_problem_desc> ldesc;  // descriptor of each layout
+  std::vector<mhpc_problem_desc> ldesc;  // descriptor of each group's layout
   std::vector<int> lid, gidx;
-  Layout* dlay = nullptr;
+  Group* dgrp = nullptr;  // device group table [MAXL]
   int *dgidx = nullptr, *dlid = nullptr;
   Cmd* dcmd = nullptr;
-  // algorithmic byte model per problem of each layout
+  // algorithmic byte model per problem of each group's layout
   std::vector<ByteModel> bym;
   // receding horizon (MHPCLocomotion::update_problem): each problem's current mode, the
   // buffer store [B][spmax][nbk] (allocated at the first update), knot capacity of the
@@ -282,11 +293,11 @@ static int validate(const mhpc_problem_desc* d) {
 static void free_bufs(Handle* h) {
   DevBufs& d = h->d;
   void* ptrs[] = {d.traj, d.refpos, d.K, d.du, d.G, d.par, d.px, d.x0, d.st, d.out, d.carry,
-                  h->dlay, h->dgidx, h->dlid, h->dcmd};
+                  h->dgrp, h->dgidx, h->dlid, h->dcmd};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   memset(&d, 0, sizeof d);
-  h->dlay = nullptr;
+  h->dgrp = nullptr;
   h->dgidx = h->dlid = nullptr;
   h->dcmd = nullptr;
 }
@@ -351,10 +362,25 @@ static int ensure_knot_arrays(Handle* h, int NK) {
   return MHPC_OK;
 }
 
-// Layout groups from the per-problem layouts: the distinct (descriptor, buffer rotation)
-// pairs, longest layout first (its blocks head every launch: the long blocks start first in a
-// mixed batch), the problems of each group in batch order.  Uploads the layout table and the
-// grouped order, sets the launch fields of sp, grows the packed arrays if a layout needs it.
+// The group table (group g: layout lays[g], parameter set gset[g]) to the device.
+static int upload_params(Handle* h) {
+  std::vector<Group> t(h->gset.size());
+  for (size_t g = 0; g < t.size(); ++g) t[g] = Group{h->lays[g], h->psets[h->gset[g]]};
+  h->sp.cw = h->psets[h->pset_of[0]];  // k_init's copy (problem 0's set)
+  HIPCHK(hipMemcpyAsync(h->dgrp, t.data(), t.size() * sizeof(Group), hipMemcpyHostToDevice,
+                        h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return MHPC_OK;
+}
+
+// Groups from the per-problem layouts and parameter sets: the distinct (layout, set) pairs in
+// use, where a layout is a (descriptor, buffer rotation) pair; longest layout first (its blocks
+// head every launch: the long blocks start first in a mixed batch), then by set, the problems
+// of each group in batch order.  Group g has its own Layout record (a layout that several sets
+// share is stored once per group, so lays[lid[b]] stays problem b's layout) and its parameter
+// record.  Uploads the group table and the grouped order, sets the launch fields of sp, grows the
+// packed arrays if a layout needs it.  A call that would need more than MAXL groups fails
+// before it changes anything.
 static int rebuild_groups(Handle* h) {
   SolveParams& sp = h->sp;
   const int B = sp.B;
@@ -382,18 +408,30 @@ static int rebuild_groups(Handle* h) {
   std::vector<int> order(L), rank(L);
   std::iota(order.begin(), order.end(), 0);
   std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return lay[a].NK > lay[c].NK; });
-  for (int g = 0; g < L; ++g) rank[order[g]] = g;
-  h->lays.resize(L);
-  h->ldesc.resize(L);
-  h->bym.resize(L);
+  for (int l = 0; l < L; ++l) rank[order[l]] = l;
+  // the (layout rank, set) pairs in use, in that order
+  std::map<std::pair<int, int>, int> grp;
+  for (int b = 0; b < B; ++b) grp[{rank[first_lid[b]], h->pset_of[b]}] = 0;
+  const int G = (int)grp.size();
+  if (G > MAXL)
+    return fail(MHPC_ERR_INVALID,
+                "more than MHPC_MAX_LAYOUTS distinct (layout, parameter set) pairs");
+  h->lays.resize(G);
+  h->ldesc.resize(G);
+  h->bym.resize(G);
+  h->gset.resize(G);
+  h->nlay = L;
   int NK = 0, pmax = 0;
   sp.split_ok = 0;
   sp.stage_fits = 1;
-  for (int g = 0; g < L; ++g) {
-    const Layout& Lg = lay[order[g]];
+  int ng = 0;
+  for (auto& kv : grp) {
+    const int g = kv.second = ng++;
+    const Layout& Lg = lay[order[kv.first.first]];
     h->lays[g] = Lg;
-    h->ldesc[g] = uniq[order[g]].desc;
+    h->ldesc[g] = uniq[order[kv.first.first]].desc;
     h->bym[g] = byte_model(Lg);
+    h->gset[g] = kv.first.second;
     NK = std::max(NK, Lg.NK);
     pmax = std::max(pmax, Lg.P);
     if (Lg.n_wb > 0 && Lg.P > Lg.n_wb) sp.split_ok = 1;
@@ -403,14 +441,14 @@ static int rebuild_groups(Handle* h) {
     sp.gpi[g] = Lg.par_imp;
   }
   h->lid.resize(B);
-  std::vector<int> cnt(L + 1, 0);
+  std::vector<int> cnt(G + 1, 0);
   for (int b = 0; b < B; ++b) {
-    h->lid[b] = rank[first_lid[b]];
+    h->lid[b] = grp[{rank[first_lid[b]], h->pset_of[b]}];
     ++cnt[h->lid[b] + 1];
   }
-  sp.ngrp = L;
-  for (int g = 0; g < L; ++g) cnt[g + 1] += cnt[g];
-  for (int g = 0; g <= L; ++g) sp.go[g] = cnt[g];
+  sp.ngrp = G;
+  for (int g = 0; g < G; ++g) cnt[g + 1] += cnt[g];
+  for (int g = 0; g <= G; ++g) sp.go[g] = cnt[g];
   h->gidx.resize(B);
   sp.ident = 1;
   for (int b = 0; b < B; ++b) {
@@ -422,15 +460,14 @@ static int rebuild_groups(Handle* h) {
   int rc = ensure_knot_arrays(h, NK);
   if (rc) return rc;
   sp.NK = NK;
-  h->d.lay = h->dlay;
+  h->d.grp = h->dgrp;
   h->d.gidx = h->dgidx;
   h->d.lid = h->dlid;
   h->d.cmd = h->dcmd;
-  HIPCHK(hipMemcpyAsync(h->dlay, h->lays.data(), L * sizeof(Layout), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->dgidx, h->gidx.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->dlid, h->lid.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  return MHPC_OK;
+  return upload_params(h);
 }
 
 // Host (double) parameter structs <-> the kernels' parameter block (real).
@@ -491,21 +528,13 @@ static void get_constraints(const CostParams& cw, mhpc_constraint_params& c) {
   }
 }
 
-int api_set_cost_weights(Handle* h, const mhpc_cost_weights* w) {
-  if (!h || !w) return fail(MHPC_ERR_INVALID, "null argument");
+static int check_weights(const mhpc_cost_weights* w) {
   const double* v = &w->wb_Q[0][0];
   for (size_t i = 0; i < sizeof(mhpc_cost_weights) / sizeof(double); ++i)
     if (!std::isfinite(v[i]) || v[i] < 0) return fail(MHPC_ERR_INVALID, "cost weights must be finite and >= 0");
-  put_weights(h->sp.cw, *w);
   return MHPC_OK;
 }
-int api_get_cost_weights(Handle* h, mhpc_cost_weights* w) {
-  if (!h || !w) return fail(MHPC_ERR_INVALID, "null argument");
-  get_weights(h->sp.cw, *w);
-  return MHPC_OK;
-}
-int api_set_constraint_params(Handle* h, const mhpc_constraint_params* c) {
-  if (!h || !c) return fail(MHPC_ERR_INVALID, "null argument");
+static int check_constraints(const mhpc_constraint_params* c) {
   const double* v = &c->torque_limit;
   for (size_t i = 0; i < sizeof(mhpc_constraint_params) / sizeof(double); ++i)
     if (!std::isfinite(v[i])) return fail(MHPC_ERR_INVALID, "constraint parameters must be finite");
@@ -520,13 +549,135 @@ int api_set_constraint_params(Handle* h, const mhpc_constraint_params* c) {
     if (c->sigma[m] < 0 || c->eps_torque[m] < 0 || c->eps_grf[m] < 0)
       return fail(MHPC_ERR_INVALID, "sigma and the ReB weights must be >= 0");
   }
-  put_constraints(h->sp.cw, *c);
+  return MHPC_OK;
+}
+
+// Parameter sets compare by value, entry by entry (CostParams holds nothing but reals).
+static bool same_params(const CostParams& a, const CostParams& b) {
+  const real *x = (const real*)&a, *y = (const real*)&b;
+  for (size_t i = 0; i < sizeof(CostParams) / sizeof(real); ++i)
+    if (!(x[i] == y[i])) return false;
+  return true;
+}
+// Merge the sets that compare equal and drop the ones no problem uses (first occurrence
+// kept, order preserved); `of` is renumbered accordingly.
+static void merge_sets(std::vector<CostParams>& sets, std::vector<int>& of) {
+  std::vector<int> to(sets.size(), -1);
+  std::vector<char> used(sets.size(), 0);
+  for (int s : of) used[s] = 1;
+  std::vector<CostParams> out;
+  for (size_t i = 0; i < sets.size(); ++i) {
+    if (!used[i]) continue;
+    for (size_t j = 0; j < out.size() && to[i] < 0; ++j)
+      if (same_params(out[j], sets[i])) to[i] = (int)j;
+    if (to[i] < 0) {
+      to[i] = (int)out.size();
+      out.push_back(sets[i]);
+    }
+  }
+  for (int& s : of) s = to[s];
+  sets.swap(out);
+}
+// A handle-wide setter rewrote one half of every set in `ns`: sets that became equal merge (the
+// groups are then rebuilt), otherwise only the device table changes.  On a device error the
+// handle keeps its old sets, host and device (as far as the device still answers).
+static int apply_sets(Handle* h, std::vector<CostParams>& ns) {
+  HIPCHK(hipSetDevice(h->device));
+  std::vector<int> nof = h->pset_of;
+  const size_t n = ns.size();
+  merge_sets(ns, nof);
+  h->psets.swap(ns);
+  h->pset_of.swap(nof);
+  const int rc = h->psets.size() != n ? rebuild_groups(h) : upload_params(h);
+  if (rc) {
+    h->psets.swap(ns);
+    h->pset_of.swap(nof);
+    (void)rebuild_groups(h);
+  }
+  return rc;
+}
+
+int api_set_cost_weights(Handle* h, const mhpc_cost_weights* w) {
+  if (!h || !w) return fail(MHPC_ERR_INVALID, "null argument");
+  int rc = check_weights(w);
+  if (rc) return rc;
+  std::vector<CostParams> ns = h->psets;
+  for (CostParams& cw : ns) put_weights(cw, *w);
+  return apply_sets(h, ns);
+}
+int api_get_cost_weights(Handle* h, mhpc_cost_weights* w) {
+  if (!h || !w) return fail(MHPC_ERR_INVALID, "null argument");
+  get_weights(h->psets[h->pset_of[0]], *w);
+  return MHPC_OK;
+}
+int api_set_constraint_params(Handle* h, const mhpc_constraint_params* c) {
+  if (!h || !c) return fail(MHPC_ERR_INVALID, "null argument");
+  int rc = check_constraints(c);
+  if (rc) return rc;
+  std::vector<CostParams> ns = h->psets;
+  for (CostParams& cw : ns) put_constraints(cw, *c);
+  if ((rc = apply_sets(h, ns))) return rc;
   if (h->initialized) h->params_changed = true;
   return MHPC_OK;
 }
 int api_get_constraint_params(Handle* h, mhpc_constraint_params* c) {
   if (!h || !c) return fail(MHPC_ERR_INVALID, "null argument");
-  get_constraints(h->sp.cw, *c);
+  get_constraints(h->psets[h->pset_of[0]], *c);
+  return MHPC_OK;
+}
+
+// Per-problem parameter sets (the batch axis over WBCost / FBCost / WBConstraint objects):
+// problem b gets w[set_of[b]] / c[set_of[b]] on top of problem 0's current values for the half
+// not given.  Equal sets merge, unused ones are dropped, and the groups are rebuilt over the
+// (layout, set) pairs; a call that changes no problem's values changes nothing.
+int api_set_param_sets(Handle* h, int n_sets, const mhpc_cost_weights* w,
+                       const mhpc_constraint_params* c, const int32_t* set_of) {
+  if (!h) return fail(MHPC_ERR_INVALID, "null handle");
+  if (n_sets < 1 || n_sets > MHPC_MAX_PARAM_SETS)
+    return fail(MHPC_ERR_INVALID, "n_sets must be 1..MHPC_MAX_PARAM_SETS");
+  int rc;
+  for (int i = 0; i < n_sets; ++i) {
+    if (w && (rc = check_weights(&w[i]))) return rc;
+    if (c && (rc = check_constraints(&c[i]))) return rc;
+  }
+  const int B = h->sp.B;
+  for (int b = 0; set_of && b < B; ++b)
+    if (set_of[b] < 0 || set_of[b] >= n_sets) return fail(MHPC_ERR_INVALID, "set index out of range");
+  std::vector<CostParams> ns(n_sets, h->psets[h->pset_of[0]]);
+  for (int i = 0; i < n_sets; ++i) {
+    if (w) put_weights(ns[i], w[i]);
+    if (c) put_constraints(ns[i], c[i]);
+  }
+  std::vector<int> nof(B);
+  for (int b = 0; b < B; ++b) nof[b] = set_of ? set_of[b] : b % n_sets;
+  merge_sets(ns, nof);
+  bool changed = false;
+  for (int b = 0; b < B && !changed; ++b)
+    changed = !same_params(ns[nof[b]], h->psets[h->pset_of[b]]);
+  if (!changed) return MHPC_OK;  // nothing changes: nothing pending
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->psets.swap(ns);
+  h->pset_of.swap(nof);
+  if ((rc = rebuild_groups(h))) {  // too many (layout, set) pairs: keep the old sets
+    h->psets.swap(ns);
+    h->pset_of.swap(nof);
+    (void)rebuild_groups(h);
+    return rc;
+  }
+  if (h->initialized) h->params_changed = h->sets_changed = true;
+  return MHPC_OK;
+}
+int api_get_problem_params(Handle* h, int b, mhpc_cost_weights* w, mhpc_constraint_params* c) {
+  if (!h) return fail(MHPC_ERR_INVALID, "null handle");
+  if (b < 0 || b >= h->sp.B) return fail(MHPC_ERR_INVALID, "problem out of range");
+  if (w) get_weights(h->psets[h->pset_of[b]], *w);
+  if (c) get_constraints(h->psets[h->pset_of[b]], *c);
+  return MHPC_OK;
+}
+int api_num_param_sets(Handle* h, int* n) {
+  if (!h || !n) return fail(MHPC_ERR_INVALID, "null argument");
+  *n = (int)h->psets.size();
   return MHPC_OK;
 }
 
@@ -581,8 +732,11 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
     mhpc_constraint_params c;
     mhpc_default_cost_weights(&w);
     mhpc_default_constraint_params(&c);
-    put_weights(sp.cw, w);
-    put_constraints(sp.cw, c);
+    CostParams cw;
+    put_weights(cw, w);
+    put_constraints(cw, c);
+    h->psets.assign(1, cw);
+    h->pset_of.assign(batch, 0);
   }
   h->pl.assign(batch, ProbLayout{h->desc, 0, 0});
   h->cmode.assign(batch, desc->mode_seq[0]);
@@ -599,7 +753,7 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
   alloc((void**)&d.st, B * sizeof(ProbState));
   alloc((void**)&d.carry, B * sizeof(BwsCarry));
   alloc((void**)&h->dcnt, MAXL * NCNT * sizeof(unsigned long long));
-  alloc((void**)&h->dlay, MAXL * sizeof(Layout));
+  alloc((void**)&h->dgrp, MAXL * sizeof(Group));
   alloc((void**)&h->dgidx, B * sizeof(int));
   alloc((void**)&h->dlid, B * sizeof(int));
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
@@ -622,7 +776,7 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
   }
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   int rc2 = e == hipSuccess ? MHPC_OK : fail(MHPC_ERR_DEVICE, std::string("allocation failed: ") + hipGetErrorString(e));
-  if (!rc2) rc2 = rebuild_groups(h);  // one layout group; allocates the packed arrays
+  if (!rc2) rc2 = rebuild_groups(h);  // one group; allocates the packed arrays
   if (!rc2) {  // the command array (after the packed arrays: their placement stays as it was)
     const std::vector<Cmd> hcmd(B, Cmd{(real)desc->vel_cmd, (real)desc->height_cmd});
     e = hipMalloc((void**)&h->dcmd, B * sizeof(Cmd));
@@ -734,6 +888,11 @@ static int initialize_async(Handle* h) {
   HIPCHK(launch_reset_arrays(sp, d, h->stream2));
   HIPCHK(hipEventRecord(h->evjoin, h->stream2));
   LAUNCH(h, K_INIT, launch_init(sp, d, h->stream));
+  // (k_init wrote the AL / ReB initial values of problem 0's set for every problem)
+  if (h->psets.size() > 1) {  // its time and bytes (four MAXP-long arrays a problem) count as k_init's
+    LAUNCH(h, K_INIT, launch_init_params(sp, d, h->stream));
+    h->kbytes[K_INIT] += (double)sp.B * 4 * MAXP * kB;
+  }
   HIPCHK(hipStreamWaitEvent(h->stream, h->evjoin, 0));
   for (int g = 0; g < sp.ngrp; ++g) h->kbytes[K_INIT] += h->bym[g].init * (sp.go[g + 1] - sp.go[g]);
   // the buffer store is zeroed lazily (first update_problem), so a plain initialize + solve
@@ -755,6 +914,7 @@ int api_initialize(Handle* h) {
   h->initialized = true;
   h->x0_changed = false;
   h->params_changed = false;
+  h->sets_changed = false;
   h->cmd_changed = false;
   h->solved = false;
   return MHPC_OK;
@@ -981,7 +1141,7 @@ static int solve_async(Handle* h) {
     }
     HIPCHK(ej);
   }
-  // totals of the per-problem counters per layout group (tiny reduction, NCNT words each)
+  // totals of the per-problem counters per group (tiny reduction, NCNT words each)
   HIPCHK(hipMemsetAsync(h->dcnt, 0, (size_t)h->sp.ngrp * NCNT * sizeof(unsigned long long), h->stream));
   HIPCHK(launch_reduce_counters(h->sp, h->d, h->dcnt, h->stream));
   return MHPC_OK;
@@ -1016,7 +1176,7 @@ int api_solve(Handle* h, int32_t* status) {
   rc = collect_profile(h);
   if (rc) return rc;
   const unsigned long long* c = h->cnt;
-  for (int g = 0; g < h->sp.ngrp; ++g) {  // per layout group: its problems' counters x its bytes
+  for (int g = 0; g < h->sp.ngrp; ++g) {  // per group: its problems' counters x its layout's bytes
     const unsigned long long* cg = h->gcnt[g];
     const ByteModel& m = h->bym[g];
     const SolveParams& sp = h->sp;
@@ -1170,6 +1330,9 @@ int api_rollout_costs(Handle* h, int n_eps, const double* eps, double* J,
   if (n_eps < 1 || n_eps > MHPC_MAX_ROLLOUT_EPS) return fail(MHPC_ERR_INVALID, "n_eps out of range");
   if (h->cmd_changed)
     return fail(MHPC_ERR_STATE, "commands changed: call mhpc_initialize or mhpc_update_problem first");
+  if (h->sets_changed)
+    return fail(MHPC_ERR_STATE,
+                "parameter sets changed: call mhpc_initialize or mhpc_update_problem first");
   HIPCHK(hipSetDevice(h->device));
   const size_t B = h->sp.B, n = B * (size_t)n_eps;
   real *deps = nullptr, *dJ = nullptr, *dv = nullptr;
@@ -1398,7 +1561,7 @@ int api_get_cost_gradients(Handle* h, int phase, int first, int count, double* l
   std::vector<real> hlx(nlx), hph(nph);
   hipError_t e = hipMalloc((void**)&dlx, nlx * sizeof(real) + 8);
   if (e == hipSuccess) e = hipMalloc((void**)&dph, nph * sizeof(real));
-  // one launch per run of problems with the same layout
+  // one launch per run of problems of the same group
   for (int r0 = first; r0 < first + count && e == hipSuccess;) {
     const int g = h->lid[r0];
     int r1 = r0 + 1;
@@ -1449,7 +1612,7 @@ static int ensure_store(Handle* h) {
 // references are regenerated from the current x0 (mhpc_set_x0) and its AL / ReB parameters
 // re-initialised.  The rotated nominal trajectories and gains are the warm start of the next
 // mhpc_solve, whose first forward_sweep(0) is then a real rollout.  Problems whose layouts
-// change move to the layout group of their new layout.
+// change move to the group of their new layout and their parameter set.
 int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const int32_t* gait_of,
                         const int32_t* steps) {
   if (!h || !gaits) return fail(MHPC_ERR_INVALID, "null argument");
@@ -1515,12 +1678,14 @@ int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const in
   }
   h->cmode = ncm;
   HIPCHK(launch_reset(h->sp, h->d, h->stream));  // refs from x0, AL/ReB init, nom_slot = 0
+  if (h->psets.size() > 1) HIPCHK(launch_init_params(h->sp, h->d, h->stream));
   HIPCHK(launch_store(h->sp, h->d, h->store, h->nbk, h->spmax, 0, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->need_full = true;
   h->solved = false;
   h->x0_changed = false;
   h->params_changed = false;
+  h->sets_changed = false;
   h->cmd_changed = false;
   return MHPC_OK;
 }
@@ -1634,7 +1799,7 @@ int api_get_reference(Handle* h, int phase, int first, int count, double* xref) 
 
 int api_num_layouts(Handle* h, int* n) {
   if (!h || !n) return fail(MHPC_ERR_INVALID, "null argument");
-  *n = h->sp.ngrp;
+  *n = h->nlay;  // (sp.ngrp counts (layout, parameter set) pairs)
   return MHPC_OK;
 }
 

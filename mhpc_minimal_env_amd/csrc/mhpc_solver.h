@@ -19,9 +19,11 @@
 //          differentiated in registers by the backward kernel.
 //   px     [B][P][196]         impact Jacobian Px (column-major) at the end of WB phases.
 //   state  [B]                 ProbState (control flow + AL/ReB parameters).
-//   lay    [L]                 Layout table (read through the constant address space: scalar
-//          loads), gidx [B] the problems grouped by layout (group g = positions
-//          [go[g], go[g+1]) of gidx), lid [B] each problem's layout.
+//   grp    [G]                 group table: a group is a (layout, parameter set) pair in use
+//          (mhpc_set_layouts x mhpc_set_param_sets) and its record holds the Layout and the
+//          CostParams (read through the constant address space: scalar loads); a layout shared
+//          by several sets is stored once per group.  gidx [B] the problems grouped (group g =
+//          positions [go[g], go[g+1]) of gidx), lid [B] each problem's group.
 //   cmd    [B][2]              user command (vel, height) of each problem (mhpc_set_commands),
 //          indexed by problem number: it follows a problem through every regrouping.
 #pragma once
@@ -63,6 +65,10 @@ enum {
   NCNT
 };
 
+// Cost weights (diagonals per mode, CostBase.h:9-46 / MHPCCost.cpp:24-75) and constraint
+// parameters (ConstraintsBase.h:11-50 / MHPCConstraints.cpp:14-88) of one parameter set:
+// mhpc_set_cost_weights / mhpc_set_constraint_params / mhpc_set_param_sets; every kernel reads
+// its block's group record DevBufs::grp[g].cw (params_of, mhpc_device.h).
 struct CostParams {
   real wQ[4][14], wR[4][4], wS[4][4], wQf[4][14];  // whole-body phases
   real fQ[4][6], fR[4][4], fQf[4][6];              // SRB phases
@@ -83,12 +89,21 @@ struct Layout {
   real dt[MAXP];
 };
 
+// Record of one group: its layout and its parameter set, side by side, so that a kernel
+// addresses both from one base (one scalar register pair live through its loops, as before
+// parameter sets -- the sweep and the line search have no scalar registers to spare).
+struct Group {
+  Layout lay;
+  CostParams cw;
+};
+
 struct SolveParams {
   int B;                   // problems of the handle (the arrays' leading dimension)
   int NK;                  // per-problem knot stride of the packed arrays (max over layouts)
-  // layout groups: the problems of group g are gidx[go[g] .. go[g + 1]) and share layout g;
-  // a launch enumerates its blocks group by group, so no block mixes layouts (kernels map a
-  // block to its group with block_group, mhpc_device.h).  ident: gidx is the identity.
+  // groups: the problems of group g are gidx[go[g] .. go[g + 1]) and share the group record
+  // grp[g] (layout and parameter set); a launch enumerates its blocks group by group, so no
+  // block mixes layouts or parameter sets (kernels map a block to its group with block_group,
+  // mhpc_device.h).  ident: gidx is the identity.
   int ngrp, ident;
   int go[MAXL + 1];
   int gpk[MAXL], gpi[MAXL];  // partials knot / impact work items per problem of each group
@@ -108,9 +123,10 @@ struct SolveParams {
   // host side: some layout has both kinds of phase (the sweep can run split, bws_split) /
   // every phase of every layout fits the line search's LDS stage of position references
   int split_ok, stage_fits;
-  // cost weights (diagonals per mode, CostBase.h:9-46 / MHPCCost.cpp:24-75) and constraint
-  // parameters (ConstraintsBase.h:11-50 / MHPCConstraints.cpp:14-88): mhpc_set_cost_weights /
-  // mhpc_set_constraint_params; read by every kernel from its parameter block
+  // problem 0's parameter set (what mhpc_get_cost_weights / mhpc_get_constraint_params report).
+  // Only k_init reads it, for the AL / ReB initial values it writes for every problem; the
+  // groups' own values then come from the table (k_init_params, mhpc_kernels.hip, which says
+  // why k_init keeps this read).  Every other kernel reads the group table alone.
   CostParams cw;
 };
 
@@ -192,9 +208,9 @@ struct DevBufs {
   ProbState* st;
   real* out;    // export staging [B][NK][KS]
   BwsCarry* carry;  // [B]
-  const Layout* lay;  // [ngrp] layout table
-  const int* gidx;    // [B] problems grouped by layout
-  const int* lid;     // [B] layout of each problem
+  const Group* grp;   // [ngrp] group table: layout and parameter record of each group
+  const int* gidx;    // [B] problems grouped (by layout, then parameter set)
+  const int* lid;     // [B] group of each problem (its record grp[lid[b]])
   const Cmd* cmd;     // [B] user command of each problem
 };
 

@@ -477,6 +477,52 @@ class MHPCLocomotion:
                    "mhpc_get_constraint_params")
         return c
 
+    # -- per-problem parameter sets: the batch axis over weights / constraint parameters ----
+    def set_param_sets(self, weights, constraints, set_of_problem=None):
+        """mhpc_set_param_sets: problem b solves with weights[set_of_problem[b]] and
+        constraints[set_of_problem[b]] (b % n_sets when None) -- the WBCost / FBCost /
+        WBConstraint objects of one controller per problem (MHPCCost.cpp:24-75,
+        MHPCConstraints.cpp:14-88).  weights: a sequence of capi.CostWeights or None (every set
+        keeps problem 0's current weights); constraints likewise with capi.ConstraintParams; at
+        least one is given, both of the same length 1..MHPC_MAX_PARAM_SETS.  Takes effect at the
+        next initialization() / update_problem(s); an initialised handle refuses to solve until
+        then."""
+        if weights is None and constraints is None:
+            raise ValueError("give weights, constraints or both")
+        if weights is not None and constraints is not None and len(weights) != len(constraints):
+            raise ValueError("weights and constraints must have one entry per set each")
+        n = len(weights if weights is not None else constraints)
+        if not 1 <= n <= capi.MHPC_MAX_PARAM_SETS:
+            raise ValueError("the number of sets must be 1..MHPC_MAX_PARAM_SETS")
+        for seq, cls in ((weights, capi.CostWeights), (constraints, capi.ConstraintParams)):
+            if seq is not None and not all(isinstance(v, cls) for v in seq):
+                raise TypeError(f"every set must be a capi.{cls.__name__}")
+        sop = None
+        if set_of_problem is not None:
+            sop = np.ascontiguousarray(set_of_problem, dtype=np.int32)
+            if sop.shape != (self.batch,):
+                raise ValueError("set_of_problem must have one entry per problem")
+            if sop.size and (sop.min() < 0 or sop.max() >= n):
+                raise ValueError("set_of_problem entry out of range")
+        w = None if weights is None else (capi.CostWeights * n)(*weights)
+        c = None if constraints is None else (capi.ConstraintParams * n)(*constraints)
+        capi.check(capi.lib().mhpc_set_param_sets(self._h, n, w, c, capi.iptr(sop)),
+                   "mhpc_set_param_sets")
+
+    def get_problem_params(self, b: int):
+        """(capi.CostWeights, capi.ConstraintParams) of problem b (mhpc_get_problem_params)."""
+        import ctypes
+        w, c = capi.CostWeights(), capi.ConstraintParams()
+        capi.check(capi.lib().mhpc_get_problem_params(self._h, int(b), ctypes.byref(w),
+                                                      ctypes.byref(c)), "mhpc_get_problem_params")
+        return w, c
+
+    def num_param_sets(self) -> int:
+        import ctypes
+        n = ctypes.c_int(0)
+        capi.check(capi.lib().mhpc_num_param_sets(self._h, ctypes.byref(n)), "mhpc_num_param_sets")
+        return n.value
+
     def get_exec(self) -> dict:
         """Execution horizon of solve_mhpc (MHPCLocomotion.cpp:176-194): the nominal and
         cost-to-go of phase 0, followed by phase 1 when there are two WB phases."""

@@ -21,8 +21,9 @@ def shard_offsets(global_batch: int, world: int, rank: int) -> Tuple[int, int]:
 
 
 def shard_rows(a, world: int, rank: int) -> np.ndarray:
-    """Rank's rows of a per-problem array of the global batch (x0, or the vel / height arrays
-    of set_commands): the block shard_offsets gives."""
+    """Rank's rows of a per-problem array of the global batch (x0, the vel / height arrays of
+    set_commands, or the set_of_problem index array of set_param_sets -- the sets themselves go
+    to every rank whole): the block shard_offsets gives."""
     a = np.asarray(a)
     offset, count = shard_offsets(a.shape[0], world, rank)
     return a[offset:offset + count]
