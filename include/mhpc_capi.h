@@ -465,6 +465,17 @@ int mhpc_eval_wb_impact(int device, int n, int foot, const double* x, double* xp
                         double* Px);
 int mhpc_eval_srb(int device, int n, const double* x, const double* u, const double* foothold,
                   const double* contact, double* xdot, double* Ac, double* Bc);
+/* The fp32 instantiation's build of the same kernels: the signatures and output shapes of the
+ * hooks above, double host arrays, inputs rounded to float and float results widened. */
+int mhpc_eval_wb_partials_f32(int device, int n, int mode, const double* x, const double* u,
+                              double* Ac, double* Bc, double* C, double* D);
+int mhpc_eval_wb_impact_f32(int device, int n, int foot, const double* x, double* xplus,
+                            double* Px);
+int mhpc_eval_wb_touchdown_f32(int device, int n, int foot, const double* x, double* h,
+                               double* hx, double* hxx, double* J, double* Jd);
+int mhpc_eval_srb_f32(int device, int n, const double* x, const double* u,
+                      const double* foothold, const double* contact, double* xdot, double* Ac,
+                      double* Bc);
 
 #ifdef __cplusplus
 }

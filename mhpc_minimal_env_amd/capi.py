@@ -248,6 +248,14 @@ SIGNATURES = [
                                              _DP, _DP, _DP, _DP]),
     ("mhpc_eval_wb_impact", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _DP, _DP, _DP]),
     ("mhpc_eval_srb", ctypes.c_int, [ctypes.c_int, ctypes.c_int, _DP, _DP, _DP, _DP, _DP, _DP, _DP]),
+    ("mhpc_eval_wb_partials_f32", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _DP,
+                                                 _DP, _DP, _DP, _DP, _DP]),
+    ("mhpc_eval_wb_impact_f32", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _DP, _DP,
+                                               _DP]),
+    ("mhpc_eval_wb_touchdown_f32", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _DP,
+                                                  _DP, _DP, _DP, _DP, _DP]),
+    ("mhpc_eval_srb_f32", ctypes.c_int, [ctypes.c_int, ctypes.c_int, _DP, _DP, _DP, _DP, _DP, _DP,
+                                         _DP]),
 ]
 
 _lib = None

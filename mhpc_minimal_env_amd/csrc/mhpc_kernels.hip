@@ -1321,8 +1321,9 @@ __device__ __forceinline__ void partials_knot(const real* nk, real* rec, int NK)
   }
 }
 
-// MHPC_PAR_MINB: blocks per CU the register allocator must allow for the partials (1: no cap;
-// round 6: 2 in the fp32 build, 258 -> 256 VGPRs, two waves per SIMD, measured identical)
+// MHPC_PAR_MINB: blocks per CU the register allocator must allow for the partials.  1 (no cap)
+// in both builds.  2 was tried in the fp32 build in round 6 (258 -> 256 VGPRs, two waves per
+// SIMD), measured identical and not adopted; the macro stays for such experiments.
 #ifndef MHPC_PAR_MINB
 #define MHPC_PAR_MINB 1
 #endif

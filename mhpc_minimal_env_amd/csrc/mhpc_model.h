@@ -727,7 +727,19 @@ MHPC_HD real wb_touchdown_value(const real* x) {
   constexpr int ih = 3 + 2 * F, ik = 4 + 2 * F;
   const real a1 = x[2] + x[ih];
   const real a2 = a1 + x[ik];
+#ifdef MHPC_FP32
+  // sinf / cosf are sincosf's values: the same bits as wb_touchdown_compact
   return x[1] - sg * kHipX * sin(x[2]) - kThighLen * cos(a1) - kShankLen * cos(a2) - kGroundHeight;
+#else
+  // sin_cos like wb_touchdown_compact, not the library's sin / cos: in fp64 the two differ in
+  // the last bit at the angles a solve visits (|a| > 3), and the line search's h must be the
+  // backward sweep's bit for bit (tests/test_gpu_kernels.py, trajectory fixture)
+  real sth, cth, s1, c1, s2, c2;
+  sin_cos(x[2], &sth, &cth);
+  sin_cos(a1, &s1, &c1);
+  sin_cos(a2, &s2, &c2);
+  return x[1] - sg * kHipX * sth - kThighLen * c1 - kShankLen * c2 - kGroundHeight;
+#endif
 }
 
 template <int F>

@@ -52,14 +52,12 @@ hipError_t launch_reduce_counters(const SolveParams&, const DevBufs&, unsigned l
                                   hipStream_t);
 hipError_t launch_eval_wb_dyn(int, int, const real*, const real*, real*, real*, hipStream_t);
 hipError_t launch_eval_wb_dyn_pair(int, int, const real*, const real*, real*, real*, hipStream_t);
-#ifndef MHPC_FP32
 hipError_t launch_eval_wb_par(int, int, const real*, const real*, real*, real*, real*,
                               real*, hipStream_t);
 hipError_t launch_eval_wb_aux(int, int, const real*, real*, real*, real*, real*, real*, hipStream_t);
 hipError_t launch_eval_wb_impact(int, int, const real*, real*, real*, hipStream_t);
 hipError_t launch_eval_srb(int, const real*, const real*, const real*, const real*,
                            real*, real*, real*, hipStream_t);
-#endif
 }  // namespace MHPC_NS
 
 extern thread_local std::string mhpc_g_err;  // mhpc_capi.cpp (mhpc_last_error)
@@ -1936,7 +1934,7 @@ void api_destroy(Handle* h) {
   delete h;
 }
 
-#ifndef MHPC_FP32  // kernel-level parity hooks: fp64 only
+#ifndef MHPC_FP32  // kernel-level parity hooks of the fp64 build (the fp32 build's: *_f32 below)
 // ---- batched model evaluation hooks ---------------------------------------------------------
 namespace {
 struct DevScratch {
@@ -2059,7 +2057,7 @@ extern "C" int mhpc_eval_srb(int device, int n, const double* x, const double* u
   HIPCHK(hipMemcpy(Bc, dB, n * 24 * sizeof(double), hipMemcpyDeviceToHost));
   return MHPC_OK;
 }
-#else   // MHPC_FP32: the fp32 build of the two rollout dynamics models
+#else   // MHPC_FP32: the same hooks of the fp32 build (mhpc_eval_*_f32)
 // Whole-body dynamics of the fp32 instantiation, single-lane (pair = 0: xdot [n][14],
 // y [n][4]) or lane pair (pair = 1: xdot [n][2][14], y [n][2][4]); host arrays double.
 extern "C" int mhpc_eval_wb_dynamics_f32(int device, int n, int mode, int pair, const double* x,
@@ -2087,6 +2085,107 @@ extern "C" int mhpc_eval_wb_dynamics_f32(int device, int n, int mode, int pair, 
   if (e != hipSuccess) return fail(MHPC_ERR_DEVICE, std::string("mhpc_eval_wb_dynamics_f32: ") + hipGetErrorString(e));
   std::copy(hxd.begin(), hxd.end(), xdot);
   std::copy(hy.begin(), hy.end(), y);
+  return MHPC_OK;
+}
+
+// The other model hooks of the fp32 instantiation: the fp64 hooks' signatures and output
+// shapes, host arrays double, converted to float on the way in and back on the way out.
+namespace {
+struct DevScratchF {
+  struct Out { float* dev; double* host; size_t n; };
+  std::vector<void*> ptrs;
+  std::vector<Out> outs;
+  hipError_t e = hipSuccess;
+  ~DevScratchF() {
+    for (void* p : ptrs) (void)hipFree(p);
+  }
+  float* alloc(size_t n) {
+    void* p = nullptr;
+    if (e == hipSuccess) e = hipMalloc(&p, n * sizeof(float) + 8);
+    if (e == hipSuccess) ptrs.push_back(p);
+    return (float*)p;
+  }
+  float* in(const double* host, size_t n) {
+    float* p = alloc(n);
+    std::vector<float> h(host, host + n);
+    if (e == hipSuccess) e = hipMemcpy(p, h.data(), n * sizeof(float), hipMemcpyHostToDevice);
+    return p;
+  }
+  float* out(double* host, size_t n) {
+    float* p = alloc(n);
+    outs.push_back({p, host, n});
+    return p;
+  }
+  hipError_t fetch() {  // every out() array back to its host array
+    for (const Out& o : outs) {
+      std::vector<float> h(o.n);
+      if (e == hipSuccess) e = hipMemcpy(h.data(), o.dev, o.n * sizeof(float), hipMemcpyDeviceToHost);
+      if (e == hipSuccess) std::copy(h.begin(), h.end(), o.host);
+    }
+    return e;
+  }
+};
+}  // namespace
+
+extern "C" int mhpc_eval_wb_partials_f32(int device, int n, int mode, const double* x,
+                                         const double* u, double* Ac, double* Bc, double* C,
+                                         double* D) {
+  if (n < 1 || !x || !u || !Ac || !Bc || !C || !D || mode < 1 || mode > 4)
+    return fail(MHPC_ERR_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(device));
+  DevScratchF s;
+  float *dx = s.in(x, (size_t)n * 14), *du = s.in(u, (size_t)n * 4);
+  float *dA = s.out(Ac, (size_t)n * 196), *dB = s.out(Bc, (size_t)n * 56);
+  float *dC = s.out(C, (size_t)n * 56), *dD = s.out(D, (size_t)n * 16);
+  HIPCHK(s.e);
+  HIPCHK(launch_eval_wb_par(n, mode, dx, du, dA, dB, dC, dD, nullptr));
+  HIPCHK(s.fetch());
+  return MHPC_OK;
+}
+
+extern "C" int mhpc_eval_wb_impact_f32(int device, int n, int foot, const double* x,
+                                       double* xplus, double* Px) {
+  if (n < 1 || !x || !xplus || !Px || (foot != 0 && foot != 1))
+    return fail(MHPC_ERR_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(device));
+  DevScratchF s;
+  float *dx = s.in(x, (size_t)n * 14), *dxp = s.out(xplus, (size_t)n * 14);
+  float* dP = s.out(Px, (size_t)n * 196);
+  HIPCHK(s.e);
+  HIPCHK(launch_eval_wb_impact(n, foot, dx, dxp, dP, nullptr));
+  HIPCHK(s.fetch());
+  return MHPC_OK;
+}
+
+extern "C" int mhpc_eval_wb_touchdown_f32(int device, int n, int foot, const double* x, double* h,
+                                          double* hx, double* hxx, double* J, double* Jd) {
+  if (n < 1 || !x || !h || !hx || !hxx || !J || !Jd || (foot != 0 && foot != 1))
+    return fail(MHPC_ERR_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(device));
+  DevScratchF s;
+  float *dx = s.in(x, (size_t)n * 14), *dh = s.out(h, (size_t)n * 2);
+  float *dhx = s.out(hx, (size_t)n * 14), *dhxx = s.out(hxx, (size_t)n * 196);
+  float *dJ = s.out(J, (size_t)n * 14), *dJd = s.out(Jd, (size_t)n * 14);
+  HIPCHK(s.e);
+  HIPCHK(launch_eval_wb_aux(n, foot, dx, dh, dhx, dhxx, dJ, dJd, nullptr));
+  HIPCHK(s.fetch());
+  return MHPC_OK;
+}
+
+extern "C" int mhpc_eval_srb_f32(int device, int n, const double* x, const double* u,
+                                 const double* foothold, const double* contact, double* xdot,
+                                 double* Ac, double* Bc) {
+  if (n < 1 || !x || !u || !foothold || !contact || !xdot || !Ac || !Bc)
+    return fail(MHPC_ERR_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(device));
+  DevScratchF s;
+  float *dx = s.in(x, (size_t)n * 6), *du = s.in(u, (size_t)n * 4);
+  float *dp = s.in(foothold, (size_t)n * 4), *dc = s.in(contact, (size_t)n * 2);
+  float *dxd = s.out(xdot, (size_t)n * 6), *dA = s.out(Ac, (size_t)n * 36);
+  float* dB = s.out(Bc, (size_t)n * 24);
+  HIPCHK(s.e);
+  HIPCHK(launch_eval_srb(n, dx, du, dp, dc, dxd, dA, dB, nullptr));
+  HIPCHK(s.fetch());
   return MHPC_OK;
 }
 #endif  // MHPC_FP32

@@ -13,10 +13,86 @@ SOLVE_TOL = 1e-6
 # cases over the 64 KAT states (host build, tests/test_model_host.py): values 1.5e-10
 # (Dyn_FL, Imp_B), Jacobians 1.4e-9 (Dyn_FL_par); CasADi's QR leaves ~1e-10 noise itself.
 KAT_TOL = {"value": 1e-9, "jac": 5e-9}
+# The same bounds hold on the trajectory fixture (host build: values 7.0e-11, Jacobians
+# 8.5e-10, the model's two derivative paths within 3.5e-11 of each other).
+
+# The fp32 instantiation (real = float) vs the same fp64 reference vectors, per fixture and
+# quantity, as norm_err.  Each entry is 4 x the worst case of the HOST float build
+# (tests/native/model_hostcheck.cpp with -DMHPC_FP32, no contraction; the Jacobians by the
+# partials kernel's method, wb_partial_column) rounded up to one digit; the measured host value
+# stands beside it.  tests/test_model_host.py holds the host build to a quarter of each entry,
+# so the table cannot drift from what it was derived from; tests/test_gpu_kernels.py holds
+# the device to the entry.  The factor 4 covers what differs between the two builds: the
+# device's sincosf, division and reciprocal rounding, and the contraction the fp32 partials
+# and impact are compiled with (the whole-body dynamics is built without in both).
+# Beside each entry: the host float build's error, then the device's error and the device's
+# difference to the host float build as first measured on MI355X ("lam" has no device hook).
+KAT_TOL_F32 = {
+    "kat_model.npz": {
+        "xdot": 5e-5,      # host 1.04e-5; device 1.6e-5, device vs host 1.8e-5
+        "y": 4e-5,         # host 8.36e-6; device 8.4e-6, device vs host 6.2e-6
+        "Ac": 2e-4,        # host 3.48e-5; device 3.5e-5, device vs host 2.2e-5
+        "Bc": 8e-6,        # host 1.79e-6; device 1.8e-6, device vs host 1.8e-6
+        "C": 2e-4,         # host 2.51e-5; device 3.6e-5, device vs host 3.6e-5
+        "D": 5e-5,         # host 1.19e-5; device 1.2e-5, device vs host 5.0e-6
+        "xplus": 2e-4,     # host 2.62e-5; device 1.8e-5, device vs host 4.1e-5
+        "lam": 4e-5,       # host 8.65e-6
+        "Px": 1e-4,        # host 2.26e-5; device 2.4e-5, device vs host 2.7e-5
+        "h": 7e-7,         # host 1.50e-7; device 1.5e-7, device vs host 1.2e-7
+        "hx": 3e-7,        # host 5.32e-8; device 5.2e-8, device vs host 6.0e-8
+        "hxx": 2e-7,       # host 4.97e-8; device 5.0e-8, device vs host 3.0e-8
+        "J": 3e-7,         # host 5.16e-8; device 5.2e-8, device vs host 6.0e-8
+        "Jd": 7e-7,        # host 1.66e-7; device 1.9e-7, device vs host 1.2e-7
+        "srb.xdot": 3e-6,  # host 7.00e-7; device 7.0e-7, device vs host 0
+        "srb.Ac": 2e-6,    # host 4.51e-7; device 4.5e-7, device vs host 0
+        "srb.Bc": 6e-7,    # host 1.40e-7; device 1.4e-7, device vs host 0
+    },
+    "kat_model_traj.npz": {
+        "xdot": 1e-4,      # host 2.40e-5; device 2.4e-5, device vs host 3.8e-5
+        "y": 2e-6,         # host 4.66e-7; device 3.6e-7, device vs host 4.2e-7
+        "Ac": 2e-4,        # host 4.66e-5; device 5.1e-5, device vs host 6.4e-5
+        "Bc": 1e-6,        # host 2.43e-7; device 3.0e-7, device vs host 3.5e-7
+        "C": 2e-5,         # host 3.12e-6; device 2.9e-6, device vs host 5.8e-6
+        "D": 9e-6,         # host 2.22e-6; device 1.0e-6, device vs host 3.2e-6
+        "xplus": 2e-5,     # host 4.10e-6; device 2.5e-6, device vs host 1.6e-6
+        "lam": 3e-6,       # host 7.25e-7
+        "Px": 2e-5,        # host 3.21e-6; device 9.5e-6, device vs host 7.9e-6
+        "h": 4e-7,         # host 9.05e-8; device 9.0e-8, device vs host 6.0e-8
+        "hx": 2e-7,        # host 3.92e-8; device 3.9e-8, device vs host 3.0e-8
+        "hxx": 3e-7,       # host 7.12e-8; device 7.1e-8, device vs host 3.0e-8
+        "J": 3e-7,         # host 6.39e-8; device 6.4e-8, device vs host 3.0e-8
+        "Jd": 2e-6,        # host 3.29e-7; device 3.3e-7, device vs host 1.2e-7
+        "srb.xdot": 5e-6,  # host 1.12e-6; device 1.1e-6, device vs host 0
+        "srb.Ac": 5e-7,    # host 1.17e-7; device 1.2e-7, device vs host 0
+        "srb.Bc": 2e-6,    # host 2.92e-7; device 2.9e-7, device vs host 0
+    },
+}
+
+
+# The two known-answer fixtures (tests/golden/make_golden.py): uniform-random states, and
+# knots of the oracle's C5 solution (each tagged with its phase's mode).
+KAT_FIXTURES = ("kat_model.npz", "kat_model_traj.npz")
+DYN_NAME = {1: "Dyn_BS", 2: "Dyn_FL", 3: "Dyn_FS", 4: "Dyn_FL"}  # mode 4 is flight too
+IMP_NAME = {0: "Imp_F", 1: "Imp_B"}
+TD_NAME = {0: "WB_FL1_terminal_constr", 1: "WB_FL2_terminal_constr"}
+JAC_NAME = {0: "Jacob_F", 1: "Jacob_B"}
 
 
 def golden(name):
     return dict(np.load(os.path.join(GOLDEN, name), allow_pickle=False))
+
+
+def kat_rows(kat, mode=None, foot=None):
+    """Points of a fixture a dynamics mode / a touchdown impact of `foot` is checked at: all
+    of the random fixture; of the trajectory fixture the knots of that mode, and for the
+    impact the last knots of the flight phase that ends with that foot's touchdown."""
+    if "mode" not in kat:
+        return np.arange(len(kat["x"]))
+    if mode is not None:
+        return np.where(kat["mode"] == mode)[0]
+    if foot is not None:
+        return np.where(kat["pre_td"] & (kat["mode"] == (2 if foot == 0 else 4)))[0]
+    return np.arange(len(kat["x"]))
 
 
 def rel_err(a, b):
@@ -25,3 +101,38 @@ def rel_err(a, b):
     if a.size == 0:
         return 0.0
     return float(np.max(np.abs(a - b) / np.maximum(1.0, np.abs(b))))
+
+
+def norm_err(a, b):
+    """Norm-relative error of [points][...] arrays, worst point: per point
+    max|a - b| / max(1, max|b|) over the point's whole output array.  (Per element, rel_err
+    says little in fp32: Ac holds entries of 3e4 beside entries of 1e-2.)"""
+    a = np.asarray(a, dtype=float)
+    b = np.asarray(b, dtype=float)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    if a.size == 0:
+        return 0.0
+    a, b = a.reshape(len(a), -1), b.reshape(len(b), -1)
+    return float(np.max(np.abs(a - b).max(axis=1) / np.maximum(1.0, np.abs(b).max(axis=1))))
+
+
+_structure = {}
+
+
+def kat_structure(key):
+    """Entries of reference output `key` (e.g. "Dyn_BS_par.Ac") that are exactly 0, and
+    exactly 1, at every one of the 64 random points: the function's sparsity pattern."""
+    if key not in _structure:
+        ref = golden(KAT_FIXTURES[0])[key]
+        _structure[key] = ((ref == 0).all(axis=0), (ref == 1).all(axis=0))
+    return _structure[key]
+
+
+def assert_structure(got, key):
+    """The structural zeros and ones of `key` are exact in got [points][...] (the sweep's
+    structure-exploiting [A B] form relies on them; rel_err lets 1e-9 through)."""
+    zero, one = kat_structure(key)
+    got = np.asarray(got)
+    assert got.shape[1:] == zero.shape, (key, got.shape)
+    assert (got[:, zero] == 0).all(), (key, "structural zero", np.abs(got[:, zero]).max())
+    assert (got[:, one] == 1).all(), (key, "structural one")

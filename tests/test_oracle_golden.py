@@ -76,3 +76,27 @@ def test_oracle_init_only_is_the_pd_warm_start():
     np.testing.assert_array_equal(r["X"][0, :14], x0[0])
     assert np.all(r["X"][0, lx_wb:] == 0)
     assert np.all(np.isfinite(r["X"])) and np.abs(r["X"][0, 14:lx_wb]).max() > 0
+
+
+@need_oracle
+def test_trajectory_kat_fixture_regenerates():
+    """tests/golden/make_golden.py make_kat_traj: the same knots of the same problems, their
+    states as the oracle solves them here (to the solve fixtures' tolerance scaled by the worst
+    problem's amplification, ~1e4), and the reference kernels bit for bit at the stored states."""
+    import importlib.util
+    import os
+    from _util import GOLDEN
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(GOLDEN, "make_golden.py"))
+    mg = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mg)
+    k = golden("kat_model_traj.npz")
+    new = mg.make_kat_traj()
+    assert set(new) == set(k)
+    for key in ("mode", "pre_td", "problem", "srb.mode", "srb.s"):
+        np.testing.assert_array_equal(new[key], k[key], err_msg=key)
+    for key in ("x", "u", "srb.x", "srb.u", "srb.p"):
+        np.testing.assert_allclose(new[key], k[key], rtol=1e-9, atol=1e-9, err_msg=key)
+    assert (k["problem"] == mg.TRAJ_WORST).sum() == 16 and k["pre_td"].sum() >= 16
+    again = mg.eval_kat(*[k[key] for key in ("x", "u", "srb.x", "srb.u", "srb.p", "srb.s")])
+    for key in again:
+        np.testing.assert_array_equal(again[key], k[key], err_msg=key)
