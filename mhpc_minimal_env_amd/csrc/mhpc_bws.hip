@@ -46,9 +46,9 @@
 
 #include "mhpc_device.h"
 #include "mhpc_dpp.h"
+#include "mhpc_launch.h"
 
 namespace MHPC_NS {
-int launch_problems(const SolveParams& sp);  // mhpc_kernels.hip
 // MHPC_BWS_VARIANT_NS: a second instantiation of this file in one library (the fp32 library's
 // float sweep, MHPC_BWS_F64=0) lives in a nested namespace -- its kernels and entry points
 // (launch_bws, bws_split, bws_auto_variant) do not collide with the default build's.

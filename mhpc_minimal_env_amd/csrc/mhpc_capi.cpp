@@ -49,6 +49,13 @@ static int fail_exception(const char* fn) {
     }                                                                                  \
   } while (0)
 
+// Problems of the handle (0 for a null handle, which FWD then refuses)
+static int batch_of(const mhpc_handle* h) {
+  if (!h) return 0;
+  return h->precision == 32 ? mhpc32::api_batch((mhpc32::Handle*)h->impl)
+                            : mhpc::api_batch((mhpc::Handle*)h->impl);
+}
+
 extern "C" const char* mhpc_version(void) {
   return "mhpc_minimal_env_amd 0.2 (gfx950; fp64 and fp32 solve paths)";
 }
@@ -107,10 +114,7 @@ extern "C" int mhpc_initialize(mhpc_handle* h) { FWD(initialize); }
 extern "C" int mhpc_solve(mhpc_handle* h, int32_t* status) { FWD(solve, status); }
 extern "C" int mhpc_get_phase(mhpc_handle* h, int phase, double* x, double* u, double* y, double* K,
                               double* du, double* Vx) {
-  int B = 0;
-  if (h) B = h->precision == 32 ? mhpc32::api_batch((mhpc32::Handle*)h->impl)
-                                : mhpc::api_batch((mhpc::Handle*)h->impl);
-  FWD(get_phase, phase, 0, B, x, u, y, K, du, Vx);
+  FWD(get_phase, phase, 0, batch_of(h), x, u, y, K, du, Vx);
 }
 extern "C" int mhpc_get_phase_problems(mhpc_handle* h, int phase, int first, int count, double* x,
                                        double* u, double* y, double* K, double* du, double* Vx) {
@@ -138,10 +142,7 @@ extern "C" int mhpc_advance_x0(mhpc_handle* h, int n_phases, const double* dx) {
 }
 extern "C" int mhpc_get_x0(mhpc_handle* h, double* x0) { FWD(get_x0, x0); }
 extern "C" int mhpc_get_cost_gradients(mhpc_handle* h, int phase, double* lx, double* Phix) {
-  int B = 0;
-  if (h) B = h->precision == 32 ? mhpc32::api_batch((mhpc32::Handle*)h->impl)
-                                : mhpc::api_batch((mhpc::Handle*)h->impl);
-  FWD(get_cost_gradients, phase, 0, B, lx, Phix);
+  FWD(get_cost_gradients, phase, 0, batch_of(h), lx, Phix);
 }
 extern "C" int mhpc_get_cost_gradients_problems(mhpc_handle* h, int phase, int first, int count,
                                                 double* lx, double* Phix) {

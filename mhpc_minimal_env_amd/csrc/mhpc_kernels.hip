@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "mhpc_device.h"
+#include "mhpc_launch.h"
 #include "mhpc_model_pair.h"
 
 namespace MHPC_NS {
@@ -954,7 +955,6 @@ __global__ __launch_bounds__(64) void k_eps_rollout(SolveParams sp, DevBufs d, i
   vo[t] = real(sqrt(viol2));
 }
 
-constexpr int PREC_W = 22;  // k_policy_rollout's knot record: x 14, u 4, y 4
 // ============================================================================================
 // k_policy_rollout: the solved feedback policy u = u_nom + K (x - x_nom) run from start states
 // of the caller's choosing -- the reference's set_initial_condition(x) followed by
@@ -1200,7 +1200,7 @@ __global__ void k_cost_grad(SolveParams sp, DevBufs d, int g, int p, int b0, int
 // problem's layout lives in its buffer L.buf[p]; k_store_save runs with the layouts before
 // an update, k_store_load with those after it.
 // ============================================================================================
-constexpr int SREC = KS + 56 + 4 + 14;
+constexpr int SREC = kStoreRec;
 
 __global__ void k_store_save(SolveParams sp, DevBufs d, real* store, int nbk, int spmax) {
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,0 +1,72 @@
+// What the kernel translation units (mhpc_kernels.hip, mhpc_bws.hip) export to the host
+// runtime: the launchers, the launch-shape queries, and the record widths the host unpacks.
+// Included by both kernel files and by mhpc_runtime.cpp, so a prototype that no longer matches
+// its definition fails to compile instead of failing to link.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "mhpc_solver.h"
+
+namespace MHPC_NS {
+
+// ---- mhpc_kernels.hip -----------------------------------------------------------------------
+hipError_t launch_init(const SolveParams& sp, const DevBufs& d, hipStream_t s);
+hipError_t launch_init_params(const SolveParams& sp, const DevBufs& d, hipStream_t s);
+hipError_t launch_reset(const SolveParams& sp, const DevBufs& d, hipStream_t s);
+hipError_t launch_reset_arrays(const SolveParams& sp, const DevBufs& d, hipStream_t s);
+hipError_t launch_cost(const SolveParams& sp, const DevBufs& d, int al_iter, hipStream_t s);
+hipError_t launch_rollout(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter,
+                          int max_ddp, int full, hipStream_t s);
+hipError_t launch_partials(const SolveParams& sp, const DevBufs& d, hipStream_t s, hipStream_t s3,
+                           hipEvent_t fork, hipEvent_t join);
+hipError_t launch_al_end(const SolveParams& sp, const DevBufs& d, int last, hipStream_t s);
+hipError_t launch_export(const SolveParams& sp, const DevBufs& d, hipStream_t s);
+hipError_t launch_export_ref(const SolveParams& sp, const DevBufs& d, int b0, int nb, hipStream_t s);
+hipError_t launch_reduce_counters(const SolveParams& sp, const DevBufs& d,
+                                  unsigned long long* out, hipStream_t s);
+int launch_problems(const SolveParams& sp);  // problems of a launch (a sub-batch's share)
+int ro_store_default();
+int ro_store_auto(const SolveParams& sp);
+
+// Phase-buffer store of the receding-horizon loop, [B][spmax][nbk][kStoreRec]: buffers of
+// N_TIMESTEPS_MAX (MHPCLocomotion.h) knots at least; record = x,u,y + K + du + G
+constexpr int kPhaseBufKnots = 110;
+constexpr int kStoreRec = KS + 56 + 4 + 14;
+hipError_t launch_store(const SolveParams& sp, const DevBufs& d, real* store, int nbk, int spmax,
+                        int save, hipStream_t s);
+
+hipError_t launch_cost_grad(const SolveParams& sp, const DevBufs& d, int g, int p, int N, int b0,
+                            int nb, real* lx, real* phix, hipStream_t s);
+hipError_t launch_eps_rollout(const SolveParams& sp, const DevBufs& d, int n_eps,
+                              const real* eps, real* J, real* viol, hipStream_t s);
+constexpr int PREC_W = 22;  // k_policy_rollout's knot record: x 14, u 4, y 4
+hipError_t launch_policy_rollout(const SolveParams& sp, const DevBufs& d, int n_s, int b0, int nb,
+                                 const real* xs, const double* dx, int n_phases, int rec_p,
+                                 real* J, real* viol, real* xe, real* rec, hipStream_t s);
+
+// model evaluation hooks (n points each)
+hipError_t launch_eval_wb_dyn(int n, int mode, const real* x, const real* u, real* xd,
+                              real* y, hipStream_t s);
+hipError_t launch_eval_wb_dyn_pair(int n, int mode, const real* x, const real* u, real* xd,
+                                   real* y, hipStream_t s);
+hipError_t launch_eval_wb_aux(int n, int foot, const real* x, real* h, real* hx, real* hxx,
+                              real* J, real* Jd, hipStream_t s);
+hipError_t launch_eval_wb_par(int n, int mode, const real* x, const real* u, real* Ac,
+                              real* Bc, real* C, real* D, hipStream_t s);
+hipError_t launch_eval_wb_impact(int n, int foot, const real* x, real* xp, real* Px,
+                                 hipStream_t s);
+hipError_t launch_eval_srb(int n, const real* x, const real* u, const real* p,
+                           const real* c, real* xd, real* Ac, real* Bc, hipStream_t s);
+
+// ---- mhpc_bws.hip ---------------------------------------------------------------------------
+hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, real update_reg, int part,
+                      hipStream_t s);
+bool bws_split(const SolveParams& sp);
+#ifdef MHPC_FP32
+namespace fsweep {  // the float-arithmetic sweep (mhpc_bws.hip built with MHPC_BWS_F64=0)
+hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, real update_reg, int part,
+                      hipStream_t s);
+}
+#endif
+
+}  // namespace MHPC_NS

@@ -14,51 +14,8 @@
 #include <vector>
 
 #include "../../include/mhpc_capi.h"
-#include "mhpc_solver.h"
-
-namespace MHPC_NS {
-hipError_t launch_init(const SolveParams&, const DevBufs&, hipStream_t);
-hipError_t launch_init_params(const SolveParams&, const DevBufs&, hipStream_t);
-hipError_t launch_reset_arrays(const SolveParams&, const DevBufs&, hipStream_t);
-hipError_t launch_rollout(const SolveParams&, const DevBufs&, int, int, int, int, hipStream_t);
-hipError_t launch_partials(const SolveParams&, const DevBufs&, hipStream_t, hipStream_t, hipEvent_t,
-                           hipEvent_t);
-hipError_t launch_bws(const SolveParams&, const DevBufs&, real, int, hipStream_t);
-bool bws_split(const SolveParams&);
-#ifdef MHPC_FP32
-namespace fsweep {  // the float-arithmetic sweep (mhpc_bws.hip built with MHPC_BWS_F64=0)
-hipError_t launch_bws(const SolveParams&, const DevBufs&, real, int, hipStream_t);
-}
-#endif
-int ro_store_default();
-int ro_store_auto(const SolveParams&);
-hipError_t launch_cost(const SolveParams&, const DevBufs&, int, hipStream_t);
-hipError_t launch_reset(const SolveParams&, const DevBufs&, hipStream_t);
-hipError_t launch_store(const SolveParams&, const DevBufs&, real*, int, int, int, hipStream_t);
-// N_TIMESTEPS_MAX (MHPCLocomotion.h): knots per phase buffer; record = x,u,y + K + du + G
-constexpr int kPhaseBufKnots = 110;
-constexpr int kStoreRec = KS + 56 + 4 + 14;
-constexpr int PREC_W = 22;  // k_policy_rollout's knot record: x 14, u 4, y 4
-hipError_t launch_cost_grad(const SolveParams&, const DevBufs&, int, int, int, int, int, real*, real*,
-                            hipStream_t);
-hipError_t launch_eps_rollout(const SolveParams&, const DevBufs&, int, const real*, real*,
-                              real*, hipStream_t);
-hipError_t launch_policy_rollout(const SolveParams&, const DevBufs&, int, int, int, const real*,
-                                 const double*, int, int, real*, real*, real*, real*, hipStream_t);
-hipError_t launch_al_end(const SolveParams&, const DevBufs&, int, hipStream_t);
-hipError_t launch_export(const SolveParams&, const DevBufs&, hipStream_t);
-hipError_t launch_export_ref(const SolveParams&, const DevBufs&, int, int, hipStream_t);
-hipError_t launch_reduce_counters(const SolveParams&, const DevBufs&, unsigned long long*,
-                                  hipStream_t);
-hipError_t launch_eval_wb_dyn(int, int, const real*, const real*, real*, real*, hipStream_t);
-hipError_t launch_eval_wb_dyn_pair(int, int, const real*, const real*, real*, real*, hipStream_t);
-hipError_t launch_eval_wb_par(int, int, const real*, const real*, real*, real*, real*,
-                              real*, hipStream_t);
-hipError_t launch_eval_wb_aux(int, int, const real*, real*, real*, real*, real*, real*, hipStream_t);
-hipError_t launch_eval_wb_impact(int, int, const real*, real*, real*, hipStream_t);
-hipError_t launch_eval_srb(int, const real*, const real*, const real*, const real*,
-                           real*, real*, real*, hipStream_t);
-}  // namespace MHPC_NS
+#include "mhpc_devtemp.h"
+#include "mhpc_launch.h"
 
 extern thread_local std::string mhpc_g_err;  // mhpc_capi.cpp (mhpc_last_error)
 
@@ -799,17 +756,29 @@ static int x0_row(const Handle* h) {
   return 6;
 }
 
+// Caller rows src [count][n_s][r] (r = x0_row) of problems [first, first + count) as the device
+// rows of 14: a problem with a whole-body phase has 14 entries, an SRB-only one the first 6 of
+// its row; the rest is zero.  unpad_rows is the way back for rows of one width.
+template <class E>
+static std::vector<E> pad_rows(const Handle* h, int first, int count, int n_s, const double* src) {
+  const int r = x0_row(h);
+  std::vector<E> out((size_t)count * n_s * 14, E(0));
+  for (int b = 0; b < count; ++b) {
+    const int nb = h->lays[h->lid[first + b]].n_wb > 0 ? 14 : 6;
+    for (size_t t = (size_t)b * n_s; t < (size_t)(b + 1) * n_s; ++t)
+      std::copy(src + t * r, src + t * r + nb, out.begin() + t * 14);
+  }
+  return out;
+}
+static void unpad_rows(const real* src, size_t rows, int r, double* dst) {
+  for (size_t t = 0; t < rows; ++t)
+    for (int i = 0; i < r; ++i) dst[t * r + i] = src[t * 14 + i];
+}
+
 int api_set_x0(Handle* h, const double* x0) {
   if (!h || !x0) return fail(MHPC_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(h->device));
-  // rows of 14 when any layout starts with a whole-body phase (an SRB-only problem reads the
-  // first 6 entries of its row), else 6
-  const int n0 = x0_row(h);
-  std::vector<real> pad((size_t)h->sp.B * 14, real(0));
-  for (int b = 0; b < h->sp.B; ++b) {
-    const int nb = h->lays[h->lid[b]].n_wb > 0 ? 14 : 6;
-    for (int i = 0; i < nb; ++i) pad[(size_t)b * 14 + i] = (real)x0[(size_t)b * n0 + i];
-  }
+  const std::vector<real> pad = pad_rows<real>(h, 0, h->sp.B, 1, x0);
   HIPCHK(hipMemcpyAsync(h->d.x0, pad.data(), pad.size() * sizeof(real), hipMemcpyHostToDevice,
                         h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1259,6 +1228,18 @@ static int get_phase_run(Handle* h, int phase, int n, int N, int ko, size_t b0, 
   return MHPC_OK;
 }
 
+// Runs of consecutive problems of [first, first + count) with the same key(b): run(r0, n) for
+// each in turn, until one returns non-zero (returned).
+template <class Key, class Run>
+static int for_runs(int first, int count, Key key, Run run) {
+  for (int r0 = first, r1; r0 < first + count; r0 = r1) {
+    for (r1 = r0 + 1; r1 < first + count && key(r1) == key(r0); ++r1) {
+    }
+    if (int rc = run(r0, r1 - r0)) return rc;
+  }
+  return 0;
+}
+
 // Shape check of a phase over a problem range: *n, *N of the phase (one shape for the range)
 static int range_phase_shape(const Handle* h, int phase, int first, int count, int* n, int* N) {
   if (first < 0 || count < 1 || first > h->sp.B - count)
@@ -1284,18 +1265,13 @@ int api_get_phase(Handle* h, int phase, int first, int count, double* x, double*
   int rc = range_phase_shape(h, phase, first, count, &n, &N);
   if (rc) return rc;
   HIPCHK(hipSetDevice(h->device));
-  for (int r0 = first; r0 < first + count;) {
-    const int ko = h->lays[h->lid[r0]].ko[phase];
-    int r1 = r0 + 1;
-    while (r1 < first + count && h->lays[h->lid[r1]].ko[phase] == ko) ++r1;
+  auto ko = [&](int b) { return h->lays[h->lid[b]].ko[phase]; };
+  return for_runs(first, count, ko, [&](int r0, int nb) {
     const size_t o = (size_t)(r0 - first) * N;
     auto at = [&](double* p, int per) { return p ? p + o * per : nullptr; };
-    rc = get_phase_run(h, phase, n, N, ko, r0, r1 - r0, at(x, n), at(u, 4), at(y, 4), at(K, 4 * n),
-                       at(du, 4), at(Vx, n));
-    if (rc) return rc;
-    r0 = r1;
-  }
-  return MHPC_OK;
+    return get_phase_run(h, phase, n, N, ko(r0), r0, nb, at(x, n), at(u, 4), at(y, 4), at(K, 4 * n),
+                         at(du, 4), at(Vx, n));
+  });
 }
 
 int api_get_scalars(Handle* h, double* J, double* dV_exp, double* viol,
@@ -1321,6 +1297,23 @@ int api_get_scalars(Handle* h, double* J, double* dV_exp, double* viol,
   return MHPC_OK;
 }
 
+// MHPC_ERR_DEVICE naming the entry point fn and the HIP error
+static int dev_fail(const char* fn, hipError_t e) {
+  return fail(MHPC_ERR_DEVICE, std::string(fn) + ": " + hipGetErrorString(e));
+}
+// One launch on the handle's stream between its ev0 / ev1, the outputs of t staged after it,
+// and the launch's time to *ms (ms may be null); all of it folded into t.e.
+template <class Launch>
+static void timed_launch(Handle* h, DevTemp<real>& t, float* ms, Launch launch) {
+  if (t.e == hipSuccess) t.e = hipEventRecord(h->ev0, h->stream);
+  if (t.e == hipSuccess) t.e = launch();
+  if (t.e == hipSuccess) t.e = hipEventRecord(h->ev1, h->stream);
+  t.stage();
+  float el = 0;
+  if (t.e == hipSuccess) t.e = hipEventElapsedTime(&el, h->ev0, h->ev1);
+  if (t.e == hipSuccess && ms) *ms = el;
+}
+
 int api_rollout_costs(Handle* h, int n_eps, const double* eps, double* J,
                                   double* viol, float* ms) {
   if (!h || !eps || !J) return fail(MHPC_ERR_INVALID, "null argument");
@@ -1332,34 +1325,12 @@ int api_rollout_costs(Handle* h, int n_eps, const double* eps, double* J,
     return fail(MHPC_ERR_STATE,
                 "parameter sets changed: call mhpc_initialize or mhpc_update_problem first");
   HIPCHK(hipSetDevice(h->device));
-  const size_t B = h->sp.B, n = B * (size_t)n_eps;
-  real *deps = nullptr, *dJ = nullptr, *dv = nullptr;
-  std::vector<real> heps(eps, eps + n_eps), hJ(n), hv(n);
-  auto cleanup = [&]() {
-    if (deps) (void)hipFree(deps);
-    if (dJ) (void)hipFree(dJ);
-    if (dv) (void)hipFree(dv);
-  };
-  hipError_t e = hipMalloc((void**)&deps, n_eps * sizeof(real));
-  if (e == hipSuccess) e = hipMalloc((void**)&dJ, n * sizeof(real));
-  if (e == hipSuccess) e = hipMalloc((void**)&dv, n * sizeof(real));
-  if (e == hipSuccess) e = hipMemcpyAsync(deps, heps.data(), n_eps * sizeof(real), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipEventRecord(h->ev0, h->stream);
-  if (e == hipSuccess) e = launch_eps_rollout(h->sp, h->d, n_eps, deps, dJ, dv, h->stream);
-  if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(hJ.data(), dJ, n * sizeof(real), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(hv.data(), dv, n * sizeof(real), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e == hipSuccess)
-    for (size_t i = 0; i < n; ++i) {
-      J[i] = hJ[i];
-      if (viol) viol[i] = hv[i];
-    }
-  float t = 0;
-  if (e == hipSuccess) e = hipEventElapsedTime(&t, h->ev0, h->ev1);
-  cleanup();
-  if (e != hipSuccess) return fail(MHPC_ERR_DEVICE, std::string("mhpc_rollout_costs: ") + hipGetErrorString(e));
-  if (ms) *ms = t;
+  const size_t n = (size_t)h->sp.B * n_eps;
+  DevTemp<real> t(h->stream);
+  real *deps = t.in(eps, n_eps), *dJ = t.out(J, n), *dv = t.out(viol, n);
+  timed_launch(h, t, ms,
+               [&] { return launch_eps_rollout(h->sp, h->d, n_eps, deps, dJ, dv, h->stream); });
+  if (t.fetch() != hipSuccess) return dev_fail("mhpc_rollout_costs", t.e);
   return MHPC_OK;
 }
 
@@ -1376,21 +1347,15 @@ static int policy_ready(const Handle* h) {
                 "constraint parameters changed: call mhpc_initialize or mhpc_update_problem first");
   return MHPC_OK;
 }
-// Start states xs [count][n_s][r] of problems [first, first + count) as the device rows of 14
-// (mhpc_set_x0's padding and rounding); MHPC_ERR_INVALID for a non-finite entry.
+// Caller rows xs [count][n_s][r] of problems [first, first + count) as the device rows of 14
+// (mhpc_set_x0's padding and, for E = real, rounding); MHPC_ERR_INVALID for a non-finite entry
+// of what.
+template <class E>
 static int policy_pack(const Handle* h, int first, int count, int n_s, const double* xs,
-                       std::vector<real>& out) {
-  const int r = x0_row(h);
-  for (size_t i = 0; i < (size_t)count * n_s * r; ++i)
-    if (!std::isfinite(xs[i])) return fail(MHPC_ERR_INVALID, "start states must be finite");
-  out.assign((size_t)count * n_s * 14, real(0));
-  for (int b = 0; b < count; ++b) {
-    const int nb = h->lays[h->lid[first + b]].n_wb > 0 ? 14 : 6;
-    for (int e = 0; e < n_s; ++e) {
-      const size_t t = (size_t)b * n_s + e;
-      for (int i = 0; i < nb; ++i) out[t * 14 + i] = (real)xs[t * r + i];
-    }
-  }
+                       const char* what, std::vector<E>& out) {
+  for (size_t i = 0; i < (size_t)count * n_s * x0_row(h); ++i)
+    if (!std::isfinite(xs[i])) return fail(MHPC_ERR_INVALID, std::string(what) + " must be finite");
+  out = pad_rows<E>(h, first, count, n_s, xs);
   return MHPC_OK;
 }
 static int min_phases(const Handle* h) {
@@ -1408,44 +1373,20 @@ int api_rollout_policy(Handle* h, int n_samples, const double* xs, int n_phases,
     return fail(MHPC_ERR_INVALID, "n_samples out of range");
   if (n_phases < 0 || n_phases > min_phases(h))
     return fail(MHPC_ERR_INVALID, "n_phases out of range");
-  const int B = h->sp.B, r = x0_row(h);
+  const int B = h->sp.B;
   const size_t n = (size_t)B * n_samples;
-  std::vector<real> hxs, hJ(n), hv(n), hxe(x_end ? n * 14 : 0);
-  if ((rc = policy_pack(h, 0, B, n_samples, xs, hxs))) return rc;
+  std::vector<real> hxs;
+  if ((rc = policy_pack(h, 0, B, n_samples, xs, "start states", hxs))) return rc;
   HIPCHK(hipSetDevice(h->device));
-  real *dxs = nullptr, *dJ = nullptr, *dv = nullptr, *dxe = nullptr;
-  auto cleanup = [&]() {
-    if (dxs) (void)hipFree(dxs);
-    if (dJ) (void)hipFree(dJ);
-    if (dv) (void)hipFree(dv);
-    if (dxe) (void)hipFree(dxe);
-  };
-  hipError_t e = hipMalloc((void**)&dxs, n * 14 * sizeof(real));
-  if (e == hipSuccess) e = hipMalloc((void**)&dJ, n * sizeof(real));
-  if (e == hipSuccess) e = hipMalloc((void**)&dv, n * sizeof(real));
-  if (e == hipSuccess && x_end) e = hipMalloc((void**)&dxe, n * 14 * sizeof(real));
-  if (e == hipSuccess) e = hipMemcpyAsync(dxs, hxs.data(), n * 14 * sizeof(real), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipEventRecord(h->ev0, h->stream);
-  if (e == hipSuccess)
-    e = launch_policy_rollout(h->sp, h->d, n_samples, 0, B, dxs, nullptr, n_phases, 0, dJ, dv, dxe,
-                              nullptr, h->stream);
-  if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(hJ.data(), dJ, n * sizeof(real), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(hv.data(), dv, n * sizeof(real), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess && x_end)
-    e = hipMemcpyAsync(hxe.data(), dxe, n * 14 * sizeof(real), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  float t = 0;
-  if (e == hipSuccess) e = hipEventElapsedTime(&t, h->ev0, h->ev1);
-  cleanup();
-  if (e != hipSuccess) return fail(MHPC_ERR_DEVICE, std::string("mhpc_rollout_policy: ") + hipGetErrorString(e));
-  for (size_t i = 0; i < n; ++i) {
-    J[i] = hJ[i];
-    if (viol) viol[i] = hv[i];
-    if (x_end)
-      for (int j = 0; j < r; ++j) x_end[i * r + j] = hxe[i * 14 + j];
-  }
-  if (ms) *ms = t;
+  DevTemp<real> t(h->stream);
+  real *dxs = t.in(std::move(hxs)), *dJ = t.out(J, n), *dv = t.out(viol, n);
+  real* dxe = x_end ? t.out(nullptr, n * 14) : nullptr;
+  timed_launch(h, t, ms, [&] {
+    return launch_policy_rollout(h->sp, h->d, n_samples, 0, B, dxs, nullptr, n_phases, 0, dJ, dv,
+                                 dxe, nullptr, h->stream);
+  });
+  if (t.fetch() != hipSuccess) return dev_fail("mhpc_rollout_policy", t.e);
+  if (x_end) unpad_rows(t.staged(dxe), n, x0_row(h), x_end);
   return MHPC_OK;
 }
 
@@ -1458,25 +1399,19 @@ int api_rollout_policy_phase(Handle* h, int phase, int first, int count, int n_s
     return fail(MHPC_ERR_INVALID, "n_samples out of range");
   int nx = 0, N = 0;
   if ((rc = range_phase_shape(h, phase, first, count, &nx, &N))) return rc;
-  const size_t S = n_samples, n = (size_t)count * S, nrec = n * N * PREC_W;
-  std::vector<real> hxs, hrec(nrec);
-  if ((rc = policy_pack(h, first, count, n_samples, xs, hxs))) return rc;
+  const size_t S = n_samples, n = (size_t)count * S;
+  std::vector<real> hxs;
+  if ((rc = policy_pack(h, first, count, n_samples, xs, "start states", hxs))) return rc;
   HIPCHK(hipSetDevice(h->device));
-  real *dxs = nullptr, *drec = nullptr;
-  hipError_t e = hipMalloc((void**)&dxs, n * 14 * sizeof(real));
-  if (e == hipSuccess) e = hipMalloc((void**)&drec, nrec * sizeof(real));
-  if (e == hipSuccess) e = hipMemcpyAsync(dxs, hxs.data(), n * 14 * sizeof(real), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess)
-    e = launch_policy_rollout(h->sp, h->d, n_samples, first, count, dxs, nullptr, 0, phase, nullptr,
-                              nullptr, nullptr, drec, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(hrec.data(), drec, nrec * sizeof(real), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (dxs) (void)hipFree(dxs);
-  if (drec) (void)hipFree(drec);
-  if (e != hipSuccess)
-    return fail(MHPC_ERR_DEVICE, std::string("mhpc_rollout_policy_phase: ") + hipGetErrorString(e));
+  DevTemp<real> t(h->stream);
+  real *dxs = t.in(std::move(hxs)), *drec = t.out(nullptr, n * N * PREC_W);
+  if (t.e == hipSuccess)
+    t.e = launch_policy_rollout(h->sp, h->d, n_samples, first, count, dxs, nullptr, 0, phase, nullptr,
+                                nullptr, nullptr, drec, h->stream);
+  if (t.fetch() != hipSuccess) return dev_fail("mhpc_rollout_policy_phase", t.e);
   // device records [count][N][PREC_W][n_s] (the sample fastest: coalesced stores); the last
   // knot has no u, y and an SRB knot no y: zero rows
+  const real* hrec = t.staged(drec);
   const bool wb = nx == 14;
   for (size_t b = 0; b < (size_t)count; ++b)
     for (size_t s = 0; s < S; ++s)
@@ -1505,30 +1440,16 @@ int api_advance_x0(Handle* h, int n_phases, const double* dx) {
     if (L.n_wb > 0 && n_phases - 1 >= L.n_wb)
       return fail(MHPC_ERR_INVALID,
                   "phase n_phases-1 is an SRB phase: its end state cannot start a whole-body horizon");
-  const int B = h->sp.B, r = x0_row(h);
+  const int B = h->sp.B;
   std::vector<double> hdx;
-  if (dx) {
-    for (size_t i = 0; i < (size_t)B * r; ++i)
-      if (!std::isfinite(dx[i])) return fail(MHPC_ERR_INVALID, "dx must be finite");
-    hdx.assign((size_t)B * 14, 0.0);
-    for (int b = 0; b < B; ++b) {
-      const int nb = h->lays[h->lid[b]].n_wb > 0 ? 14 : 6;
-      for (int i = 0; i < nb; ++i) hdx[(size_t)b * 14 + i] = dx[(size_t)b * r + i];
-    }
-  }
+  if (dx && (rc = policy_pack(h, 0, B, 1, dx, "dx", hdx))) return rc;
   HIPCHK(hipSetDevice(h->device));
-  double* ddx = nullptr;
-  hipError_t e = hipSuccess;
-  if (dx) {
-    e = hipMalloc((void**)&ddx, hdx.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(ddx, hdx.data(), hdx.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
-  }
-  if (e == hipSuccess)
-    e = launch_policy_rollout(h->sp, h->d, 1, 0, B, h->d.x0, ddx, n_phases, 0, nullptr, nullptr,
-                              h->d.x0, nullptr, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (ddx) (void)hipFree(ddx);
-  if (e != hipSuccess) return fail(MHPC_ERR_DEVICE, std::string("mhpc_advance_x0: ") + hipGetErrorString(e));
+  DevTemp<real> t(h->stream);
+  const double* ddx = dx ? t.in_double(std::move(hdx)) : nullptr;  // added in double
+  if (t.e == hipSuccess)
+    t.e = launch_policy_rollout(h->sp, h->d, 1, 0, B, h->d.x0, ddx, n_phases, 0, nullptr, nullptr,
+                                h->d.x0, nullptr, h->stream);
+  if (t.fetch() != hipSuccess) return dev_fail("mhpc_advance_x0", t.e);  // no outputs: the sync
   h->x0_set = true;
   h->x0_changed = true;  // as after mhpc_set_x0
   return MHPC_OK;
@@ -1538,47 +1459,30 @@ int api_get_x0(Handle* h, double* x0) {
   if (!h || !x0) return fail(MHPC_ERR_INVALID, "null argument");
   if (!h->initialized) return fail(MHPC_ERR_STATE, "not initialized");
   HIPCHK(hipSetDevice(h->device));
-  const int B = h->sp.B, r = x0_row(h);
-  std::vector<real> buf((size_t)B * 14);
+  std::vector<real> buf((size_t)h->sp.B * 14);
   D2H(buf.data(), h->d.x0, buf.size() * sizeof(real));
-  for (int b = 0; b < B; ++b)
-    for (int i = 0; i < r; ++i) x0[(size_t)b * r + i] = buf[(size_t)b * 14 + i];
+  unpad_rows(buf.data(), h->sp.B, x0_row(h), x0);
   return MHPC_OK;
 }
 
 int api_get_cost_gradients(Handle* h, int phase, int first, int count, double* lx, double* Phix) {
   if (!h) return fail(MHPC_ERR_INVALID, "null handle");
   if (!h->initialized) return fail(MHPC_ERR_STATE, "not initialized");
-  const SolveParams& sp = h->sp;
   int n = 0, N = 0;
   int rc = range_phase_shape(h, phase, first, count, &n, &N);
   if (rc) return rc;
   HIPCHK(hipSetDevice(h->device));
-  const size_t nlx = (size_t)count * (N - 1) * n, nph = (size_t)count * n;
-  real *dlx = nullptr, *dph = nullptr;
-  std::vector<real> hlx(nlx), hph(nph);
-  hipError_t e = hipMalloc((void**)&dlx, nlx * sizeof(real) + 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&dph, nph * sizeof(real));
+  DevTemp<real> t(h->stream);
+  real *dlx = t.out(lx, (size_t)count * (N - 1) * n), *dph = t.out(Phix, (size_t)count * n);
   // one launch per run of problems of the same group
-  for (int r0 = first; r0 < first + count && e == hipSuccess;) {
-    const int g = h->lid[r0];
-    int r1 = r0 + 1;
-    while (r1 < first + count && h->lid[r1] == g) ++r1;
-    const size_t o = (size_t)(r0 - first);
-    e = launch_cost_grad(sp, h->d, g, phase, N, r0, r1 - r0, dlx + o * (N - 1) * n, dph + o * n,
-                         h->stream);
-    r0 = r1;
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(hlx.data(), dlx, nlx * sizeof(real), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(hph.data(), dph, nph * sizeof(real), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e == hipSuccess) {
-    if (lx) std::copy(hlx.begin(), hlx.end(), lx);
-    if (Phix) std::copy(hph.begin(), hph.end(), Phix);
-  }
-  if (dlx) (void)hipFree(dlx);
-  if (dph) (void)hipFree(dph);
-  if (e != hipSuccess) return fail(MHPC_ERR_DEVICE, std::string("mhpc_get_cost_gradients: ") + hipGetErrorString(e));
+  if (t.e == hipSuccess)
+    for_runs(first, count, [&](int b) { return h->lid[b]; }, [&](int r0, int nb) {
+      const size_t o = (size_t)(r0 - first);
+      t.e = launch_cost_grad(h->sp, h->d, h->lid[r0], phase, N, r0, nb, dlx + o * (N - 1) * n,
+                             dph + o * n, h->stream);
+      return t.e != hipSuccess;
+    });
+  if (t.fetch() != hipSuccess) return dev_fail("mhpc_get_cost_gradients", t.e);
   return MHPC_OK;
 }
 
@@ -1782,17 +1686,14 @@ int api_get_reference(Handle* h, int phase, int first, int count, double* xref) 
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(launch_export_ref(h->sp, h->d, first, count, h->stream));
   std::vector<real> buf;
-  for (int r0 = first; r0 < first + count;) {
-    const int ko = h->lays[h->lid[r0]].ko[phase];
-    int r1 = r0 + 1;
-    while (r1 < first + count && h->lays[h->lid[r1]].ko[phase] == ko) ++r1;
-    if ((rc = copy_rows(h, h->d.out, KS, ko, N, r0, r1 - r0, buf))) return rc;
+  auto ko = [&](int b) { return h->lays[h->lid[b]].ko[phase]; };
+  return for_runs(first, count, ko, [&](int r0, int nb) -> int {
+    if (int rc = copy_rows(h, h->d.out, KS, ko(r0), N, r0, nb, buf)) return rc;
     double* o = xref + (size_t)(r0 - first) * N * n;
-    for (size_t i = 0; i < (size_t)(r1 - r0) * N; ++i)
+    for (size_t i = 0; i < (size_t)nb * N; ++i)
       for (int j = 0; j < n; ++j) o[i * n + j] = buf[i * KS + j];
-    r0 = r1;
-  }
-  return MHPC_OK;
+    return MHPC_OK;
+  });
 }
 
 int api_num_layouts(Handle* h, int* n) {
@@ -1934,260 +1835,108 @@ void api_destroy(Handle* h) {
   delete h;
 }
 
-#ifndef MHPC_FP32  // kernel-level parity hooks of the fp64 build (the fp32 build's: *_f32 below)
 // ---- batched model evaluation hooks ---------------------------------------------------------
-namespace {
-struct DevScratch {
-  std::vector<void*> ptrs;
-  ~DevScratch() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  double* put(const double* host, size_t n, hipError_t* e) {
-    void* p = nullptr;
-    if (*e == hipSuccess) *e = hipMalloc(&p, n * sizeof(double) + 8);
-    if (*e == hipSuccess) ptrs.push_back(p);
-    if (*e == hipSuccess && host) *e = hipMemcpy(p, host, n * sizeof(double), hipMemcpyHostToDevice);
-    return (double*)p;
-  }
-};
-}  // namespace
+// Kernel-level parity hooks of this build's arithmetic type: mhpc_eval_* in the fp64 build,
+// mhpc_eval_*_f32 in the fp32 one (the same signatures and output shapes; host arrays double,
+// converted to real on the way in and back on the way out).
+#ifdef MHPC_FP32
+#define HOOK(name) name##_f32
+#else
+#define HOOK(name) name
+#endif
+#define HOOK_STR2(x) #x
+#define HOOK_STR(x) HOOK_STR2(x)
+#define HOOK_NAME(name) HOOK_STR(HOOK(name))
+// the launch between the hook's inputs and its outputs' way back; fn: the exported name
+#define HOOK_RUN(t, fn, launch)                                \
+  do {                                                         \
+    if (t.e == hipSuccess) t.e = (launch);                     \
+    if (t.fetch() != hipSuccess) return dev_fail(fn, t.e);     \
+    return MHPC_OK;                                            \
+  } while (0)
 
-extern "C" int mhpc_eval_wb_dynamics(int device, int n, int mode, const double* x, const double* u,
-                                     double* xdot, double* y) {
-  if (n < 1 || !x || !u || !xdot || !y || mode < 1 || mode > 4)
-    return fail(MHPC_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(device));
-  DevScratch s;
-  hipError_t e = hipSuccess;
-  double *dx = s.put(x, n * 14, &e), *du = s.put(u, n * 4, &e);
-  double *dxd = s.put(nullptr, n * 14, &e), *dy = s.put(nullptr, n * 4, &e);
-  HIPCHK(e);
-  HIPCHK(launch_eval_wb_dyn(n, mode, dx, du, dxd, dy, nullptr));
-  HIPCHK(hipMemcpy(xdot, dxd, n * 14 * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(y, dy, n * 4 * sizeof(double), hipMemcpyDeviceToHost));
-  return MHPC_OK;
-}
-
-extern "C" int mhpc_eval_wb_dynamics_pair(int device, int n, int mode, const double* x,
-                                          const double* u, double* xdot, double* y) {
-  if (n < 1 || !x || !u || !xdot || !y || mode < 1 || mode > 4)
-    return fail(MHPC_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(device));
-  DevScratch s;
-  hipError_t e = hipSuccess;
-  double *dx = s.put(x, n * 14, &e), *du = s.put(u, n * 4, &e);
-  double *dxd = s.put(nullptr, n * 28, &e), *dy = s.put(nullptr, n * 8, &e);
-  HIPCHK(e);
-  HIPCHK(launch_eval_wb_dyn_pair(n, mode, dx, du, dxd, dy, nullptr));
-  HIPCHK(hipMemcpy(xdot, dxd, n * 28 * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(y, dy, n * 8 * sizeof(double), hipMemcpyDeviceToHost));
-  return MHPC_OK;
-}
-
-extern "C" int mhpc_eval_wb_touchdown(int device, int n, int foot, const double* x, double* h,
-                                      double* hx, double* hxx, double* J, double* Jd) {
-  if (n < 1 || !x || !h || !hx || !hxx || !J || !Jd || (foot != 0 && foot != 1))
-    return fail(MHPC_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(device));
-  DevScratch s;
-  hipError_t e = hipSuccess;
-  double *dx = s.put(x, n * 14, &e), *dh = s.put(nullptr, n * 2, &e);
-  double *dhx = s.put(nullptr, n * 14, &e), *dhxx = s.put(nullptr, n * 196, &e);
-  double *dJ = s.put(nullptr, n * 14, &e), *dJd = s.put(nullptr, n * 14, &e);
-  HIPCHK(e);
-  HIPCHK(launch_eval_wb_aux(n, foot, dx, dh, dhx, dhxx, dJ, dJd, nullptr));
-  HIPCHK(hipMemcpy(h, dh, n * 2 * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(hx, dhx, n * 14 * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(hxx, dhxx, n * 196 * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(J, dJ, n * 14 * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(Jd, dJd, n * 14 * sizeof(double), hipMemcpyDeviceToHost));
-  return MHPC_OK;
-}
-
-extern "C" int mhpc_eval_wb_partials(int device, int n, int mode, const double* x, const double* u,
-                                     double* Ac, double* Bc, double* C, double* D) {
-  if (n < 1 || !x || !u || !Ac || !Bc || !C || !D || mode < 1 || mode > 4)
-    return fail(MHPC_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(device));
-  DevScratch s;
-  hipError_t e = hipSuccess;
-  double *dx = s.put(x, n * 14, &e), *du = s.put(u, n * 4, &e);
-  double *dA = s.put(nullptr, n * 196, &e), *dB = s.put(nullptr, n * 56, &e);
-  double *dC = s.put(nullptr, n * 56, &e), *dD = s.put(nullptr, n * 16, &e);
-  HIPCHK(e);
-  HIPCHK(launch_eval_wb_par(n, mode, dx, du, dA, dB, dC, dD, nullptr));
-  HIPCHK(hipMemcpy(Ac, dA, n * 196 * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(Bc, dB, n * 56 * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(C, dC, n * 56 * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(D, dD, n * 16 * sizeof(double), hipMemcpyDeviceToHost));
-  return MHPC_OK;
-}
-
-extern "C" int mhpc_eval_wb_impact(int device, int n, int foot, const double* x, double* xplus,
-                                   double* Px) {
-  if (n < 1 || !x || !xplus || !Px || (foot != 0 && foot != 1))
-    return fail(MHPC_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(device));
-  DevScratch s;
-  hipError_t e = hipSuccess;
-  double *dx = s.put(x, n * 14, &e), *dxp = s.put(nullptr, n * 14, &e);
-  double* dP = s.put(nullptr, n * 196, &e);
-  HIPCHK(e);
-  HIPCHK(launch_eval_wb_impact(n, foot, dx, dxp, dP, nullptr));
-  HIPCHK(hipMemcpy(xplus, dxp, n * 14 * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(Px, dP, n * 196 * sizeof(double), hipMemcpyDeviceToHost));
-  return MHPC_OK;
-}
-
-extern "C" int mhpc_eval_srb(int device, int n, const double* x, const double* u,
-                             const double* foothold, const double* contact, double* xdot,
-                             double* Ac, double* Bc) {
-  if (n < 1 || !x || !u || !foothold || !contact || !xdot || !Ac || !Bc)
-    return fail(MHPC_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(device));
-  DevScratch s;
-  hipError_t e = hipSuccess;
-  double *dx = s.put(x, n * 6, &e), *du = s.put(u, n * 4, &e), *dp = s.put(foothold, n * 4, &e);
-  double *dc = s.put(contact, n * 2, &e), *dxd = s.put(nullptr, n * 6, &e);
-  double *dA = s.put(nullptr, n * 36, &e), *dB = s.put(nullptr, n * 24, &e);
-  HIPCHK(e);
-  HIPCHK(launch_eval_srb(n, dx, du, dp, dc, dxd, dA, dB, nullptr));
-  HIPCHK(hipMemcpy(xdot, dxd, n * 6 * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(Ac, dA, n * 36 * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(Bc, dB, n * 24 * sizeof(double), hipMemcpyDeviceToHost));
-  return MHPC_OK;
-}
-#else   // MHPC_FP32: the same hooks of the fp32 build (mhpc_eval_*_f32)
-// Whole-body dynamics of the fp32 instantiation, single-lane (pair = 0: xdot [n][14],
-// y [n][4]) or lane pair (pair = 1: xdot [n][2][14], y [n][2][4]); host arrays double.
-extern "C" int mhpc_eval_wb_dynamics_f32(int device, int n, int mode, int pair, const double* x,
-                                         const double* u, double* xdot, double* y) {
+// Whole-body dynamics, single-lane (pair = 0: xdot [n][14], y [n][4]) or lane pair (pair = 1:
+// xdot [n][2][14], y [n][2][4])
+static int eval_wb_dynamics(const char* fn, int device, int n, int mode, int pair, const double* x,
+                            const double* u, double* xdot, double* y) {
   if (n < 1 || !x || !u || !xdot || !y || mode < 1 || mode > 4 || (pair != 0 && pair != 1))
     return fail(MHPC_ERR_INVALID, "bad argument");
   HIPCHK(hipSetDevice(device));
-  const int L = pair ? 2 : 1;
-  std::vector<float> hx(x, x + (size_t)n * 14), hu(u, u + (size_t)n * 4);
-  std::vector<float> hxd((size_t)n * 14 * L), hy((size_t)n * 4 * L);
-  float *dx = nullptr, *du = nullptr, *dxd = nullptr, *dy = nullptr;
-  hipError_t e = hipMalloc((void**)&dx, hx.size() * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&du, hu.size() * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&dxd, hxd.size() * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&dy, hy.size() * 4);
-  if (e == hipSuccess) e = hipMemcpy(dx, hx.data(), hx.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(du, hu.data(), hu.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = pair ? launch_eval_wb_dyn_pair(n, mode, dx, du, dxd, dy, nullptr)
-             : launch_eval_wb_dyn(n, mode, dx, du, dxd, dy, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(hxd.data(), dxd, hxd.size() * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(hy.data(), dy, hy.size() * 4, hipMemcpyDeviceToHost);
-  for (float* p : {dx, du, dxd, dy})
-    if (p) (void)hipFree(p);
-  if (e != hipSuccess) return fail(MHPC_ERR_DEVICE, std::string("mhpc_eval_wb_dynamics_f32: ") + hipGetErrorString(e));
-  std::copy(hxd.begin(), hxd.end(), xdot);
-  std::copy(hy.begin(), hy.end(), y);
-  return MHPC_OK;
+  const size_t L = pair ? 2 : 1;
+  DevTemp<real> t;
+  real *dx = t.in(x, (size_t)n * 14), *du = t.in(u, (size_t)n * 4);
+  real *dxd = t.out(xdot, n * 14 * L), *dy = t.out(y, n * 4 * L);
+  HOOK_RUN(t, fn,
+           pair ? launch_eval_wb_dyn_pair(n, mode, dx, du, dxd, dy, nullptr)
+                : launch_eval_wb_dyn(n, mode, dx, du, dxd, dy, nullptr));
 }
-
-// The other model hooks of the fp32 instantiation: the fp64 hooks' signatures and output
-// shapes, host arrays double, converted to float on the way in and back on the way out.
-namespace {
-struct DevScratchF {
-  struct Out { float* dev; double* host; size_t n; };
-  std::vector<void*> ptrs;
-  std::vector<Out> outs;
-  hipError_t e = hipSuccess;
-  ~DevScratchF() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  float* alloc(size_t n) {
-    void* p = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&p, n * sizeof(float) + 8);
-    if (e == hipSuccess) ptrs.push_back(p);
-    return (float*)p;
-  }
-  float* in(const double* host, size_t n) {
-    float* p = alloc(n);
-    std::vector<float> h(host, host + n);
-    if (e == hipSuccess) e = hipMemcpy(p, h.data(), n * sizeof(float), hipMemcpyHostToDevice);
-    return p;
-  }
-  float* out(double* host, size_t n) {
-    float* p = alloc(n);
-    outs.push_back({p, host, n});
-    return p;
-  }
-  hipError_t fetch() {  // every out() array back to its host array
-    for (const Out& o : outs) {
-      std::vector<float> h(o.n);
-      if (e == hipSuccess) e = hipMemcpy(h.data(), o.dev, o.n * sizeof(float), hipMemcpyDeviceToHost);
-      if (e == hipSuccess) std::copy(h.begin(), h.end(), o.host);
-    }
-    return e;
-  }
-};
-}  // namespace
-
-extern "C" int mhpc_eval_wb_partials_f32(int device, int n, int mode, const double* x,
-                                         const double* u, double* Ac, double* Bc, double* C,
-                                         double* D) {
-  if (n < 1 || !x || !u || !Ac || !Bc || !C || !D || mode < 1 || mode > 4)
-    return fail(MHPC_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(device));
-  DevScratchF s;
-  float *dx = s.in(x, (size_t)n * 14), *du = s.in(u, (size_t)n * 4);
-  float *dA = s.out(Ac, (size_t)n * 196), *dB = s.out(Bc, (size_t)n * 56);
-  float *dC = s.out(C, (size_t)n * 56), *dD = s.out(D, (size_t)n * 16);
-  HIPCHK(s.e);
-  HIPCHK(launch_eval_wb_par(n, mode, dx, du, dA, dB, dC, dD, nullptr));
-  HIPCHK(s.fetch());
-  return MHPC_OK;
+#ifdef MHPC_FP32
+extern "C" int mhpc_eval_wb_dynamics_f32(int device, int n, int mode, int pair, const double* x,
+                                         const double* u, double* xdot, double* y) {
+  return eval_wb_dynamics("mhpc_eval_wb_dynamics_f32", device, n, mode, pair, x, u, xdot, y);
 }
-
-extern "C" int mhpc_eval_wb_impact_f32(int device, int n, int foot, const double* x,
-                                       double* xplus, double* Px) {
-  if (n < 1 || !x || !xplus || !Px || (foot != 0 && foot != 1))
-    return fail(MHPC_ERR_INVALID, "bad argument");
-  HIPCHK(hipSetDevice(device));
-  DevScratchF s;
-  float *dx = s.in(x, (size_t)n * 14), *dxp = s.out(xplus, (size_t)n * 14);
-  float* dP = s.out(Px, (size_t)n * 196);
-  HIPCHK(s.e);
-  HIPCHK(launch_eval_wb_impact(n, foot, dx, dxp, dP, nullptr));
-  HIPCHK(s.fetch());
-  return MHPC_OK;
+#else
+extern "C" int mhpc_eval_wb_dynamics(int device, int n, int mode, const double* x, const double* u,
+                                     double* xdot, double* y) {
+  return eval_wb_dynamics("mhpc_eval_wb_dynamics", device, n, mode, 0, x, u, xdot, y);
 }
+extern "C" int mhpc_eval_wb_dynamics_pair(int device, int n, int mode, const double* x,
+                                          const double* u, double* xdot, double* y) {
+  return eval_wb_dynamics("mhpc_eval_wb_dynamics_pair", device, n, mode, 1, x, u, xdot, y);
+}
+#endif
 
-extern "C" int mhpc_eval_wb_touchdown_f32(int device, int n, int foot, const double* x, double* h,
-                                          double* hx, double* hxx, double* J, double* Jd) {
+extern "C" int HOOK(mhpc_eval_wb_touchdown)(int device, int n, int foot, const double* x, double* h,
+                                            double* hx, double* hxx, double* J, double* Jd) {
   if (n < 1 || !x || !h || !hx || !hxx || !J || !Jd || (foot != 0 && foot != 1))
     return fail(MHPC_ERR_INVALID, "bad argument");
   HIPCHK(hipSetDevice(device));
-  DevScratchF s;
-  float *dx = s.in(x, (size_t)n * 14), *dh = s.out(h, (size_t)n * 2);
-  float *dhx = s.out(hx, (size_t)n * 14), *dhxx = s.out(hxx, (size_t)n * 196);
-  float *dJ = s.out(J, (size_t)n * 14), *dJd = s.out(Jd, (size_t)n * 14);
-  HIPCHK(s.e);
-  HIPCHK(launch_eval_wb_aux(n, foot, dx, dh, dhx, dhxx, dJ, dJd, nullptr));
-  HIPCHK(s.fetch());
-  return MHPC_OK;
+  const size_t m = n;
+  DevTemp<real> t;
+  real *dx = t.in(x, m * 14), *dh = t.out(h, m * 2), *dhx = t.out(hx, m * 14);
+  real *dhxx = t.out(hxx, m * 196), *dJ = t.out(J, m * 14), *dJd = t.out(Jd, m * 14);
+  HOOK_RUN(t, HOOK_NAME(mhpc_eval_wb_touchdown),
+           launch_eval_wb_aux(n, foot, dx, dh, dhx, dhxx, dJ, dJd, nullptr));
 }
 
-extern "C" int mhpc_eval_srb_f32(int device, int n, const double* x, const double* u,
-                                 const double* foothold, const double* contact, double* xdot,
-                                 double* Ac, double* Bc) {
+extern "C" int HOOK(mhpc_eval_wb_partials)(int device, int n, int mode, const double* x,
+                                           const double* u, double* Ac, double* Bc, double* C,
+                                           double* D) {
+  if (n < 1 || !x || !u || !Ac || !Bc || !C || !D || mode < 1 || mode > 4)
+    return fail(MHPC_ERR_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(device));
+  const size_t m = n;
+  DevTemp<real> t;
+  real *dx = t.in(x, m * 14), *du = t.in(u, m * 4), *dA = t.out(Ac, m * 196);
+  real *dB = t.out(Bc, m * 56), *dC = t.out(C, m * 56), *dD = t.out(D, m * 16);
+  HOOK_RUN(t, HOOK_NAME(mhpc_eval_wb_partials),
+           launch_eval_wb_par(n, mode, dx, du, dA, dB, dC, dD, nullptr));
+}
+
+extern "C" int HOOK(mhpc_eval_wb_impact)(int device, int n, int foot, const double* x,
+                                         double* xplus, double* Px) {
+  if (n < 1 || !x || !xplus || !Px || (foot != 0 && foot != 1))
+    return fail(MHPC_ERR_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(device));
+  const size_t m = n;
+  DevTemp<real> t;
+  real *dx = t.in(x, m * 14), *dxp = t.out(xplus, m * 14), *dP = t.out(Px, m * 196);
+  HOOK_RUN(t, HOOK_NAME(mhpc_eval_wb_impact),
+           launch_eval_wb_impact(n, foot, dx, dxp, dP, nullptr));
+}
+
+extern "C" int HOOK(mhpc_eval_srb)(int device, int n, const double* x, const double* u,
+                                   const double* foothold, const double* contact, double* xdot,
+                                   double* Ac, double* Bc) {
   if (n < 1 || !x || !u || !foothold || !contact || !xdot || !Ac || !Bc)
     return fail(MHPC_ERR_INVALID, "bad argument");
   HIPCHK(hipSetDevice(device));
-  DevScratchF s;
-  float *dx = s.in(x, (size_t)n * 6), *du = s.in(u, (size_t)n * 4);
-  float *dp = s.in(foothold, (size_t)n * 4), *dc = s.in(contact, (size_t)n * 2);
-  float *dxd = s.out(xdot, (size_t)n * 6), *dA = s.out(Ac, (size_t)n * 36);
-  float* dB = s.out(Bc, (size_t)n * 24);
-  HIPCHK(s.e);
-  HIPCHK(launch_eval_srb(n, dx, du, dp, dc, dxd, dA, dB, nullptr));
-  HIPCHK(s.fetch());
-  return MHPC_OK;
+  const size_t m = n;
+  DevTemp<real> t;
+  real *dx = t.in(x, m * 6), *du = t.in(u, m * 4), *dp = t.in(foothold, m * 4);
+  real *dc = t.in(contact, m * 2), *dxd = t.out(xdot, m * 6), *dA = t.out(Ac, m * 36);
+  real* dB = t.out(Bc, m * 24);
+  HOOK_RUN(t, HOOK_NAME(mhpc_eval_srb), launch_eval_srb(n, dx, du, dp, dc, dxd, dA, dB, nullptr));
 }
-#endif  // MHPC_FP32
 
 }  // namespace MHPC_NS

@@ -2,10 +2,16 @@
 must not change a single rounding).  Each build runs in its own process (MHPC_AMD_LIB):
 
   python tools/lib_bitwise.py dump <out.npz> <workload> <batch> [bws variant] [precision] [sweep bits]
+  python tools/lib_bitwise.py dump-api <out.npz>
   python tools/lib_bitwise.py cmp <a.npz> <b.npz>
 
 Dump: C3 / C5 initial states of configs.x0_for, one full solve (every variant choice left
-automatic unless given), all per-knot outputs and scalars.  Cmp: exact equality (+0 == -0)."""
+automatic unless given), all per-knot outputs and scalars.
+Dump-api: every output of the entry points that stage caller arrays through per-call device
+temporaries -- the rollouts, advance_x0 / get_x0, the ranged cost gradients and references,
+and every model hook of both precisions -- at the smallest shapes that exercise their host
+logic (api_cases).
+Cmp: exact equality (+0 == -0) of every array of the two files."""
 import os
 import sys
 
@@ -37,10 +43,124 @@ def dump(out, workload, batch, bws="auto", precision=64, sweep_bits=0):
     np.savez(out, **{k: np.asarray(res[k]) for k in KEYS})
 
 
+def _hooks(res, n):
+    """Every model hook of both precisions at n points."""
+    from mhpc_minimal_env_amd import capi, locomotion as L
+    lib, d = capi.lib(), capi.dptr
+    rng = np.random.default_rng(n)
+    x = np.ascontiguousarray(L.random_x0(n))
+    u = 5.0 * rng.standard_normal((n, 4))
+    sx = np.ascontiguousarray(x[:, L.STATE_PROJ_ROWS])
+    sp = 0.2 * rng.standard_normal((n, 4))
+    ss = np.ascontiguousarray(rng.integers(0, 2, (n, 2)).astype(np.float64))
+
+    def run(key, fn, args, shapes):
+        outs = [np.full((n,) + s, np.nan) for s in shapes]
+        capi.check(fn(0, n, *args, *[d(o) for o in outs]), key)
+        for i, o in enumerate(outs):
+            res[f"hook{n}.{key}.{i}"] = o
+
+    for sfx in ("", "_f32"):
+        f = lambda name: getattr(lib, name + sfx)
+        for mode in (1, 2, 3, 4):
+            if sfx:
+                for pair in (0, 1):
+                    run(f"dyn_f32.{mode}.{pair}", lib.mhpc_eval_wb_dynamics_f32,
+                        (mode, pair, d(x), d(u)), [(1 + pair, 14), (1 + pair, 4)])
+            else:
+                run(f"dyn.{mode}", lib.mhpc_eval_wb_dynamics, (mode, d(x), d(u)), [(14,), (4,)])
+                run(f"dyn_pair.{mode}", lib.mhpc_eval_wb_dynamics_pair, (mode, d(x), d(u)),
+                    [(2, 14), (2, 4)])
+            run(f"par{sfx}.{mode}", f("mhpc_eval_wb_partials"), (mode, d(x), d(u)),
+                [(14, 14), (14, 4), (4, 14), (4, 4)])
+        for foot in (0, 1):
+            run(f"imp{sfx}.{foot}", f("mhpc_eval_wb_impact"), (foot, d(x)), [(14,), (14, 14)])
+            run(f"td{sfx}.{foot}", f("mhpc_eval_wb_touchdown"), (foot, d(x)),
+                [(2,), (14,), (14, 14), (2, 7), (2, 7)])
+        run(f"srb{sfx}", f("mhpc_eval_srb"), (d(sx), d(u), d(sp), d(ss)), [(6,), (6, 6), (6, 4)])
+
+
+def _handle_case(res, tag, descs, lop, n_samples=3, n_eps=2):
+    """One solved handle (problem b of layout descs[lop[b]]) through the staged entry points:
+    the ranged calls over problems [1, B) (all of them when B = 2: [1, 2))."""
+    import ctypes
+    from mhpc_minimal_env_amd import capi, configs, locomotion as L
+    lib, d = capi.lib(), capi.dptr
+    B = len(lop)
+    loco = L.MHPCLocomotion(desc=descs[0], option=L.HSDDP_OPTION(), batch=B, device=0)
+    try:
+        if len(descs) > 1:
+            loco.set_layouts(descs, np.asarray(lop, dtype=np.int32))
+        x0 = configs.x0_for(descs[0], B)
+        r = x0.shape[1]
+        loco.set_initial_condition(x0)
+        loco.initialization()
+        res[f"{tag}.status"] = loco.solve_mhpc().copy()
+        ro = loco.rollout_costs([1.0, 0.25][:n_eps])
+        res[f"{tag}.costs.J"], res[f"{tag}.costs.viol"] = ro["J"], ro["viol"]
+        rng = np.random.default_rng(B)
+        xs = np.ascontiguousarray(x0[:, None, :] + 1e-2 * rng.uniform(-1, 1, (B, n_samples, r)))
+        for n_phases in (0, 1):
+            ro = loco.rollout_policy(xs, n_phases)
+            for k in ("J", "viol", "x_end"):
+                res[f"{tag}.policy{n_phases}.{k}"] = ro[k]
+        J = np.full((B, n_samples), np.nan)  # without viol and x_end
+        capi.check(lib.mhpc_rollout_policy(loco._h, n_samples, d(xs), 0, d(J), None, None, None),
+                   "mhpc_rollout_policy")
+        res[f"{tag}.policy_J_only"] = J
+        first, count = 1, B - 1
+        own = [descs[l] for l in lop[first:]]
+        for p in range(descs[0].n_wb + descs[0].n_fb):
+            if len({(q.N[p], q.xsize(p)) for q in own}) > 1:
+                continue  # the ranged calls need one phase shape over the range
+            ro = loco.rollout_policy_phase(p, first, count, xs[first:first + count])
+            for k in ("x", "u", "y"):
+                res[f"{tag}.policy_phase{p}.{k}"] = ro[k]
+            n, N = own[0].xsize(p), own[0].N[p]
+            lx, phix = np.full((count, N - 1, n), np.nan), np.full((count, n), np.nan)
+            capi.check(lib.mhpc_get_cost_gradients_problems(loco._h, p, first, count, d(lx), d(phix)),
+                       "mhpc_get_cost_gradients_problems")
+            res[f"{tag}.lx{p}"], res[f"{tag}.Phix{p}"] = lx, phix
+            res[f"{tag}.xref{p}"] = loco.get_reference_problems(p, first, count)
+        loco.advance_x0(1, None)
+        res[f"{tag}.x0_advanced"] = loco.get_x0()
+        loco.advance_x0(1, 1e-3 * rng.uniform(-1, 1, (B, r)))
+        res[f"{tag}.x0_advanced_dx"] = loco.get_x0()
+    finally:
+        loco.close()
+
+
+def api_cases():
+    """(tag, layouts, layout of each problem) of dump-api's handles: C3 at batch 5 over two
+    points of its gait cycle (two groups: the ranged calls cross both boundaries) and over two
+    layouts whose phases 1.. start at different knots (a shorter phase 0); C1 (SRB only: rows
+    of 6) at batch 2; C3 in fp32 at batch 2."""
+    from mhpc_minimal_env_amd import configs, locomotion as L
+    c3 = configs.c3_desc()
+    short = L.make_problem_desc(2, 2, list(c3.mode_seq[:4]), [0.0] * 4, c3.dt_wb, c3.dt_fb, 1.5,
+                                N=[60] + list(c3.N[1:4]))
+    c3f = configs.c3_desc()
+    c3f.precision = 32
+    return [("c3", [configs.c3_at(1), configs.c3_at(2)], [0, 1, 1, 0, 0]),
+            ("c3ko", [short, c3], [0, 0, 1, 1, 0]),
+            ("c1", [configs.c1_desc()], [0, 0]),
+            ("c3f32", [c3f], [0, 0])]
+
+
+def dump_api(out):
+    res = {}
+    for n in (1, 5):
+        _hooks(res, n)
+    for tag, descs, lop in api_cases():
+        _handle_case(res, tag, descs, lop)
+    np.savez(out, **res)
+    print(f"{out}: {len(res)} arrays")
+
+
 def cmp(a, b):
     A, B = np.load(a), np.load(b)
-    bad = []
-    for k in KEYS:
+    bad = [f"{k}: in one file only" for k in sorted(set(A.files) ^ set(B.files))]
+    for k in sorted(set(A.files) & set(B.files)):
         x, y = A[k], B[k]
         if x.shape != y.shape:
             bad.append(f"{k}: shape {x.shape} vs {y.shape}")
@@ -61,7 +181,9 @@ def cmp(a, b):
 
 
 if __name__ == "__main__":
-    if sys.argv[1] == "dump":
+    if sys.argv[1] == "dump-api":
+        dump_api(sys.argv[2])
+    elif sys.argv[1] == "dump":
         dump(sys.argv[2], sys.argv[3], int(sys.argv[4]), *(sys.argv[5:]))
     else:
         sys.exit(0 if cmp(sys.argv[2], sys.argv[3]) else 1)
