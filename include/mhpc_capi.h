@@ -34,6 +34,8 @@
  *   mhpc_set_layouts     one MHPCLocomotion per controller, each built from its own Gait
  *                        (MHPCLocomotion.cpp:63-104): per-problem phase layouts in one batch
  *   mhpc_update_problems update_problem of every controller with its own gait and step count
+ *   mhpc_reset_problems  set_initial_condition + initialization() of single controllers of the
+ *                        fleet (MHPCLocomotion.cpp:47-53): the listed problems only
  *   mhpc_set_commands    MHPCUserParameters::usrcmd of every controller (vel, height), which
  *                        build_problem / update_problem hand to ReferenceGen
  *                        (MHPCLocomotion.cpp:98-103): per-problem user commands in one batch;
@@ -206,6 +208,37 @@ int mhpc_get_problem_desc(mhpc_handle* h, int problem, mhpc_problem_desc* desc);
  * mhpc_update_problem).  n_gaits in 1..MHPC_MAX_LAYOUTS. */
 int mhpc_update_problems(mhpc_handle* h, int n_gaits, const mhpc_gait* gaits,
                          const int32_t* gait_of_problem, const int32_t* steps);
+/* ---- per-problem re-initialisation: restart lost problems inside a live batch -----------
+ * MHPCLocomotion::initialization() (MHPCLocomotion.cpp:47-53: memory_reset, build_problem,
+ * ReferenceGen::generate_ref, warmstart) for the n listed problems only: a fleet restarts one
+ * controller with set_initial_condition + initialization() on that object, and the others
+ * never notice.  problems: n distinct problem numbers, 1 <= n <= batch.  x0: [n][r] rows in
+ * list order (r as in mhpc_set_x0); NULL keeps each listed problem's current device row (a
+ * fresh warm start from where the robot is).  descs == NULL (n_desc == 0): each listed problem
+ * keeps its current descriptor, its phase buffers go back to identity and its gait to the
+ * descriptor's first mode, as mhpc_initialize does.  descs != NULL: listed problem i gets
+ * descs[desc_of ? desc_of[i] : i % n_desc] (mhpc_set_layouts' checks; the handle's x0 row width
+ * must not change).
+ *  - A listed problem comes out as mhpc_initialize leaves a problem: x0 row, position
+ *    references, solver state (status, trace, counters, the option values a solve rewrites),
+ *    the AL / ReB initial values of its own parameter set, the PD warm start, zero K / du / G,
+ *    zero phase buffers.  Its command and parameter set belong to the problem number and stay.
+ *  - Every other problem's device state stays bit for bit.  So a reset never changes the knot
+ *    stride and never reallocates: MHPC_ERR_INVALID, before anything changes, for a descriptor
+ *    with more knots than the current stride, or -- once the phase-buffer store exists (after the
+ *    first mhpc_update_problem[s]) -- more phases or a longer phase than the store holds; also for
+ *    duplicate or out-of-range problem numbers and for more than MHPC_MAX_LAYOUTS groups.  The
+ *    stride stays even when the longest problem leaves its layout (a later
+ *    mhpc_update_problem[s] may shrink it).
+ *  - MHPC_ERR_STATE before mhpc_initialize.  The call-order state of the handle (solved, pending
+ *    x0 / commands / parameters) stays as it is.  Both orders work: mhpc_solve ->
+ *    mhpc_reset_problems -> mhpc_update_problems with steps[b] = 0 for the reset problems ->
+ *    mhpc_solve; and mhpc_initialize / mhpc_update_problem[s] -> mhpc_reset_problems -> mhpc_solve.
+ *    Either way the reset problems' next solve is the one of a freshly initialised handle, bit for
+ *    bit (tests/test_gpu_reset.py).
+ *  - Device work is proportional to n, not to the batch. */
+int mhpc_reset_problems(mhpc_handle* h, int n, const int32_t* problems, const double* x0,
+                        int n_desc, const mhpc_problem_desc* descs, const int32_t* desc_of);
 /* ---- per-problem user commands: the batch axis over speed / height commands -----------
  * Per-problem user command (the reference's MHPCUserParameters::usrcmd of each controller,
  * MHPCLocomotion.cpp:98-103).  vel, height: host arrays [batch]; either may be NULL = unchanged.

@@ -309,6 +309,33 @@ class MHPCLocomotion {
           "mhpc_update_problems");
     refresh_descs();
   }
+  // extension: initialization() of the listed problems only -- set_initial_condition +
+  // initialization() on one controller of a fleet (MHPCLocomotion.cpp:47-53), the others keep
+  // their warm start bit for bit.  x0 [problems.size()][x0_width()] in list order, empty: each
+  // listed problem keeps its current device row.  After a solve, follow with update_problems
+  // (steps 0 for the reset problems); before a solve, just solve.
+  void reset_problems(const std::vector<int>& problems, const std::vector<double>& x0 = {}) {
+    if (!x0.empty() && x0.size() != problems.size() * (size_t)xw_)
+      throw std::runtime_error("reset_problems: x0 must be [problems][x0_width()]");
+    const std::vector<int32_t> pr(problems.begin(), problems.end());
+    check(mhpc_reset_problems(h_, (int)pr.size(), pr.data(), x0.empty() ? nullptr : x0.data(), 0,
+                              nullptr, nullptr),
+          "mhpc_reset_problems");
+    for (size_t i = 0; i < pr.size() && !x0.empty(); ++i)  // what update_problem(s) hands back
+      std::copy(x0.begin() + i * xw_, x0.begin() + (i + 1) * xw_, x0_.begin() + (size_t)pr[i] * xw_);
+    refresh_descs();
+  }
+  // problems whose last solve did not end MHPC_SOLVE_OK or left a non-finite cost
+  std::vector<int> lost_problems() {
+    std::vector<double> J(batch_);
+    check(mhpc_get_scalars(h_, J.data(), nullptr, nullptr, nullptr, nullptr, nullptr),
+          "mhpc_get_scalars");
+    std::vector<int> lost;
+    for (int b = 0; b < batch_; ++b)
+      if ((b < (int)status_.size() && status_[b] != MHPC_SOLVE_OK) || !std::isfinite(J[b]))
+        lost.push_back(b);
+    return lost;
+  }
   // extension: per-problem user commands in one batch -- the usrcmd (float vel, height) of one
   // controller per problem, which build_problem hands to ReferenceGen (MHPCLocomotion.cpp
   // :98-103).  One entry per problem, an empty vector keeps the current values; they take

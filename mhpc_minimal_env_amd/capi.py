@@ -24,6 +24,8 @@ MHPC_MAX_POLICY_SAMPLES = 4096
 
 MHPC_OK = 0
 MHPC_ERR_INVALID = 1
+MHPC_ERR_DEVICE = 2
+MHPC_ERR_STATE = 3
 
 # mhpc_set_kernel_variant (include/mhpc_capi.h)
 MHPC_VARIANT_BWS = 0
@@ -202,6 +204,8 @@ SIGNATURES = [
                                         _IP]),
     ("mhpc_get_problem_desc", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int,
                                              ctypes.POINTER(ProblemDesc)]),
+    ("mhpc_reset_problems", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _IP, _DP, ctypes.c_int,
+                                           ctypes.POINTER(ProblemDesc), _IP]),
     ("mhpc_set_commands", ctypes.c_int, [ctypes.c_void_p, _DP, _DP]),
     ("mhpc_get_commands", ctypes.c_int, [ctypes.c_void_p, _DP, _DP]),
     ("mhpc_get_reference_problems", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,

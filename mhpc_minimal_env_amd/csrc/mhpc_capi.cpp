@@ -160,6 +160,11 @@ extern "C" int mhpc_set_layouts(mhpc_handle* h, int n_desc, const mhpc_problem_d
                                 const int32_t* layout_of_problem) {
   FWD(set_layouts, n_desc, descs, layout_of_problem);
 }
+extern "C" int mhpc_reset_problems(mhpc_handle* h, int n, const int32_t* problems, const double* x0,
+                                   int n_desc, const mhpc_problem_desc* descs,
+                                   const int32_t* desc_of) {
+  FWD(reset_problems, n, problems, x0, n_desc, descs, desc_of);
+}
 extern "C" int mhpc_get_problem_desc(mhpc_handle* h, int problem, mhpc_problem_desc* desc) {
   FWD(get_problem_desc, problem, desc);
 }

@@ -1519,6 +1519,49 @@ __global__ __launch_bounds__(256) void k_reset_arrays(SolveParams sp, DevBufs d)
   init_reset_arrays(sp, d, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256);
 }
 
+// ---- per-problem re-initialisation (mhpc_reset_problems): list-driven, work ~ n not B ----------
+// The padded x0 rows [n][14] of the listed problems to their device rows.
+__global__ __launch_bounds__(64) void k_scatter_x0(DevBufs d, int n, const int* list,
+                                                   const real* rows) {
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= n * 14) return;
+  d.x0[(size_t)list[t / 14] * 14 + t % 14] = rows[t];
+}
+
+// memory_reset of the listed problems: what k_reset_arrays does for the batch (K, du, G over the
+// whole knot stride; u, y of every phase's last knot in every slot, by the problem's current
+// layout) and, when the phase-buffer store exists, their store rows (ensure_store's memset for
+// one problem).  A block per (listed problem, chunk of RL_CH items): item t is knot t of the
+// stride and record t of the problem's spmax * nbk store records (spmax = 0 without a store;
+// nch = chunks per problem over the longer of the two).  A chunk's K, du, G and store records are
+// contiguous, so the block's lanes stride over their elements (whole lines per wave).
+constexpr int RL_CH = 64;
+__global__ __launch_bounds__(256) void k_reset_list(SolveParams sp, DevBufs d, const int* list,
+                                                    int nch, real* store, int nbk, int spmax) {
+  const int b = list[blockIdx.x / nch], i0 = (int)(blockIdx.x % nch) * RL_CH, t = threadIdx.x;
+  const int k1 = min(i0 + RL_CH, sp.NK);
+  if (i0 < k1) {
+    const size_t r0 = (size_t)b * sp.NK + i0;
+    const int nk = k1 - i0;
+    for (int e = t; e < nk * 56; e += 256) d.K[r0 * 56 + e] = real(0.0);
+    for (int e = t; e < nk * 4; e += 256) d.du[r0 * 4 + e] = real(0.0);
+    for (int e = t; e < nk * 14; e += 256) d.G[r0 * 14 + e] = real(0.0);
+    const Layout& L = d.grp[d.lid[b]].lay;
+    for (int e = t; e < L.P * sp.nslot; e += 256) {  // a lane per (phase, slot) tail
+      const int p = e / sp.nslot, slot = e % sp.nslot;
+      const int kk = L.ko[p] + L.N[p] - 1;
+      if (kk < i0 || kk >= k1) continue;
+      real* r = traj_ptr(sp, d, b, slot, kk);
+      for (int q = p < L.n_wb ? 14 : 6; q < KS; ++q) r[q] = real(0.0);
+    }
+  }
+  const int s1 = min(i0 + RL_CH, spmax * nbk);
+  if (i0 < s1) {
+    real* o = store + ((size_t)b * spmax * nbk + i0) * SREC;
+    for (int e = t; e < (s1 - i0) * SREC; e += 256) o[e] = real(0.0);
+  }
+}
+
 // The AL / ReB initial values of every problem from its group's parameter record, after k_init
 // (which wrote problem 0's set for all): launched only when the handle holds more than one set
 // (mhpc_set_param_sets).  k_init keeps its own read of the parameter block, SolveParams::cw:
@@ -1941,6 +1984,21 @@ hipError_t launch_reset_arrays(const SolveParams& sp, const DevBufs& d, hipStrea
   const long e = (long)sp.B * sp.NK * 74 + (long)sp.B * sp.nslot * sp.pmax;
   const long nb = std::min((e + 256 * 64 - 1) / (256 * 64), 2L * sp.ncu);
   hipLaunchKernelGGL(k_reset_arrays, dim3((unsigned)nb), dim3(256), 0, s, sp, d);
+  return hipGetLastError();
+}
+hipError_t launch_scatter_x0(const DevBufs& d, int n, const int* list, const real* rows,
+                             hipStream_t s) {
+  hipLaunchKernelGGL(k_scatter_x0, dim3((unsigned)((n * 14L + 63) / 64)), dim3(64), 0, s, d, n, list,
+                     rows);
+  return hipGetLastError();
+}
+// store == nullptr: no phase-buffer store yet (nbk, spmax ignored)
+hipError_t launch_reset_list(const SolveParams& sp, const DevBufs& d, int n, const int* list,
+                             real* store, int nbk, int spmax, hipStream_t s) {
+  if (!store) nbk = spmax = 0;
+  const int nch = (std::max(sp.NK, spmax * nbk) + RL_CH - 1) / RL_CH;
+  hipLaunchKernelGGL(k_reset_list, dim3((unsigned)n * nch), dim3(256), 0, s, sp, d, list, nch, store,
+                     nbk, spmax);
   return hipGetLastError();
 }
 hipError_t launch_init_params(const SolveParams& sp, const DevBufs& d, hipStream_t s) {

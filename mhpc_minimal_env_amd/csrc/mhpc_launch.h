@@ -14,6 +14,12 @@ hipError_t launch_init(const SolveParams& sp, const DevBufs& d, hipStream_t s);
 hipError_t launch_init_params(const SolveParams& sp, const DevBufs& d, hipStream_t s);
 hipError_t launch_reset(const SolveParams& sp, const DevBufs& d, hipStream_t s);
 hipError_t launch_reset_arrays(const SolveParams& sp, const DevBufs& d, hipStream_t s);
+// list-driven device code of mhpc_reset_problems: x0 rows [n][14] to the listed problems, and
+// their memory_reset (K / du / G, last-knot tails, store rows when store != nullptr)
+hipError_t launch_scatter_x0(const DevBufs& d, int n, const int* list, const real* rows,
+                             hipStream_t s);
+hipError_t launch_reset_list(const SolveParams& sp, const DevBufs& d, int n, const int* list,
+                             real* store, int nbk, int spmax, hipStream_t s);
 hipError_t launch_cost(const SolveParams& sp, const DevBufs& d, int al_iter, hipStream_t s);
 hipError_t launch_rollout(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter,
                           int max_ddp, int full, hipStream_t s);

@@ -118,6 +118,14 @@ struct Handle {
   int nbk = 0, nk_cap = 0, spmax = 0;
   bool need_full = false;
   bool store_valid = false;  // store zeroed since the last initialize (memory_reset)
+  // problems whose nominal k_init wrote since the last solve (mhpc_reset_problems) and no gait
+  // step rotated: in a solve that starts with the real rollout (need_full) their first
+  // forward_sweep(0) is still the cost evaluation, as after mhpc_initialize -- the fp32 k_init
+  // rounds its warm start its own way, so only k_cost continues it bit for bit.  dsplit [B]:
+  // the grouped order split for that op, the others first, then the fresh ones.
+  std::vector<char> fresh;
+  int nfresh = 0;
+  int* dsplit = nullptr;
   // sub-batches (MHPC_VARIANT_SUBBATCH): the solve schedule runs once per contiguous block of
   // problems, each block on its own stream pair; created on first use
   int nsub_req = 0;
@@ -335,8 +343,11 @@ static int upload_params(Handle* h) {
 // share is stored once per group, so lays[lid[b]] stays problem b's layout) and its parameter
 // record.  Uploads the group table and the grouped order, sets the launch fields of sp, grows the
 // packed arrays if a layout needs it.  A call that would need more than MAXL groups fails
-// before it changes anything.
-static int rebuild_groups(Handle* h) {
+// before it changes anything.  keep_stride (mhpc_reset_problems, whose caller checked that every
+// layout fits, and the parameter-set calls, which change no layout): the knot stride stays what
+// it is even if the longest layout left, so no array is re-strided, re-zeroed or reallocated and
+// the problems' records stay where they are.
+static int rebuild_groups(Handle* h, bool keep_stride = false) {
   SolveParams& sp = h->sp;
   const int B = sp.B;
   std::map<std::string, int> seen;
@@ -412,9 +423,11 @@ static int rebuild_groups(Handle* h) {
     if (pos != b) sp.ident = 0;
   }
   sp.pmax = pmax;
-  int rc = ensure_knot_arrays(h, NK);
-  if (rc) return rc;
-  sp.NK = NK;
+  if (!keep_stride) {
+    int rc = ensure_knot_arrays(h, NK);
+    if (rc) return rc;
+    sp.NK = NK;
+  }
   h->d.grp = h->dgrp;
   h->d.gidx = h->dgidx;
   h->d.lid = h->dlid;
@@ -543,11 +556,12 @@ static int apply_sets(Handle* h, std::vector<CostParams>& ns) {
   merge_sets(ns, nof);
   h->psets.swap(ns);
   h->pset_of.swap(nof);
-  const int rc = h->psets.size() != n ? rebuild_groups(h) : upload_params(h);
+  // (no layout changes here: the knot stride stays, also one a reset left above the longest layout)
+  const int rc = h->psets.size() != n ? rebuild_groups(h, true) : upload_params(h);
   if (rc) {
     h->psets.swap(ns);
     h->pset_of.swap(nof);
-    (void)rebuild_groups(h);
+    (void)rebuild_groups(h, true);
   }
   return rc;
 }
@@ -614,10 +628,11 @@ int api_set_param_sets(Handle* h, int n_sets, const mhpc_cost_weights* w,
   HIPCHK(hipStreamSynchronize(h->stream));
   h->psets.swap(ns);
   h->pset_of.swap(nof);
-  if ((rc = rebuild_groups(h))) {  // too many (layout, set) pairs: keep the old sets
+  // (the knot stride stays as in apply_sets: the records of an initialised handle are live)
+  if ((rc = rebuild_groups(h, true))) {  // too many (layout, set) pairs: keep the old sets
     h->psets.swap(ns);
     h->pset_of.swap(nof);
-    (void)rebuild_groups(h);
+    (void)rebuild_groups(h, true);
     return rc;
   }
   if (h->initialized) h->params_changed = h->sets_changed = true;
@@ -694,6 +709,7 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
     h->pset_of.assign(batch, 0);
   }
   h->pl.assign(batch, ProbLayout{h->desc, 0, 0});
+  h->fresh.assign(batch, 0);
   h->cmode.assign(batch, desc->mode_seq[0]);
 
   DevBufs& d = h->d;
@@ -711,6 +727,7 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
   alloc((void**)&h->dgrp, MAXL * sizeof(Group));
   alloc((void**)&h->dgidx, B * sizeof(int));
   alloc((void**)&h->dlid, B * sizeof(int));
+  alloc((void**)&h->dsplit, B * sizeof(int));
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->evfork, hipEventDisableTiming);
@@ -866,6 +883,8 @@ static int initialize_async(Handle* h) {
   // pays nothing for it
   h->store_valid = false;
   h->need_full = false;
+  std::fill(h->fresh.begin(), h->fresh.end(), 0);
+  h->nfresh = 0;
   return MHPC_OK;
 }
 
@@ -908,7 +927,23 @@ struct SolveBlock {
   DevBufs d;
   hipStream_t s1, s2, s3;
   hipEvent_t fork, join, pfork, pjoin;
+  // OP_FULL with fresh problems in the batch (Handle::fresh): the block's problems split into
+  // the rolled-out ones (spf) and the fresh ones (spc, k_cost), both over Handle::dsplit
+  bool mixed = false;
+  SolveParams spf, spc;
 };
+// The block's two halves for a mixed OP_FULL: nf[pos] = problems before gidx position pos that
+// are not fresh, nnf their total (dsplit: those first, then the fresh ones, each in gidx order,
+// so a contiguous range of positions stays contiguous and grouped in both halves).
+static void split_block(SolveBlock& k, const std::vector<int>& nf, int nnf) {
+  k.mixed = true;
+  k.spf = k.spc = k.sp;
+  k.spf.ident = k.spc.ident = 0;
+  for (int g = 0; g <= k.sp.ngrp; ++g) {
+    k.spf.go[g] = nf[k.sp.go[g]];
+    k.spc.go[g] = nnf + k.sp.go[g] - nf[k.sp.go[g]];
+  }
+}
 
 // Problems [b0, b0 + sp.B) of the handle's arrays as the kernels index them (b * per-problem
 // stride, with sp.NK the knot stride of the packed arrays): for the layout-free export kernel.
@@ -964,6 +999,15 @@ static int issue_op(Handle* h, const SolveBlock& k, const SolveOp& op) {
 #endif
   switch (op.kind) {
     case OP_FULL:
+      if (k.mixed) {
+        DevBufs ds = d;
+        ds.gidx = h->dsplit;
+        if (launch_problems(k.spf) > 0)
+          LAUNCH_ON(h, K_FULL, k.s1, launch_rollout(k.spf, ds, op.al, 0, 0, 1, k.s1));
+        if (launch_problems(k.spc) > 0)
+          LAUNCH_ON(h, K_FULL, k.s1, launch_cost(k.spc, ds, op.al, k.s1));
+        break;
+      }
       LAUNCH_ON(h, K_FULL, k.s1, launch_rollout(sp, d, op.al, 0, 0, 1, k.s1));
       break;
     case OP_COST:
@@ -1028,9 +1072,30 @@ static int solve_async(Handle* h) {
   const int nops = (int)ops.size();
   const int nsub = sub_batches(h);
   int rc;
+  // fresh problems in a solve that starts with the real rollout: the split order to the device
+  const bool mixed = h->need_full && h->nfresh > 0;
+  std::vector<int> nf;
+  int nnf = 0;
+  if (mixed) {
+    const int B = h->sp.B;
+    nf.resize(B + 1);
+    for (int pos = 0; pos < B; ++pos) {
+      nf[pos] = nnf;
+      nnf += !h->fresh[h->gidx[pos]];
+    }
+    nf[B] = nnf;
+    std::vector<int> split(B);
+    for (int pos = 0; pos < B; ++pos) {
+      const bool f = h->fresh[h->gidx[pos]];
+      split[f ? nnf + pos - nf[pos] : nf[pos]] = h->gidx[pos];
+    }
+    HIPCHK(hipMemcpyAsync(h->dsplit, split.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
   if (nsub <= 1) {
-    const SolveBlock k{h->sp,       h->d,      h->stream,  h->stream2, h->stream3,
-                       h->evfork,   h->evjoin, h->evpfork, h->evpjoin};
+    SolveBlock k{h->sp,       h->d,      h->stream,  h->stream2, h->stream3,
+                 h->evfork,   h->evjoin, h->evpfork, h->evpjoin};
+    if (mixed) split_block(k, nf, nnf);
     for (const SolveOp& op : ops)
       if ((rc = issue_op(h, k, op))) {
         // an issue failure may leave launches queued on the second / third stream (the
@@ -1066,6 +1131,7 @@ static int solve_async(Handle* h) {
       k.s3 = ss.s3;
       k.pfork = ss.pfork;
       k.pjoin = ss.pjoin;
+      if (mixed) split_block(k, nf, nnf);
       HIPCHK(hipStreamWaitEvent(k.s1, h->evstart, 0));
     }
     // block s runs `lag` launches behind block s - 1 (its first launch waits on the gate
@@ -1140,6 +1206,8 @@ int api_solve(Handle* h, int32_t* status) {
   HIPCHK(hipEventElapsedTime(&h->solve_ms, h->ev0, h->ev1));
   h->solved = true;
   h->need_full = false;
+  std::fill(h->fresh.begin(), h->fresh.end(), 0);
+  h->nfresh = 0;
   rc = collect_profile(h);
   if (rc) return rc;
   const unsigned long long* c = h->cnt;
@@ -1579,6 +1647,11 @@ int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const in
     return rc;
   }
   h->cmode = ncm;
+  for (int b = 0; b < B; ++b)  // a gait step rotates the nominal: no longer k_init's
+    if (h->fresh[b] && (steps ? steps[b] : 1) > 0) {
+      h->fresh[b] = 0;
+      --h->nfresh;
+    }
   HIPCHK(launch_reset(h->sp, h->d, h->stream));  // refs from x0, AL/ReB init, nom_slot = 0
   if (h->psets.size() > 1) HIPCHK(launch_init_params(h->sp, h->d, h->stream));
   HIPCHK(launch_store(h->sp, h->d, h->store, h->nbk, h->spmax, 0, h->stream));
@@ -1631,6 +1704,132 @@ int api_set_layouts(Handle* h, int n_desc, const mhpc_problem_desc* descs, const
   h->solved = false;
   h->x0_set = false;  // the x0 row length may have changed
   return MHPC_OK;
+}
+
+// The device half of mhpc_reset_problems: `order` is the listed problems by group (then problem
+// number), rows their padded x0 rows in that order (empty: the device rows stay).  The list-driven
+// memory_reset runs on the second stream beside the warm start, as in initialize_async; k_init
+// and k_init_params are the batch's own kernels over a restricted SolveParams (go[] over the
+// list, gidx = the list).  Every launch counts as k_init under profiling.
+static int reset_launches(Handle* h, const std::vector<int>& order, std::vector<real>&& rows) {
+  const int n = (int)order.size();
+  SolveParams rs = h->sp;
+  rs.ident = 0;
+  for (int g = 0; g <= rs.ngrp; ++g) rs.go[g] = 0;
+  for (int b : order) ++rs.go[h->lid[b] + 1];
+  for (int g = 0; g < rs.ngrp; ++g) rs.go[g + 1] += rs.go[g];
+  DevTemp<int> ti(h->stream);
+  DevTemp<real> tr(h->stream);
+  const int* dlist = ti.in(std::vector<int>(order));
+  const real* drows = rows.empty() ? nullptr : tr.in(std::move(rows));
+  if (ti.e != hipSuccess) return dev_fail("mhpc_reset_problems", ti.e);
+  if (tr.e != hipSuccess) return dev_fail("mhpc_reset_problems", tr.e);
+  DevBufs rd = h->d;
+  rd.gidx = dlist;
+  HIPCHK(hipEventRecord(h->evfork, h->stream));
+  HIPCHK(hipStreamWaitEvent(h->stream2, h->evfork, 0));
+  LAUNCH_ON(h, K_INIT, h->stream2,
+            launch_reset_list(h->sp, h->d, n, dlist, h->store_valid ? h->store : nullptr, h->nbk,
+                              h->spmax, h->stream2));
+  HIPCHK(hipEventRecord(h->evjoin, h->stream2));
+  if (drows) LAUNCH(h, K_INIT, launch_scatter_x0(h->d, n, dlist, drows, h->stream));
+  LAUNCH(h, K_INIT, launch_init(rs, rd, h->stream));
+  // (k_init wrote the AL / ReB initial values of problem 0's set)
+  if (h->psets.size() > 1) LAUNCH(h, K_INIT, launch_init_params(rs, rd, h->stream));
+  HIPCHK(hipStreamWaitEvent(h->stream, h->evjoin, 0));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return MHPC_OK;
+}
+
+// MHPCLocomotion::initialization() (MHPCLocomotion.cpp:47-53: memory_reset, build_problem,
+// generate_ref, warmstart) of the listed problems only: each comes out as mhpc_initialize leaves
+// a problem (its own command and parameter set, the given x0 row or its current one, identity
+// phase buffers, optionally another descriptor); every other problem's device records stay bit
+// for bit, so the knot stride never changes here and a descriptor that does not fit the arrays
+// as they are is refused.  The handle's call-order flags stay as they are.
+int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* x0, int n_desc,
+                       const mhpc_problem_desc* descs, const int32_t* desc_of) {
+  if (!h || !problems) return fail(MHPC_ERR_INVALID, "null argument");
+  if (!h->initialized) return fail(MHPC_ERR_STATE, "mhpc_initialize must precede mhpc_reset_problems");
+  const int B = h->sp.B;
+  if (n < 1 || n > B) return fail(MHPC_ERR_INVALID, "n must be 1..batch");
+  std::vector<int> at(B, -1);  // a listed problem's place in the list
+  for (int i = 0; i < n; ++i) {
+    const int b = problems[i];
+    if (b < 0 || b >= B) return fail(MHPC_ERR_INVALID, "problem out of range");
+    if (at[b] >= 0) return fail(MHPC_ERR_INVALID, "problem listed twice");
+    at[b] = i;
+  }
+  if (!descs && n_desc != 0) return fail(MHPC_ERR_INVALID, "n_desc without descriptors");
+  if (descs && (n_desc < 1 || n_desc > MAXL))
+    return fail(MHPC_ERR_INVALID, "n_desc must be 1..MHPC_MAX_LAYOUTS");
+  for (int i = 0; i < n_desc; ++i) {  // the checks of mhpc_set_layouts
+    int rc = validate(&descs[i]);
+    if (rc) return rc;
+    if (descs[i].precision != h->desc.precision)
+      return fail(MHPC_ERR_INVALID, "a layout's precision differs from the handle's");
+    if (descs[i].vel_cmd != h->desc.vel_cmd || descs[i].height_cmd != h->desc.height_cmd)
+      return fail(MHPC_ERR_INVALID, "a layout's vel_cmd / height_cmd differs from the handle's");
+  }
+  for (int i = 0; descs && desc_of && i < n; ++i)
+    if (desc_of[i] < 0 || desc_of[i] >= n_desc) return fail(MHPC_ERR_INVALID, "layout index out of range");
+  const int r = x0_row(h);
+  std::vector<ProbLayout> npl = h->pl;
+  for (int i = 0; i < n; ++i) {
+    ProbLayout& q = npl[problems[i]];
+    if (descs) q.desc = norm_desc(descs[desc_of ? desc_of[i] : i % n_desc]);
+    q.rot_wb = q.rot_fb = 0;
+    // the arrays stay as they are: the layout must fit the knot stride and the phase buffers
+    const int P = q.desc.n_wb + q.desc.n_fb;
+    int NK = 0;
+    for (int p = 0; p < P; ++p) {
+      NK += q.desc.N[p];
+      if (h->store_valid && q.desc.N[p] > h->nbk)
+        return fail(MHPC_ERR_INVALID, "phase longer than the phase buffers");
+    }
+    if (NK > h->sp.NK)
+      return fail(MHPC_ERR_INVALID, "layout longer than the knot stride (a reset never grows the arrays)");
+    if (h->store_valid && P > h->spmax)
+      return fail(MHPC_ERR_INVALID, "more phases than the phase-buffer store holds");
+  }
+  bool any_wb = false;
+  for (const ProbLayout& q : npl) any_wb = any_wb || q.desc.n_wb > 0;
+  if ((any_wb ? 14 : 6) != r) return fail(MHPC_ERR_INVALID, "the x0 row width would change");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->pl.swap(npl);
+  int rc = rebuild_groups(h, true);
+  if (rc) {  // too many groups: nothing changed but pl
+    h->pl.swap(npl);
+    return rc;
+  }
+  std::vector<int> order(problems, problems + n);
+  std::sort(order.begin(), order.end(), [&](int a, int c) {
+    return h->lid[a] != h->lid[c] ? h->lid[a] < h->lid[c] : a < c;
+  });
+  std::vector<real> rows;
+  if (x0) {
+    rows.assign((size_t)n * 14, real(0));
+    for (int j = 0; j < n; ++j) {
+      const int b = order[j], nb = h->pl[b].desc.n_wb > 0 ? 14 : 6;
+      std::copy(x0 + (size_t)at[b] * r, x0 + (size_t)at[b] * r + nb, rows.begin() + (size_t)j * 14);
+    }
+  }
+  for (int b : order) {
+    h->cmode[b] = h->pl[b].desc.mode_seq[0];
+    h->kbytes[K_INIT] += h->bym[h->lid[b]].init + (h->psets.size() > 1 ? 4 * MAXP * kB : 0.0);
+    if (!h->fresh[b]) {
+      h->fresh[b] = 1;
+      ++h->nfresh;
+    }
+  }
+  rc = reset_launches(h, order, std::move(rows));
+  if (rc) {  // nothing of the handle's may stay queued behind a failed launch
+    (void)hipStreamSynchronize(h->stream2);
+    (void)hipStreamSynchronize(h->stream);
+    return rc;
+  }
+  return collect_profile(h);
 }
 
 int api_get_problem_desc(Handle* h, int b, mhpc_problem_desc* desc) {
@@ -1815,6 +2014,7 @@ void api_destroy(Handle* h) {
   free_bufs(h);
   if (h->dcnt) (void)hipFree(h->dcnt);
   if (h->store) (void)hipFree(h->store);
+  if (h->dsplit) (void)hipFree(h->dsplit);
   for (hipEvent_t e : h->evpool) (void)hipEventDestroy(e);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);

@@ -341,6 +341,41 @@ class MHPCLocomotion:
                    "mhpc_update_problems")
         self._refresh_descs()
 
+    # -- per-problem re-initialisation: restart lost problems inside a live batch -------------
+    def reset_problems(self, problems, x0=None, descs=None, desc_of=None):
+        """mhpc_reset_problems: initialization() of the listed problems only -- the reference's
+        set_initial_condition + initialization() on one controller of a fleet
+        (MHPCLocomotion.cpp:47-53).  x0 [len(problems)][r] in list order (None: each keeps its
+        current device row); descs / desc_of move listed problem i to descs[desc_of[i]]
+        (descs[i % len] when None), else it keeps its descriptor with identity phase buffers.
+        Every other problem keeps its warm start, bit for bit.  After a solve, follow with
+        update_problems(steps=0 for the reset problems); before a solve, just solve."""
+        pr = np.ascontiguousarray(problems, dtype=np.int32).reshape(-1)
+        if x0 is not None:
+            x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).reshape(pr.size, -1))
+            if x0.shape[1] != self._x0_row():
+                raise ValueError("x0 must be [len(problems)][x0 row length]")
+        arr, dof = None, None
+        if descs is not None:
+            arr = (capi.ProblemDesc * len(descs))(*descs)
+            if desc_of is not None:
+                dof = np.ascontiguousarray(desc_of, dtype=np.int32)
+                if dof.shape != pr.shape:
+                    raise ValueError("desc_of must have one entry per listed problem")
+        capi.check(capi.lib().mhpc_reset_problems(self._h, int(pr.size), capi.iptr(pr),
+                                                  capi.dptr(x0), 0 if descs is None else len(descs),
+                                                  arr, capi.iptr(dof)), "mhpc_reset_problems")
+        if x0 is not None:  # what the next update_problem(s) hands back to the device
+            self._x0 = self._x0.copy()
+            self._x0[pr] = x0
+        if descs is not None:
+            self._refresh_descs()
+
+    def lost_problems(self) -> np.ndarray:
+        """Problems whose last solve did not end MHPC_SOLVE_OK or left a non-finite cost."""
+        J = self.get_scalars()["J"]
+        return np.flatnonzero((self.status != capi.MHPC_SOLVE_OK) | ~np.isfinite(J))
+
     # -- per-problem user commands: the batch axis over USRCMD ------------------------------
     def _command_array(self, v, name: str):
         """None, a scalar (broadcast over the batch) or [batch] values, each rounded through
