@@ -510,6 +510,31 @@ int mhpc_eval_srb_f32(int device, int n, const double* x, const double* u,
                       const double* foothold, const double* contact, double* xdot, double* Ac,
                       double* Bc);
 
+/* ---- hand-written elementary functions on the device (accuracy hooks) ---------------
+ * Each function evaluated at n points exactly as the solve kernels call it.  Lane i of a
+ * 64-lane block takes point i (of the SINCOS_N functions: group i of 5 / 3 consecutive angles,
+ * n a multiple of the group), so the caller decides which arguments share a wavefront.
+ * Host arrays are double, rounded to the library's type on the way in and widened on the way
+ * out; b is read by REDUCED_BARRIER and DIV_CONST only (else it may be null).
+ * out: [n][2] (sin, cos), [n][3] (B, Bz, Bzz) or [n]. */
+#define MHPC_PRIM_SINCOS 0          /* sin_cos(a) */
+#define MHPC_PRIM_SINCOS_N5 1       /* sin_cos_n<5> (whole-body geometry) */
+#define MHPC_PRIM_SINCOS_N3 2       /* sin_cos_n<3> (lane-pair model) */
+#define MHPC_PRIM_SINCOS_N5_VK 3    /* the same two with the knot loops' register copy of */
+#define MHPC_PRIM_SINCOS_N3_VK 4    /* the reduction constants */
+#define MHPC_PRIM_PIVOT_RCP 5       /* pivot_rcp(a) (model pivots) */
+#define MHPC_PRIM_SWEEP_RECIP 6     /* the backward sweep's recip(a) in the sweep's type: double
+                                       in both libraries (a and out are not rounded) */
+#define MHPC_PRIM_SWEEP_RECIP_F32 7 /* mhpc_eval_primitive_f32 only: recip(float) of the float
+                                       sweep (MHPC_VARIANT_SWEEP_BITS 32) */
+#define MHPC_PRIM_LOG_POS 8         /* log_pos(a) */
+#define MHPC_PRIM_REDUCED_BARRIER 9 /* reduced_barrier(g = a, delta = b) */
+#define MHPC_PRIM_DIV_CONST 10      /* div_const(a, c, RN(1 / c)): c the SRB mass (b = 0) or the
+                                       SRB inertia (b != 0) */
+int mhpc_eval_primitive(int device, int fn, int n, const double* a, const double* b, double* out);
+int mhpc_eval_primitive_f32(int device, int fn, int n, const double* a, const double* b,
+                            double* out);
+
 #ifdef __cplusplus
 }
 #endif

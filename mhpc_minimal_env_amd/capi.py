@@ -260,7 +260,17 @@ SIGNATURES = [
                                                   _DP, _DP, _DP, _DP, _DP]),
     ("mhpc_eval_srb_f32", ctypes.c_int, [ctypes.c_int, ctypes.c_int, _DP, _DP, _DP, _DP, _DP, _DP,
                                          _DP]),
+    ("mhpc_eval_primitive", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _DP, _DP,
+                                           _DP]),
+    ("mhpc_eval_primitive_f32", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _DP, _DP,
+                                               _DP]),
 ]
+
+# mhpc_eval_primitive's functions (MHPC_PRIM_*): name -> (fn, outputs per point)
+PRIMITIVES = {"sin_cos": (0, 2), "sin_cos_n5": (1, 2), "sin_cos_n3": (2, 2),
+              "sin_cos_n5_vk": (3, 2), "sin_cos_n3_vk": (4, 2), "pivot_rcp": (5, 1),
+              "sweep_recip": (6, 1), "sweep_recip_f32": (7, 1), "log_pos": (8, 1),
+              "reduced_barrier": (9, 3), "div_const": (10, 1)}
 
 _lib = None
 

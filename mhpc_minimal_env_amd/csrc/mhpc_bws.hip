@@ -159,19 +159,35 @@ __device__ __forceinline__ void row_pair_swap(float v, float& a, float& b) {
 }
 
 // 1 / a by the hardware estimate and two Newton steps (within an ulp of the division; the
-// IEEE division sequence is twice the instructions and latency)
-__device__ __forceinline__ double recip(double a) {
-  double r = __builtin_amdgcn_rcp(a);
-  double e = __builtin_fma(-a, r, 1.0);
-  r = __builtin_fma(r, e, r);
+// IEEE division sequence is twice the instructions and latency); 0 where `zero` holds (the PSD
+// test's zero pivot).  Where the estimate is +-0, +-inf or NaN (a = +-inf, NaN, +-0, a double
+// below 2^-1024) the refinement is inf - inf or 0 inf, and the estimate itself is returned:
+// the IEEE value, as pivot_rcp does (tests/test_gpu_primitives.py; without it NaN).  The class
+// test reads the estimate, not the refinement, so it issues beside the Newton steps and only
+// its select follows them: 0.5 to 1 % of the C3 solve.  (Measured alternatives, all slower: the
+// test on the refined value 1.2 %, one merged select 1.2-1.6 %, a test on a's exponent bits
+// ahead of the estimate 6 %: the serial pivot chain pays for every instruction put into it.)
+constexpr unsigned kFpZeroInfNan = 0x001 | 0x002 | 0x004 | 0x020 | 0x040 | 0x200;
+__device__ __forceinline__ double recip_or_zero(double a, bool zero) {
+  const double r0 = __builtin_amdgcn_rcp(a);
+  const bool keep = zero || __builtin_isfpclass(r0, kFpZeroInfNan);
+  const double other = zero ? 0.0 : r0;
+  double e = __builtin_fma(-a, r0, 1.0);
+  double r = __builtin_fma(r0, e, r0);
   e = __builtin_fma(-a, r, 1.0);
-  return __builtin_fma(r, e, r);
+  r = __builtin_fma(r, e, r);
+  return keep ? other : r;
 }
-__device__ __forceinline__ float recip(float a) {
-  float r = __builtin_amdgcn_rcpf(a);
-  const float e = __builtin_fmaf(-a, r, 1.0f);
-  return __builtin_fmaf(r, e, r);
+__device__ __forceinline__ float recip_or_zero(float a, bool zero) {
+  const float r0 = __builtin_amdgcn_rcpf(a);
+  const bool keep = zero || __builtin_isfpclass(r0, kFpZeroInfNan);
+  const float other = zero ? 0.0f : r0;
+  const float e = __builtin_fmaf(-a, r0, 1.0f);
+  const float r = __builtin_fmaf(r0, e, r0);
+  return keep ? other : r;
 }
+__device__ __forceinline__ double recip(double a) { return recip_or_zero(a, false); }
+__device__ __forceinline__ float recip(float a) { return recip_or_zero(a, false); }
 
 // Eigen::LDLT(Quu - 1e-9 I).isPositive() (SinglePhase.cpp:202-209): an unpivoted LDL^T of
 // the lower triangle.  By Sylvester's law of inertia its pivots have the signs of Eigen's
@@ -184,7 +200,7 @@ __device__ __forceinline__ bool ldlt_nopiv_is_positive4(breal* A) {
     const breal akk = A[k * 5];
     neg = neg || akk < breal(0.0);
     // a zero pivot leaves its column (r = 0: the updates subtract exact zeros)
-    const breal r = akk != breal(0.0) ? recip(akk) : breal(0.0);
+    const breal r = recip_or_zero(akk, !(akk != breal(0.0)));
 #pragma unroll
     for (int i = k + 1; i < 4; ++i) {
       const breal l = A[i * 4 + k] * r;
@@ -223,7 +239,7 @@ struct Ldl4 {
   // rule and returns its verdict in neg (pivot < 0).  That lane must hold no matrix row the knot
   // needs (its K, du, H are garbage, but finite).  One factorisation per knot instead of two.
   __device__ __forceinline__ Ldl4(const T (&q)[4][4], T shift, bool psd_lane, bool& neg) {
-    auto piv = [&](T a) { return (a != T(0.0) || !psd_lane) ? recip(a) : T(0.0); };
+    auto piv = [&](T a) { return recip_or_zero(a, !(a != T(0.0) || !psd_lane)); };
     const T a00 = q[0][0] - shift;
     r0 = piv(a00);
     l10 = q[1][0] * r0;
@@ -1610,6 +1626,16 @@ hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, real update_reg, 
 // both kinds of phase present, not switched off (var_overlap 2).
 bool bws_split(const SolveParams& sp) {
   return sp.split_ok && sp.var_overlap != 2;
+}
+
+// recip of this build's sweep type at n points (mhpc_eval_primitive, MHPC_PRIM_SWEEP_RECIP*)
+__global__ void k_eval_recip(int n, const breal* a, breal* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = recip(a[i]);
+}
+hipError_t launch_eval_recip(int n, const breal* a, breal* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_eval_recip, dim3((n + 63) / 64), dim3(64), 0, s, n, a, out);
+  return hipGetLastError();
 }
 
 #ifdef MHPC_BWS_VARIANT_NS

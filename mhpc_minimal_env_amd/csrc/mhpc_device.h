@@ -88,10 +88,15 @@ static __device__ __forceinline__ Cmd cmd_of(const DevBufs& d, int b) { return d
 
 // Natural log of a positive argument (the barrier's g > delta > 0 and delta itself).  fp64:
 // the fdlibm algorithm (e_log.c: x = 2^k (1 + f) with sqrt(2)/2 <= 1 + f < sqrt(2),
-// s = f / (2 + f), a degree-14 odd polynomial in s), < 1 ulp -- about a third of the
-// instructions of the library log, whose extra work covers denormal scaling and special
-// values this path never sees.  The line search evaluates up to 11 of these per WB knot
-// and candidate while the ReB barrier is active.
+// s = f / (2 + f), a degree-14 odd polynomial in s), < 1 ulp on every positive finite argument,
+// subnormals included (frexp scales them), and log_pos(1) = +0 (tests/test_gpu_primitives.py
+// against a 60-digit reference) -- about a third of the instructions of the library log, whose
+// extra work covers special values this path never sees.  log_pos(+inf) is NaN (f / (2 + f) is
+// inf / inf) where the library gives +inf: a barrier argument of +inf, which no constraint of
+// the model is known to reach, gives B = NaN where the reference has -inf (the test records
+// it as an expected failure; a select on the result cost 0.5 % of the C3 solve).  The line
+// search evaluates up to 11 of these per WB knot and candidate while the ReB barrier is
+// active.
 static __device__ __forceinline__ real log_pos(real x) {
   MHPC_NO_FMA_F32
 #ifdef MHPC_FP32

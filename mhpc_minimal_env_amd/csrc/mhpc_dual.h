@@ -89,11 +89,13 @@ MHPC_HD Dual mad(Dual a, real b, real c) { return Dual(fma(a.v, b, c), a.d * b);
 // 2x2 contact KKT block).  fp64 device code: the hardware reciprocal estimate refined by two
 // Newton steps (within an ulp of the IEEE quotient, about half the instructions and dependent
 // steps of the division sequence on the serial knot chain), the estimate itself where the
-// refinement is not finite (a = 0, +-inf, NaN: the IEEE value).  The fp32 build keeps the
-// IEEE quotient: its C5 cost error is chaotic in the last bits of the model (one Newton step
-// from the fp32 estimate moved the worst of 64 problems from 1.8e-3 to 6.0e-3, past the
-// test's 5e-3 target).  The single-lane, lane-pair and dual-number models all take it, so they
-// still agree bit for bit where they must (tests/test_pair_host.py, test_gpu_kernels.py).
+// refinement is not finite (a = +-0, +-inf, NaN, and a double below 2^-1024, whose quotient
+// overflows: the IEEE value; the subnormal quotients of |a| > 2^1022 are the IEEE value too
+// on every point of tests/test_gpu_primitives.py).  The fp32 build keeps the IEEE quotient:
+// its C5 cost error is chaotic in the last bits of the model (one Newton step from the fp32
+// estimate moved the worst of 64 problems from 1.8e-3 to 6.0e-3, past the test's 5e-3
+// target).  The single-lane, lane-pair and dual-number models all take it, so they still
+// agree bit for bit where they must (tests/test_pair_host.py, test_gpu_kernels.py).
 MHPC_HD real pivot_rcp(real a) {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(MHPC_FP32)
   const double r = __builtin_amdgcn_rcp(a);
@@ -137,10 +139,15 @@ constexpr SinCosK kSinCosK = {{0.63661977236758138,  // 2 / pi
 
 #ifndef MHPC_FP32
 // sin and cos of a link angle: one Cody-Waite reduction by pi/2 (two-part pi/2, FMA) and
-// the fdlibm kernels on |r| <= pi/4 (< 0.75 ulp each); <= 1.5 ulp overall, checked against
-// long double on |a| <= 60.  About half the instructions of the library sincos, whose
-// reduction carries a double-double and a Payne-Hanek path for huge arguments -- kept here
-// only for |a| > 1e5 (a diverged rollout), where the short reduction loses accuracy.
+// the fdlibm kernels on |r| <= pi/4 (< 0.75 ulp each).  On |a| <= 1e5 the absolute error is
+// below 1.2e-16 (the bound the model needs), which is <= 1.5 ulp at random arguments; it is
+// no relative bound: at the doubles next to a multiple of pi/2 the result is tiny, the
+// reduced argument keeps its absolute error (about |k| 2^-110), and the error reaches 1.8e3
+// ulps of the result (a = 46066.743875913933).  sin(-0) is +0.  Checked against 60-digit
+// references in tests/test_prim_host.py (host) and tests/test_gpu_primitives.py (device).
+// About half the instructions of the library sincos, whose reduction carries a double-double
+// and a Payne-Hanek path for huge arguments -- kept here only for |a| > 1e5 (a diverged
+// rollout), where the short reduction loses accuracy.
 MHPC_HD void sin_cos_short(double a, double* s, double* c, const SinCosK& K = kSinCosK) {
   const double k = rint(a * K.c[0]);
   double r = fma(-k, K.c[1], a);

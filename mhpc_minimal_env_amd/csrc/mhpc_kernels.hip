@@ -1925,6 +1925,68 @@ __global__ void k_eval_srb(int n, const real* x, const real* u, const real* p,
   srb_jacobians(x + (size_t)i * 6, u + (size_t)i * 4, p + (size_t)i * 4, s + (size_t)i * 2, Ac + (size_t)i * 36, Bc + (size_t)i * 24);
 }
 
+// One hand-written elementary function per point, called as the solve kernels call it
+// (mhpc_eval_primitive, MHPC_PRIM_*).  Lane t of a 64-lane block evaluates point t of the
+// launch, so the caller decides which arguments share a wave (the wave-uniform library
+// fallback of sin_cos); of the sin_cos_n functions, group t of N consecutive angles.  out is
+// [n][w]: w = 2 (sin, cos), 3 (B, Bz, Bzz) or 1.
+template <int N>
+static __device__ __forceinline__ void eval_sin_cos_n(int n, bool vk, const real* a, real* out) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  // the knot loops' VGPR copy of the constants (k_rollout); lanes past the last group run the
+  // functions too, on zeros: the ballot inside is over the whole wave
+  SinCosK scK = kSinCosK;
+#if !defined(MHPC_FP32)
+  if (vk) {
+#pragma unroll
+    for (int i = 0; i < 15; ++i) asm volatile("" : "+v"(scK.c[i]));
+  }
+#endif
+  const bool live = (g + 1) * N <= n;
+  real v[N], s[N], c[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = live ? a[(size_t)g * N + i] : real(0.0);
+  if (vk) sin_cos_n<N>(v, s, c, scK);
+  else sin_cos_n<N>(v, s, c);
+  if (!live) return;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    out[((size_t)g * N + i) * 2] = s[i];
+    out[((size_t)g * N + i) * 2 + 1] = c[i];
+  }
+}
+__global__ void k_eval_prim(int fn, int n, const real* a, const real* b, real* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  switch (fn) {  // uniform
+    case MHPC_PRIM_SINCOS_N5: eval_sin_cos_n<5>(n, false, a, out); return;
+    case MHPC_PRIM_SINCOS_N3: eval_sin_cos_n<3>(n, false, a, out); return;
+    case MHPC_PRIM_SINCOS_N5_VK: eval_sin_cos_n<5>(n, true, a, out); return;
+    case MHPC_PRIM_SINCOS_N3_VK: eval_sin_cos_n<3>(n, true, a, out); return;
+    default: break;
+  }
+  const bool live = i < n;
+  const real ai = live ? a[i] : real(1.0);
+  if (fn == MHPC_PRIM_SINCOS) {  // every lane of the wave reaches the ballot
+    real s, c;
+    sin_cos(ai, &s, &c);
+    if (live) { out[(size_t)i * 2] = s; out[(size_t)i * 2 + 1] = c; }
+    return;
+  }
+  if (!live) return;
+  if (fn == MHPC_PRIM_PIVOT_RCP) {
+    out[i] = pivot_rcp(ai);
+  } else if (fn == MHPC_PRIM_LOG_POS) {
+    out[i] = log_pos(ai);
+  } else if (fn == MHPC_PRIM_REDUCED_BARRIER) {
+    real B, Bz, Bzz;
+    reduced_barrier(ai, b[i], &B, &Bz, &Bzz);
+    out[(size_t)i * 3] = B; out[(size_t)i * 3 + 1] = Bz; out[(size_t)i * 3 + 2] = Bzz;
+  } else if (fn == MHPC_PRIM_DIV_CONST) {  // b: 0 the SRB mass, otherwise its inertia
+    out[i] = b[i] == real(0.0) ? div_const(ai, kSrbMass, kSrbMassRcp)
+                               : div_const(ai, kSrbInertia, kSrbInertiaRcp);
+  }
+}
+
 // Sum the per-problem counters of each group (int64 atomics into NCNT slots per group).
 // One block of 256 threads, strided over the batch, tree-reduced in LDS: NCNT atomics per
 // block instead of per problem (the per-problem atomics on NCNT words serialised, ~35 us).
@@ -2217,6 +2279,17 @@ hipError_t launch_eval_wb_impact(int n, int foot, const real* x, real* xp, real*
 hipError_t launch_eval_srb(int n, const real* x, const real* u, const real* p,
                            const real* c, real* xd, real* Ac, real* Bc, hipStream_t s) {
   hipLaunchKernelGGL(k_eval_srb, dim3((n + 63) / 64), dim3(64), 0, s, n, x, u, p, c, xd, Ac, Bc);
+  return hipGetLastError();
+}
+int eval_prim_group(int fn) {
+  return fn == MHPC_PRIM_SINCOS_N5 || fn == MHPC_PRIM_SINCOS_N5_VK   ? 5
+         : fn == MHPC_PRIM_SINCOS_N3 || fn == MHPC_PRIM_SINCOS_N3_VK ? 3
+                                                                     : 1;
+}
+hipError_t launch_eval_prim(int fn, int n, const real* a, const real* b, real* out,
+                            hipStream_t s) {
+  const int lanes = n / eval_prim_group(fn);  // n is a multiple of the group (the hook checks)
+  hipLaunchKernelGGL(k_eval_prim, dim3((lanes + 63) / 64), dim3(64), 0, s, fn, n, a, b, out);
   return hipGetLastError();
 }
 

@@ -64,14 +64,23 @@ hipError_t launch_eval_wb_impact(int n, int foot, const real* x, real* xp, real*
 hipError_t launch_eval_srb(int n, const real* x, const real* u, const real* p,
                            const real* c, real* xd, real* Ac, real* Bc, hipStream_t s);
 
+// primitive evaluation hook (MHPC_PRIM_*): n points, out [n][2 | 3 | 1]; eval_prim_group = the
+// angles one lane takes (5 / 3 of the sin_cos_n functions, else 1), which n is a multiple of
+int eval_prim_group(int fn);
+hipError_t launch_eval_prim(int fn, int n, const real* a, const real* b, real* out,
+                            hipStream_t s);
+
 // ---- mhpc_bws.hip ---------------------------------------------------------------------------
 hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, real update_reg, int part,
                       hipStream_t s);
 bool bws_split(const SolveParams& sp);
+// the sweep's pivot reciprocal in the sweep's arithmetic type (double in both libraries)
+hipError_t launch_eval_recip(int n, const double* a, double* out, hipStream_t s);
 #ifdef MHPC_FP32
 namespace fsweep {  // the float-arithmetic sweep (mhpc_bws.hip built with MHPC_BWS_F64=0)
 hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, real update_reg, int part,
                       hipStream_t s);
+hipError_t launch_eval_recip(int n, const float* a, float* out, hipStream_t s);
 }
 #endif
 

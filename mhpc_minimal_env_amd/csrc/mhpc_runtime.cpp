@@ -2139,4 +2139,33 @@ extern "C" int HOOK(mhpc_eval_srb)(int device, int n, const double* x, const dou
   HOOK_RUN(t, HOOK_NAME(mhpc_eval_srb), launch_eval_srb(n, dx, du, dp, dc, dxd, dA, dB, nullptr));
 }
 
+// One elementary function at n points (MHPC_PRIM_*, include/mhpc_capi.h).
+extern "C" int HOOK(mhpc_eval_primitive)(int device, int fn, int n, const double* a,
+                                         const double* b, double* out) {
+  const bool two = fn == MHPC_PRIM_REDUCED_BARRIER || fn == MHPC_PRIM_DIV_CONST;
+  bool known = fn >= MHPC_PRIM_SINCOS && fn <= MHPC_PRIM_DIV_CONST;
+#ifndef MHPC_FP32
+  known = known && fn != MHPC_PRIM_SWEEP_RECIP_F32;
+#endif
+  if (n < 1 || !a || !out || !known || (two && !b) || n % eval_prim_group(fn))
+    return fail(MHPC_ERR_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(device));
+  const size_t m = n;
+  if (fn == MHPC_PRIM_SWEEP_RECIP) {  // the sweep's type, not the library's
+    DevTemp<double> t;
+    double *da = t.in(a, m), *dout = t.out(out, m);
+    HOOK_RUN(t, HOOK_NAME(mhpc_eval_primitive), launch_eval_recip(n, da, dout, nullptr));
+  }
+  DevTemp<real> t;
+#ifdef MHPC_FP32
+  if (fn == MHPC_PRIM_SWEEP_RECIP_F32) {
+    real *da = t.in(a, m), *dout = t.out(out, m);
+    HOOK_RUN(t, HOOK_NAME(mhpc_eval_primitive), fsweep::launch_eval_recip(n, da, dout, nullptr));
+  }
+#endif
+  const size_t w = fn <= MHPC_PRIM_SINCOS_N3_VK ? 2 : fn == MHPC_PRIM_REDUCED_BARRIER ? 3 : 1;
+  real *da = t.in(a, m), *db = two ? t.in(b, m) : nullptr, *dout = t.out(out, m * w);
+  HOOK_RUN(t, HOOK_NAME(mhpc_eval_primitive), launch_eval_prim(fn, n, da, db, dout, nullptr));
+}
+
 }  // namespace MHPC_NS

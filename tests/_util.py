@@ -66,12 +66,39 @@ KAT_TOL_F32 = {
         "srb.Ac": 5e-7,    # host 1.17e-7; device 1.2e-7, device vs host 0
         "srb.Bc": 2e-6,    # host 2.92e-7; device 2.9e-7, device vs host 0
     },
+    # Rows 0-47 only: a float cannot hold the angles of rows 48-63 (link-angle sums of 1e3 to
+    # 3e5, where a float ulp is 6e-5 to 0.03 rad), so the fp32 builds are not run on them.  On
+    # rows 32-47 (angles up to 60, float ulp 4e-6 rad) the rounding of the inputs alone is what
+    # the entries of h, hx, hxx, J and Jd measure.
+    "kat_model_wide.npz": {
+        "xdot": 3e-5,      # host 5.15e-6; device 1.4e-6, device vs host 4.5e-7
+        "y": 2e-4,         # host 2.76e-5; device 2.7e-5, device vs host 1.0e-6
+        "Ac": 9e-5,        # host 2.13e-5; device 2.2e-5, device vs host 2.4e-5
+        "Bc": 2e-5,        # host 3.36e-6; device 3.5e-6, device vs host 4.7e-7
+        "C": 2e-4,         # host 4.66e-5; device 5.2e-5, device vs host 1.2e-5
+        "D": 8e-5,         # host 1.94e-5; device 1.9e-5, device vs host 1.4e-6
+        "xplus": 5e-5,     # host 1.17e-5; device 1.2e-5, device vs host 1.5e-6
+        "lam": 6e-5,       # host 1.29e-5
+        "Px": 9e-5,        # host 2.05e-5; device 2.3e-5, device vs host 1.2e-5
+        "h": 4e-6,         # host 7.84e-7; device 7.7e-7, device vs host 1.1e-7
+        "hx": 6e-6,        # host 1.28e-6; device 1.3e-6, device vs host 3.0e-8
+        "hxx": 6e-6,       # host 1.33e-6; device 1.3e-6, device vs host 3.0e-8
+        "J": 6e-6,         # host 1.33e-6; device 1.3e-6, device vs host 3.0e-8
+        "Jd": 2e-5,        # host 3.84e-6; device 3.9e-6, device vs host 1.3e-7
+        "srb.xdot": 3e-6,  # host 7.00e-7; device 7.0e-7, device vs host 0 (the SRB points of kat_model.npz)
+        "srb.Ac": 2e-6,    # host 4.51e-7; device 4.5e-7, device vs host 0
+        "srb.Bc": 6e-7,    # host 1.40e-7; device 1.4e-7, device vs host 0
+    },
 }
 
 
-# The two known-answer fixtures (tests/golden/make_golden.py): uniform-random states, and
-# knots of the oracle's C5 solution (each tagged with its phase's mode).
-KAT_FIXTURES = ("kat_model.npz", "kat_model_traj.npz")
+# The known-answer fixtures (tests/golden/make_golden.py): uniform-random states, knots of
+# the oracle's C5 solution (each tagged with its phase's mode), and states off the range of
+# both (the nominal posture, angles of several turns, link-angle sums up to 3e5).
+KAT_FIXTURES = ("kat_model.npz", "kat_model_traj.npz", "kat_model_wide.npz")
+KAT_WIDE = KAT_FIXTURES[2]
+KAT_WIDE_COND = 48    # its rows from here on are bounded by the reference's own conditioning
+KAT_COND_SKIP = 1e-6  # a row whose bound exceeds this says nothing (at most 4 rows may)
 DYN_NAME = {1: "Dyn_BS", 2: "Dyn_FL", 3: "Dyn_FS", 4: "Dyn_FL"}  # mode 4 is flight too
 IMP_NAME = {0: "Imp_F", 1: "Imp_B"}
 TD_NAME = {0: "WB_FL1_terminal_constr", 1: "WB_FL2_terminal_constr"}
@@ -80,6 +107,55 @@ JAC_NAME = {0: "Jacob_F", 1: "Jacob_B"}
 
 def golden(name):
     return dict(np.load(os.path.join(GOLDEN, name), allow_pickle=False))
+
+
+def kat_for(name, precision):
+    """Fixture `name` as a build of `precision` is checked on it: the fp32 build skips the
+    wide fixture's rows from KAT_WIDE_COND on (a float cannot hold those angles: at 1e5 its
+    ulp is 0.008 rad)."""
+    kat = golden(name)
+    if name == KAT_WIDE and precision == 32:
+        n = len(kat["x"])
+        kat = {k: (v[:KAT_WIDE_COND] if v.ndim and len(v) == n and not k.startswith(("srb.", "FBDynamics"))
+                   else v) for k, v in kat.items() if not k.startswith("spread.")}
+    return kat
+
+
+def kat_row_bounds(kat, key, tol, rows):
+    """Bound of each of `rows` for reference output `key`: tol, and on the rows the wide
+    fixture stores a conditioning spread for (make_kat_wide: how far the reference's own output
+    moves when a position moves by an ulp) tol + 4 x that spread."""
+    rows = np.asarray(rows)
+    b = np.full(len(rows), float(tol))
+    if "spread." + key in kat:
+        c = rows >= KAT_WIDE_COND
+        b[c] += 4.0 * kat["spread." + key][rows[c] - KAT_WIDE_COND]
+    return b
+
+
+def assert_rows_within(got, ref, bounds, what):
+    """rel_err of each row (a point's whole output) below its bound; rows whose bound exceeds
+    KAT_COND_SKIP are not checked, and at most 4 may be such."""
+    got = np.asarray(got, dtype=float).reshape(len(bounds), -1)
+    ref = np.asarray(ref, dtype=float).reshape(len(bounds), -1)
+    use = bounds <= KAT_COND_SKIP
+    assert (~use).sum() <= 4, (what, bounds)
+    if not use.any():
+        return 0.0
+    e = (np.abs(got - ref) / np.maximum(1.0, np.abs(ref))).max(axis=1)
+    assert (e[use] < bounds[use]).all(), (what, int(np.argmax(e / bounds)), e.max())
+    return float((e[use] / bounds[use]).max())
+
+
+def assert_abs_within(got, ref, kat, key, tol):
+    """|got - ref| < tol on every row of a per-point scalar; on the wide fixture's conditioned
+    rows the row's bound (kat_row_bounds) instead, relative to max(1, |ref|)."""
+    got, ref = np.asarray(got, dtype=float), np.asarray(ref, dtype=float)
+    rows = np.arange(len(ref))
+    cond = rows >= KAT_WIDE_COND if "spread." + key in kat else np.zeros(len(ref), dtype=bool)
+    assert np.max(np.abs(got - ref)[~cond]) < tol, key
+    if cond.any():
+        assert_rows_within(got[cond], ref[cond], kat_row_bounds(kat, key, tol, rows[cond]), key)
 
 
 def kat_rows(kat, mode=None, foot=None):
@@ -114,6 +190,29 @@ def norm_err(a, b):
         return 0.0
     a, b = a.reshape(len(a), -1), b.reshape(len(b), -1)
     return float(np.max(np.abs(a - b).max(axis=1) / np.maximum(1.0, np.abs(b).max(axis=1))))
+
+
+def ulp_err(got, hi, lo, f32=False):
+    """Error of got in ulps of the reference hi + lo (a double-double of prim_kat.npz), per
+    element.  The ulp is that of hi (rounded to float when f32) and is not taken below the
+    smallest normal number, so a subnormal result flushed to zero is within an ulp.  Where the
+    reference is not finite the error is 0 if got is the same value (any NaN for NaN), else
+    inf."""
+    got, hi, lo = (np.asarray(v, dtype=np.float64) for v in (got, hi, lo))
+    fin = np.isfinite(hi)
+    h = np.where(fin, hi, 1.0)
+    if f32:
+        with np.errstate(over="ignore"):
+            sp = np.spacing(np.abs(h).astype(np.float32)).astype(np.float64)
+        sp = np.where(np.isfinite(sp), sp, 2.0 ** 104)  # a reference past the largest float
+        unit = np.maximum(sp, 2.0 ** -126)
+    else:
+        unit = np.maximum(np.spacing(np.abs(h)), 2.0 ** -1022)
+    with np.errstate(invalid="ignore"):
+        e = np.abs((got - h) - lo) / unit
+    same = (got == hi) | (np.isnan(got) & np.isnan(hi))
+    e = np.where(fin, e, np.where(same, 0.0, np.inf))
+    return np.where(np.isnan(e), np.inf, e)
 
 
 _structure = {}

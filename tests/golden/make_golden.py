@@ -7,6 +7,11 @@
   kat_model_traj.npz the same kernels at knots of the oracle's C5 solution (make_kat_traj):
                      states the solver visits, with contact forces, torques and the
                      barrier active, a quarter of them from its worst-conditioned problem.
+  kat_model_wide.npz the same kernels off the range of both (make_kat_wide): the nominal
+                     posture, angles of several turns, link-angle sums up to 3e5 with the
+                     reference's own conditioning there.
+  prim_kat.npz       arguments and 60-digit references (mpmath) of the hand-written elementary
+                     functions (make_prim_kat; `make_golden.py prim_kat` writes this file alone).
   solve_<cfg>.npz    full HSDDP solves of the CPU oracle (restatement + CasADi kernels) for
                      the BASELINE configs at small batch: inputs (x0) and every output incl.
                      the decision trace.
@@ -149,6 +154,296 @@ def make_kat_traj():
     return out
 
 
+WIDE_SEED = 20261020
+WIDE_COND = slice(48, 64)  # the rows whose bound is the reference's own conditioning
+
+
+def _from_link_angles(a):
+    """Pitch and joint angles [n][5] whose link-angle sums (pitch, pitch + hip, pitch + hip +
+    knee, per leg) are a [n][5] up to the rounding of the differences."""
+    return np.stack([a[:, 0], a[:, 1] - a[:, 0], a[:, 2] - a[:, 1], a[:, 3] - a[:, 0],
+                     a[:, 4] - a[:, 3]], axis=1)
+
+
+def make_kat_wide():
+    """The kernels off the range of the other two fixtures, 64 whole-body points:
+      rows 0-31   joint angles around the robot's nominal posture (cQjointBias +- 0.6: hips at
+                  0.3 pi, knees at -0.7 pi), pitch in +-pi, velocities +-10, torques up to the
+                  limit of 33;
+      rows 32-47  pitch and joint angles of several turns (link-angle sums up to 60);
+      rows 48-63  link-angle sums between 1e3 and 3e5, in rows 48-55 some of a point's five
+                  sums above 1e5 (the library sin / cos) and some below (the short reduction).
+    At the last 16 rows one rounding of an angle sum moves the reference itself, so the
+    generator evaluates every kernel again with each of the seven positions moved by +-1 ulp
+    and stores, per output "<key>", "spread.<key>" [16]: the largest change of the point's
+    output, max |d| / max(1, |ref|) over its elements (tests/_conditioning.py does the same one
+    level up).  The SRB points are those of kat_model.npz (the SRB model has no wide range)."""
+    rng = np.random.default_rng(WIDE_SEED)
+    bias = np.array([0.3, -0.7, 0.3, -0.7]) * np.pi
+    x = np.zeros((64, 14))
+    x[:, :2] = rng.uniform(-1, 1, (64, 2))
+    x[:32, 2] = rng.uniform(-np.pi, np.pi, 32)
+    x[:32, 3:7] = bias + rng.uniform(-0.6, 0.6, (32, 4))
+    x[:32, 7:] = rng.uniform(-10, 10, (32, 7))
+    x[32:48, 2:7] = _from_link_angles(rng.uniform(-60, 60, (16, 5)))
+    x[32:, 7:] = rng.uniform(-3, 3, (32, 7))
+    mag = np.exp(rng.uniform(np.log(1e3), np.log(1e5), (16, 5)))
+    big = np.zeros((16, 5), dtype=bool)           # which sums lie above 1e5
+    for i in range(8):                            # rows 48-55: one to four of the five
+        big[i, rng.permutation(5)[:1 + i % 4]] = True
+    big[12:] = True                               # rows 60-63: all five
+    mag[big] = np.exp(rng.uniform(np.log(1.05e5), np.log(3e5), big.sum()))
+    x[48:, 2:7] = _from_link_angles(mag * rng.choice([-1.0, 1.0], (16, 5)))
+    u = rng.uniform(-20, 20, (64, 4))
+    u[:32] = rng.uniform(-33, 33, (32, 4))
+    u[:8] = 33.0 * rng.choice([-1.0, 1.0], (8, 4))
+    srb = dict(np.load(os.path.join(HERE, "kat_model.npz")))
+    s = (srb["srb.x"], srb["srb.u"], srb["srb.p"], srb["srb.s"])
+    out = eval_kat(x, u, *s)
+    xc, uc = x[WIDE_COND], u[WIDE_COND]
+    keys = [k for k in out if "." in k and not k.startswith(("srb.", "FBDynamics"))]
+    spread = {k: np.zeros(len(xc)) for k in keys}
+    for j in range(7):
+        for d in (-np.inf, np.inf):
+            xp = xc.copy()
+            xp[:, j] = np.nextafter(xp[:, j], d)
+            alt = eval_kat(xp, uc, s[0][:1], s[1][:1], s[2][:1], s[3][:1])
+            for k in keys:
+                ref = out[k][WIDE_COND].reshape(len(xc), -1)
+                dif = np.abs(alt[k].reshape(len(xc), -1) - ref) / np.maximum(1.0, np.abs(ref))
+                spread[k] = np.maximum(spread[k], dif.max(axis=1))
+    out.update({"spread." + k: v for k, v in spread.items()})
+    return out
+
+
+PRIM_SEED = 20261019
+PRIM_DIGITS = 60
+
+
+def _dd(vals):
+    """High-precision values as double-doubles: hi the nearest double, lo the nearest double
+    of value - hi (0 where hi is not finite or the value is no number)."""
+    import mpmath as mp
+    hi = np.array([float(v) for v in vals])
+    lo = np.array([float(v - mp.mpf(h)) if np.isfinite(h) else 0.0 for v, h in zip(vals, hi)])
+    return hi, lo
+
+
+def _signed(rng, lo, hi, n, log=False):
+    m = np.exp(rng.uniform(np.log(lo), np.log(hi), n)) if log else rng.uniform(lo, hi, n)
+    return m * rng.choice([-1.0, 1.0], n)
+
+
+def _prim_sincos(rng, out, key, f32):
+    """sin / cos points and references; f32: every argument a float (the fp32 build's hook
+    rounds its inputs), bands to 1e5 only beyond the special values."""
+    import mpmath as mp
+    t = np.float32 if f32 else np.float64
+    r = lambda v: np.asarray(v, dtype=t).astype(np.float64)
+    nb = 256 if f32 else 512
+    a, band = [], []
+
+    def add(v, b):
+        v = np.atleast_1d(r(v))
+        a.append(v), band.append(np.full(len(v), b, dtype=np.int8))
+
+    for b, (lo, hi) in enumerate(((0, 3), (3, 60), (60, 1e3), (1e3, 1e5))):
+        add(_signed(rng, lo, hi, nb), b)
+    # the doubles (floats) nearest k pi/2 and two neighbours on each side
+    ks = np.unique(np.concatenate([np.round(np.linspace(1, 63661, 64 if f32 else 255)), [29327]]))
+    for k in ks:
+        c = t(float(mp.mpf(int(k)) * mp.pi / 2))
+        pts = [c]
+        for d in (-np.inf, np.inf):
+            p = c
+            for _ in range(2):
+                p = np.nextafter(p, t(d))
+                pts.append(p)
+        add(np.array(pts, dtype=t), 4)
+    if not f32:
+        assert 46066.743875913933 in np.concatenate(a)
+    q = t(np.pi / 4)
+    tiny = np.nextafter(t(0), t(1))
+    add([0.0, -0.0, tiny, -tiny, 2.0 ** -30, -2.0 ** -30, np.nextafter(q, t(0)), q,
+         np.nextafter(q, t(1)), -q], 5)
+    s = t(1e5)  # the switch from the short reduction to the library path
+    add([np.nextafter(s, t(0)), s, np.nextafter(s, t(np.inf))], 6)
+    add(-np.array([np.nextafter(s, t(0)), s, np.nextafter(s, t(np.inf))]), 6)
+    if f32:
+        add(_signed(rng, 1e5, 1e30, 64, log=True), 7)
+    else:
+        add(_signed(rng, 1e5, 1e15, 512, log=True), 7)
+        add([1e300, -1e300], 7)
+    add([np.inf, -np.inf, np.nan], 8)
+    a, band = np.concatenate(a), np.concatenate(band)
+    assert len(a) <= 4096
+    fin = np.isfinite(a)
+    sv = [mp.sin(mp.mpf(v)) if ok else mp.nan for v, ok in zip(a, fin)]
+    cv = [mp.cos(mp.mpf(v)) if ok else mp.nan for v, ok in zip(a, fin)]
+    out[key + ".a"], out[key + ".band"] = a, band
+    out[key + ".s.hi"], out[key + ".s.lo"] = _dd(sv)
+    out[key + ".c.hi"], out[key + ".c.lo"] = _dd(cv)
+
+
+def _barrier_ref(g, d, t):
+    """SinglePhase::reduced_barrier (SinglePhase.cpp:298-317, k = 2) as the reference computes
+    it in type t, operation by operation, with a correctly rounded log and pow (mpmath, then
+    rounded): what an ideal C library would give the reference.  Returns B, Bz, Bzz, side."""
+    import mpmath as mp
+    rn = lambda v: t(float(v)) if t is np.float64 else t(np.float64(float(v)))
+    g, d = t(g), t(d)
+    with np.errstate(all="ignore"):
+        if g > d:
+            if g == np.inf:  # log(inf) = inf, -1 / inf = -0, pow(inf, -2) = +0
+                return t(-np.inf), t(-0.0), t(0.0), True
+            return -rn(mp.log(mp.mpf(float(g)))), t(-1.0) / g, rn(mp.mpf(float(g)) ** -2), True
+        k = 2
+        tt = (g - t(k) * d) / (t(k - 1) * d)
+        p = rn(mp.mpf(float(tt)) ** 2)
+        B = t((k - 1) / k) * (p - t(1)) - rn(mp.log(mp.mpf(float(d))))
+        return B, tt / d, t(1.0), False
+
+
+def _prim_log_barrier(rng, out, f32):
+    import mpmath as mp
+    t = np.float32 if f32 else np.float64
+    r = lambda v: np.asarray(v, dtype=t).astype(np.float64)
+    sfx = "32" if f32 else ""
+    emin, emax, mbits = (-149, 128, 23) if f32 else (-1074, 1024, 52)
+    one, up = t(1), t(np.inf)
+    a, band = [], []
+
+    def add(v, b):
+        v = np.atleast_1d(r(v))
+        a.append(v), band.append(np.full(len(v), b, dtype=np.int8))
+
+    # every binade, random mantissas (a subnormal binade holds fewer bits: ldexp rounds)
+    reps = 8 if f32 else 1
+    e = np.repeat(np.arange(emin, emax), reps)
+    m = 1 + rng.integers(0, 2 ** mbits, len(e)) / 2.0 ** mbits
+    add(np.ldexp(m, e), 0)
+    n1 = 128 if f32 else 512
+    add(1 + rng.uniform(0, 1e-3, n1), 1)
+    add(1 - rng.uniform(0, 1e-3, n1), 1)
+    add([np.nextafter(one, t(0)), one, np.nextafter(one, up)], 2)
+    p = t(np.sqrt(0.5))
+    lo = hi = p
+    pts = [p]
+    for _ in range(8):
+        lo, hi = np.nextafter(lo, t(0)), np.nextafter(hi, up)
+        pts += [lo, hi]
+    add(np.array(pts, dtype=t), 3)
+    add([0.1, 0.01], 4)
+    a, band = np.concatenate(a), np.concatenate(band)
+    assert len(a) <= 4096 and (a > 0).all() and np.isfinite(a).all()
+    out[f"log{sfx}.a"], out[f"log{sfx}.band"] = a, band
+    out[f"log{sfx}.hi"], out[f"log{sfx}.lo"] = _dd([mp.log(mp.mpf(v)) for v in a])
+
+    # barrier pairs: both default relaxations, 0: inside (g > delta), 1: relaxed, 2: g = delta
+    # and its two neighbours, 3: g <= 0, 4: g = 1e200 (g g overflows; 1e30 in float), 5: +inf
+    g, dl, band = [], [], []
+    nb = 64 if f32 else 256
+    for d in r([0.1, 0.01]):
+        d = float(d)
+
+        def addb(v, b):
+            v = np.atleast_1d(r(v))
+            g.append(v), dl.append(np.full(len(v), d)), band.append(np.full(len(v), b, dtype=np.int8))
+
+        addb(np.exp(rng.uniform(np.log(d), np.log(100.0), nb)), 0)  # torque / GRF margins
+        addb(np.exp(rng.uniform(np.log(100.0), np.log(1e30 if f32 else 1e300), nb // 4)), 0)
+        addb(rng.uniform(0.0, d, nb // 2), 1)
+        addb(rng.uniform(-40.0, 0.0, nb // 2), 1)
+        dt_ = t(d)
+        addb([np.nextafter(dt_, t(0)), dt_, np.nextafter(dt_, up)], 2)
+        addb([0.0, -0.0, -1.0, -33.0, -1e3], 3)
+        addb([1e30 if f32 else 1e200], 4)
+        addb([np.inf], 5)
+    g, dl, band = np.concatenate(g), np.concatenate(dl), np.concatenate(band)
+    # rounding to float may have moved a random point across delta: drop it
+    keep = ~((band == 0) & ~(g > dl)) & ~((band == 1) & (g > dl))
+    g, dl, band = g[keep], dl[keep], band[keep]
+    ref = [_barrier_ref(x, y, t) for x, y in zip(g, dl)]
+    out[f"bar{sfx}.g"], out[f"bar{sfx}.delta"], out[f"bar{sfx}.band"] = g, dl, band
+    out[f"bar{sfx}.in"] = np.array([q[3] for q in ref])
+    # the reference's own results are numbers of type t: hi alone, lo = 0
+    for j, nm in enumerate(("B", "Bz", "Bzz")):
+        out[f"bar{sfx}.{nm}.hi"] = np.array([float(q[j]) for q in ref])
+        out[f"bar{sfx}.{nm}.lo"] = np.zeros(len(ref))
+
+
+def _prim_recip(rng, out, f32):
+    """Reciprocal points: hi is the IEEE quotient 1 / a (correctly rounded by definition, also
+    where it is subnormal, zero, infinite or no number), lo the rest of the exact quotient."""
+    import mpmath as mp
+    t = np.float32 if f32 else np.float64
+    sfx = "32" if f32 else ""
+    e0, e1, mbits = (-124, 124, 23) if f32 else (-1020, 1020, 52)
+    emin_sub, emin, emax = (-149, -126, 128) if f32 else (-1074, -1022, 1024)
+    a, band = [], []
+
+    def add(v, b):
+        v = np.atleast_1d(np.asarray(v, dtype=np.float64))
+        assert (v.astype(t).astype(np.float64) == v).all() or np.isnan(v).any()
+        a.append(v), band.append(np.full(len(v), b, dtype=np.int8))
+
+    def mant(n):
+        return 1 + rng.integers(0, 2 ** mbits, n) / 2.0 ** mbits
+
+    reps = 6 if f32 else 1
+    e = np.repeat(np.arange(e0, e1), reps)
+    add(np.ldexp(mant(len(e)), e), 0)                        # every binade, positive
+    e = np.repeat(np.arange(e0, e1, 1 if f32 else 2), reps)
+    add(-np.ldexp(mant(len(e)), e), 0)                       # and negative
+    e = np.arange(e0, e1 + 1, 1 if f32 else 8)
+    add(np.ldexp(1.0, e), 1), add(-np.ldexp(1.0, e), 1)      # powers of two: exact
+    add([0.0, -0.0, np.inf, -np.inf, np.nan], 2)
+    sub = np.concatenate([np.ldexp(1.0, [emin_sub, emin_sub + 1, emin - 1]),
+                          np.ldexp(np.floor(mant(8) * 2.0 ** 20) / 2.0 ** 20,
+                                   rng.integers(emin_sub + 21, emin, 8)),
+                          [np.ldexp(1.0, emin) - np.ldexp(1.0, emin_sub)]])
+    add(sub, 3), add(-sub, 3)                                # subnormal arguments
+    big = np.concatenate([np.ldexp(mant(6), rng.integers(e1, emax, 6)), np.ldexp(1.0, [e1 + 1, emax - 1]),
+                          [float(np.finfo(t).max)]])
+    add(big, 4), add(-big, 4)                                # |a| > 2^1020: subnormal quotients
+    small = np.ldexp(mant(6), rng.integers(emin, e0, 6))
+    add(small, 5), add(-small, 5)                            # normal arguments below 2^-1020
+    a, band = np.concatenate(a), np.concatenate(band)
+    assert len(a) <= 4096
+    with np.errstate(divide="ignore", over="ignore"):
+        hi = 1.0 / a  # double: exact enough to measure float ulps; the IEEE value in double
+    lo = np.zeros_like(a)
+    for i, v in enumerate(a):
+        if np.isfinite(v) and v != 0 and np.isfinite(hi[i]):
+            q = 1 / mp.mpf(v)
+            lo[i] = float(q - mp.mpf(hi[i]))
+            if abs(hi[i]) >= 2.0 ** -1022:
+                assert float(q) == hi[i]
+    out[f"rcp{sfx}.a"], out[f"rcp{sfx}.band"] = a, band
+    out[f"rcp{sfx}.hi"], out[f"rcp{sfx}.lo"] = hi, lo
+
+
+def make_prim_kat():
+    """prim_kat.npz: arguments and 60-digit references (mpmath) of the hand-written elementary
+    functions -- sin / cos, log, the reciprocals -- each reference a double-double (hi, lo) so
+    that an error can be measured to a fraction of an ulp; and the reduced barrier as the
+    reference computes it, operation by operation, with a correctly rounded log and pow (its
+    results are numbers of the working type: lo = 0).  The keys
+    ending in 32 hold float arguments (and their exact references) for the fp32 build, whose
+    hook rounds its inputs.  "band" names the group a point belongs to (see the code)."""
+    import mpmath as mp
+    mp.mp.dps = PRIM_DIGITS
+    rng = np.random.default_rng(PRIM_SEED)
+    out = {}
+    _prim_sincos(rng, out, "sc", False)
+    _prim_sincos(rng, out, "sc32", True)
+    _prim_log_barrier(rng, out, False)
+    _prim_log_barrier(rng, out, True)
+    _prim_recip(rng, out, False)
+    _prim_recip(rng, out, True)
+    return out
+
+
 SOLVES = {
     # name: (desc factory, batch)
     "c1": (configs.c1_desc, 2),
@@ -184,13 +479,21 @@ def make_edge(name):
 
 
 def main():
+    if sys.argv[1:] == ["prim_kat"]:  # needs mpmath only
+        np.savez_compressed(os.path.join(HERE, "prim_kat.npz"), **make_prim_kat())
+        return
+    if sys.argv[1:] == ["kat_model_wide"]:  # needs oracle/_ref and kat_model.npz
+        np.savez_compressed(os.path.join(HERE, "kat_model_wide.npz"), **make_kat_wide())
+        return
     assert O.available(), "build the oracle and oracle/_ref first (make -C oracle)"
+    np.savez_compressed(os.path.join(HERE, "prim_kat.npz"), **make_prim_kat())
     sys.path.insert(0, os.path.dirname(HERE))
     import _edge_cases as E
     for name in E.CASES:
         np.savez_compressed(os.path.join(HERE, f"edge_{name}.npz"), **make_edge(name))
     np.savez_compressed(os.path.join(HERE, "kat_model.npz"), **make_kat())
     np.savez_compressed(os.path.join(HERE, "kat_model_traj.npz"), **make_kat_traj())
+    np.savez_compressed(os.path.join(HERE, "kat_model_wide.npz"), **make_kat_wide())
     for name in SOLVES:
         np.savez_compressed(os.path.join(HERE, f"solve_{name}.npz"), **make_solve(name))
     # smoke fixture: first 4 problems of C3 (same x0 stream as __graft_entry__.smoke)
