@@ -36,6 +36,8 @@
  *   mhpc_update_problems update_problem of every controller with its own gait and step count
  *   mhpc_reset_problems  set_initial_condition + initialization() of single controllers of the
  *                        fleet (MHPCLocomotion.cpp:47-53): the listed problems only
+ *   mhpc_copy_problems   copy construction / assignment of a controller object (every member of
+ *                        MHPCLocomotion and its MultiPhaseDDP): problems copied between slots
  *   mhpc_set_commands    MHPCUserParameters::usrcmd of every controller (vel, height), which
  *                        build_problem / update_problem hand to ReferenceGen
  *                        (MHPCLocomotion.cpp:98-103): per-problem user commands in one batch;
@@ -239,6 +241,45 @@ int mhpc_update_problems(mhpc_handle* h, int n_gaits, const mhpc_gait* gaits,
  *  - Device work is proportional to n, not to the batch. */
 int mhpc_reset_problems(mhpc_handle* h, int n, const int32_t* problems, const double* x0,
                         int n_desc, const mhpc_problem_desc* descs, const int32_t* desc_of);
+/* ---- copies of live problems: a slot becomes another controller, warm start and all -------
+ * In the reference a controller is an object and copying it is copying the object.  Here dst
+ * problem dst_problems[i] becomes a copy of src problem src_problems[i], i < n, as the source
+ * stands at this call; dst == src copies inside one handle.  ms optional: device time of the copy
+ * launch (HIP events), as mhpc_rollout_costs reports its own.
+ *  - What travels: the nominal trajectory and every line-search slot, K / du / G, the partials
+ *    records and impact Jacobians, the solver state (status, trace, counters, AL / ReB values, the
+ *    option values a solve rewrites), the x0 row on the device, the position references, the
+ *    layout with its phase-buffer rotation and gait point, the problem's rows of the phase-buffer
+ *    store -- and, unlike mhpc_reset_problems, the command and the parameter set: a clone that kept
+ *    the destination's would not be a clone (the source's set joins dst's sets under
+ *    mhpc_set_param_sets' merge rules; change either afterwards with the setters).  After the call
+ *    every getter reports for the destination what it reports for the source, and every later
+ *    mhpc_solve / mhpc_update_problem(s) / mhpc_advance_x0 of the destination equals the source's
+ *    under the same inputs, bit for bit, in both precisions (tests/test_gpu_copy.py).
+ *  - Every unlisted problem of dst and every problem of src keeps its device state bit for bit.
+ *    The copy never re-strides or reallocates dst's packed arrays: it copies the knots below the
+ *    smaller of the two knot strides and leaves the rest of dst's stride as a reset leaves it.  If
+ *    src has a phase-buffer store and dst none, dst gets its own (zeroed, as at its first
+ *    mhpc_update_problem[s]) and then the rows; if dst has one and src none, the destination
+ *    problems' rows are zeroed.
+ *  - MHPC_ERR_INVALID, before anything changes: a null pointer; n < 1 or n > dst's batch; a
+ *    problem number out of range; a destination listed twice (a source may repeat: one to many);
+ *    with dst == src a number that is both a source and a destination; handles of different
+ *    precision, device, mhpc_hsddp_option (every field) or backward-sweep arithmetic
+ *    (MHPC_VARIANT_SWEEP_BITS 32 on one side only: the one kernel variant that changes results;
+ *    every other variant computes the same bits and may differ); a source layout with more knots than
+ *    dst's knot stride or -- once dst's store exists -- more phases or a longer phase than it holds;
+ *    x0 rows of different width (14 vs 6); more than MHPC_MAX_LAYOUTS (layout, set) groups.
+ *  - MHPC_ERR_STATE: either handle before mhpc_initialize, or with commands, constraint parameters
+ *    or parameter sets pending, or the two handles at different points of the call order (one just
+ *    solved, the other just initialized or updated).  A pending x0 is allowed: the device's current
+ *    row is what is copied.  The call-order state of both handles stays as it is.
+ *  - MHPC_ERR_DEVICE: a failure before the copy launch is queued (allocating dst's store,
+ *    uploading the lists) leaves both handles as they were; a failed launch leaves the destination
+ *    problems undefined, as a failed mhpc_reset_problems does (reset or copy them again).
+ *  - Device work is proportional to n, not to either batch. */
+int mhpc_copy_problems(mhpc_handle* dst, const int32_t* dst_problems, mhpc_handle* src,
+                       const int32_t* src_problems, int n, float* ms);
 /* ---- per-problem user commands: the batch axis over speed / height commands -----------
  * Per-problem user command (the reference's MHPCUserParameters::usrcmd of each controller,
  * MHPCLocomotion.cpp:98-103).  vel, height: host arrays [batch]; either may be NULL = unchanged.

@@ -325,6 +325,31 @@ class MHPCLocomotion {
       std::copy(x0.begin() + i * xw_, x0.begin() + (i + 1) * xw_, x0_.begin() + (size_t)pr[i] * xw_);
     refresh_descs();
   }
+  // extension: copying controller objects -- problem dst_problems[i] of this fleet becomes a copy
+  // of problem src_problems[i] of `src` (nullptr: of this fleet) as it stands: warm start, solver
+  // state, x0 row, command, parameter set, layout and phase buffers.  A source may repeat (one
+  // robot forks into several candidates); every other problem keeps its state bit for bit.
+  // Returns the device time of the copy in ms.
+  float copy_problems(const std::vector<int>& dst_problems, const std::vector<int>& src_problems,
+                      MHPCLocomotion* src = nullptr) {
+    if (dst_problems.size() != src_problems.size())
+      throw std::runtime_error("copy_problems: one source problem per destination problem");
+    if (!src) src = this;
+    const std::vector<int32_t> dp(dst_problems.begin(), dst_problems.end());
+    const std::vector<int32_t> sp(src_problems.begin(), src_problems.end());
+    float ms = 0;
+    check(mhpc_copy_problems(h_, dp.data(), src->h_, sp.data(), (int)dp.size(), &ms),
+          "mhpc_copy_problems");
+    const std::vector<double> rows = get_x0();  // what update_problem(s) hands back
+    status_.resize(batch_, 0);
+    for (size_t i = 0; i < dp.size(); ++i) {
+      std::copy(rows.begin() + (size_t)dp[i] * xw_, rows.begin() + (size_t)(dp[i] + 1) * xw_,
+                x0_.begin() + (size_t)dp[i] * xw_);
+      status_[dp[i]] = (size_t)sp[i] < src->status_.size() ? src->status_[sp[i]] : 0;
+    }
+    refresh_descs();
+    return ms;
+  }
   // problems whose last solve did not end MHPC_SOLVE_OK or left a non-finite cost
   std::vector<int> lost_problems() {
     std::vector<double> J(batch_);

@@ -206,6 +206,8 @@ SIGNATURES = [
                                              ctypes.POINTER(ProblemDesc)]),
     ("mhpc_reset_problems", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _IP, _DP, ctypes.c_int,
                                            ctypes.POINTER(ProblemDesc), _IP]),
+    ("mhpc_copy_problems", ctypes.c_int, [ctypes.c_void_p, _IP, ctypes.c_void_p, _IP, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_float)]),
     ("mhpc_set_commands", ctypes.c_int, [ctypes.c_void_p, _DP, _DP]),
     ("mhpc_get_commands", ctypes.c_int, [ctypes.c_void_p, _DP, _DP]),
     ("mhpc_get_reference_problems", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,

@@ -28,6 +28,8 @@ int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const in
 int api_set_layouts(Handle* h, int n_desc, const mhpc_problem_desc* descs, const int32_t* lop);
 int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* x0, int n_desc,
                        const mhpc_problem_desc* descs, const int32_t* desc_of);
+int api_copy_problems(Handle* dst, const int32_t* dst_problems, Handle* src,
+                      const int32_t* src_problems, int n, float* ms);
 int api_get_problem_desc(Handle* h, int b, mhpc_problem_desc* desc);
 int api_set_commands(Handle* h, const double* vel, const double* height);
 int api_get_commands(Handle* h, double* vel, double* height);

@@ -165,6 +165,27 @@ extern "C" int mhpc_reset_problems(mhpc_handle* h, int n, const int32_t* problem
                                    const int32_t* desc_of) {
   FWD(reset_problems, n, problems, x0, n_desc, descs, desc_of);
 }
+// Two handles: both must be instantiations of the same arithmetic type.
+extern "C" int mhpc_copy_problems(mhpc_handle* dst, const int32_t* dst_problems, mhpc_handle* src,
+                                  const int32_t* src_problems, int n, float* ms) {
+  if (!dst || !src) {
+    mhpc_g_err = "null handle";
+    return MHPC_ERR_INVALID;
+  }
+  if (dst->precision != src->precision) {
+    mhpc_g_err = "the handles' precisions differ";
+    return MHPC_ERR_INVALID;
+  }
+  try {
+    return dst->precision == 32
+               ? mhpc32::api_copy_problems((mhpc32::Handle*)dst->impl, dst_problems,
+                                           (mhpc32::Handle*)src->impl, src_problems, n, ms)
+               : mhpc::api_copy_problems((mhpc::Handle*)dst->impl, dst_problems,
+                                         (mhpc::Handle*)src->impl, src_problems, n, ms);
+  } catch (...) {
+    return fail_exception("mhpc_copy_problems");
+  }
+}
 extern "C" int mhpc_get_problem_desc(mhpc_handle* h, int problem, mhpc_problem_desc* desc) {
   FWD(get_problem_desc, problem, desc);
 }

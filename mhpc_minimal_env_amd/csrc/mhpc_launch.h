@@ -70,6 +70,20 @@ int eval_prim_group(int fn);
 hipError_t launch_eval_prim(int fn, int n, const real* a, const real* b, real* out,
                             hipStream_t s);
 
+// ---- mhpc_copy.hip --------------------------------------------------------------------------
+// One side of mhpc_copy_problems: a handle's arrays with their knot stride and the shape of its
+// phase-buffer store (store == nullptr: the handle has none).  pairs [n][2] on the device: source
+// problem, destination problem; blocks [nblk]: the (run, chunk) table of one pair, which
+// copy_block_table writes (out may be null) and counts; the re-stride map is mhpc_copy_map.h.
+struct CopySide {
+  DevBufs d;
+  real* store;
+  int NK, nslot, nbk, spmax;
+};
+int copy_block_table(const CopySide& src, const CopySide& dst, int* out);
+hipError_t launch_copy_problems(const CopySide& src, const CopySide& dst, int n, const int* pairs,
+                                int nblk, const int* blocks, hipStream_t s);
+
 // ---- mhpc_bws.hip ---------------------------------------------------------------------------
 hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, real update_reg, int part,
                       hipStream_t s);

@@ -1832,6 +1832,158 @@ int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* 
   return collect_profile(h);
 }
 
+// ---- copies of live problems (mhpc_copy_problems) -------------------------------------------
+// The handle-wide options, field by field: the line-search grid, nslot and the thresholds of the
+// solve's state machine are the handle's, so a problem only continues alike under equal ones.
+static bool same_option(const mhpc_hsddp_option& a, const mhpc_hsddp_option& b) {
+  return a.alpha == b.alpha && a.gamma == b.gamma && a.update_penalty == b.update_penalty &&
+         a.update_relax == b.update_relax && a.update_regularization == b.update_regularization &&
+         a.update_ReB == b.update_ReB && a.max_DDP_iter == b.max_DDP_iter &&
+         a.max_AL_iter == b.max_AL_iter && a.DDP_thresh == b.DDP_thresh &&
+         a.AL_thresh == b.AL_thresh && a.AL_active == b.AL_active && a.ReB_active == b.ReB_active &&
+         a.smooth_active == b.smooth_active;
+}
+static CopySide copy_side(const Handle* h) {
+  return CopySide{h->d, h->store_valid ? h->store : nullptr, h->sp.NK, h->sp.nslot, h->nbk, h->spmax};
+}
+
+// In the reference a controller is an object and a copy of it is a copy of the object: the
+// destination problems become the source problems as they stand -- nominal and trial slots,
+// K / du / G, partials, impact Jacobians, solver state, x0 row, references, command, parameter set,
+// layout with its buffer rotation, gait point, phase-buffer rows -- inside one handle or between
+// two of one device.  Like mhpc_reset_problems it never re-strides or reallocates the
+// destination's packed arrays and leaves every other problem's records where they are; everything
+// that can refuse the call is checked before anything changes (a device error, unlike a refusal, can
+// leave the destination problems undefined, as for a reset).  The device part is one list-driven
+// launch (mhpc_copy.hip) on the destination's stream, after an event on the source's; both
+// streams are idle when the call returns.
+int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp_, int n, float* ms) {
+  if (!d || !s || !dp || !sp_) return fail(MHPC_ERR_INVALID, "null argument");
+  const int Bd = d->sp.B, Bs = s->sp.B;
+  if (n < 1 || n > Bd) return fail(MHPC_ERR_INVALID, "n must be 1..batch of the destination");
+  std::vector<char> is_dst(Bd, 0);
+  for (int i = 0; i < n; ++i) {
+    if (dp[i] < 0 || dp[i] >= Bd || sp_[i] < 0 || sp_[i] >= Bs)
+      return fail(MHPC_ERR_INVALID, "problem out of range");
+    if (is_dst[dp[i]]) return fail(MHPC_ERR_INVALID, "destination problem listed twice");
+    is_dst[dp[i]] = 1;
+  }
+  for (int i = 0; d == s && i < n; ++i)
+    if (is_dst[sp_[i]])
+      return fail(MHPC_ERR_INVALID, "a problem is both a source and a destination");
+  if (d->device != s->device) return fail(MHPC_ERR_INVALID, "the handles are on different devices");
+  if (!same_option(d->opt, s->opt) || d->sp.nslot != s->sp.nslot)
+    return fail(MHPC_ERR_INVALID, "the handles' mhpc_hsddp_option differ");
+  // the one kernel variant that changes results: the sweep's arithmetic (0 and 64 are both double)
+  if ((d->sweep_bits == 32) != (s->sweep_bits == 32))
+    return fail(MHPC_ERR_INVALID, "the handles' backward-sweep arithmetic (MHPC_VARIANT_SWEEP_BITS) differs");
+  // the destination's arrays stay as they are: every source layout must fit them
+  const int r = x0_row(d);
+  if (x0_row(s) != r) return fail(MHPC_ERR_INVALID, "the handles' x0 row widths differ");
+  std::vector<ProbLayout> npl = d->pl;
+  std::vector<CostParams> nsets = d->psets;
+  std::vector<int> nof = d->pset_of;
+  for (int i = 0; i < n; ++i) {
+    const ProbLayout& q = s->pl[sp_[i]];
+    const int P = q.desc.n_wb + q.desc.n_fb;
+    int NK = 0;
+    for (int p = 0; p < P; ++p) {
+      NK += q.desc.N[p];
+      if (d->store_valid && q.desc.N[p] > d->nbk)
+        return fail(MHPC_ERR_INVALID, "phase longer than the destination's phase buffers");
+    }
+    if (NK > d->sp.NK)
+      return fail(MHPC_ERR_INVALID,
+                  "source layout longer than the destination's knot stride (a copy never grows the arrays)");
+    if (d->store_valid && P > d->spmax)
+      return fail(MHPC_ERR_INVALID, "more phases than the destination's phase-buffer store holds");
+    npl[dp[i]] = q;
+    nof[dp[i]] = (int)nsets.size();  // the source's set, merged below with the ones it equals
+    nsets.push_back(s->psets[s->pset_of[sp_[i]]]);
+  }
+  bool any_wb = false;
+  for (const ProbLayout& q : npl) any_wb = any_wb || q.desc.n_wb > 0;
+  if ((any_wb ? 14 : 6) != r) return fail(MHPC_ERR_INVALID, "the x0 row width would change");
+  if (!d->initialized || !s->initialized)
+    return fail(MHPC_ERR_STATE, "mhpc_initialize must precede mhpc_copy_problems");
+  for (const Handle* h : {d, s})
+    if (h->cmd_changed || h->params_changed || h->sets_changed)
+      return fail(MHPC_ERR_STATE,
+                  "commands or parameters pending: call mhpc_initialize or mhpc_update_problem first");
+  if (d->need_full != s->need_full || d->solved != s->solved)
+    return fail(MHPC_ERR_STATE, "the handles are at different points of the call order");
+  merge_sets(nsets, nof);
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(hipStreamSynchronize(d->stream));
+  d->pl.swap(npl);
+  d->psets.swap(nsets);
+  d->pset_of.swap(nof);
+  // Until the launch is queued the destination can go back to what it was: its host layouts and
+  // sets are swapped in, the groups rebuilt, its store created, the lists uploaded -- and on any
+  // failure swapped out again.  The per-problem host entries change only after that.
+  auto undo = [&]() {
+    d->pl.swap(npl);
+    d->psets.swap(nsets);
+    d->pset_of.swap(nof);
+  };
+  int rc = rebuild_groups(d, true);
+  if (rc) {  // too many groups: nothing changed but these three
+    undo();
+    return rc;
+  }
+  // a source with phase buffers gives the destination its own, as its first update would (an
+  // empty store of the new layouts' shape, which the old layouts fit as well)
+  if (s->store_valid && (rc = ensure_store(d))) {
+    undo();
+    (void)rebuild_groups(d, true);
+    return rc;
+  }
+  // the pair list and, behind it, the (run, chunk) table of one pair: one upload
+  const CopySide cs = copy_side(s), cd = copy_side(d);
+  const int nblk = copy_block_table(cs, cd, nullptr);
+  std::vector<int> pairs(2 * (size_t)n + nblk);
+  for (int i = 0; i < n; ++i) {
+    pairs[2 * (size_t)i] = sp_[i];
+    pairs[2 * (size_t)i + 1] = dp[i];
+  }
+  copy_block_table(cs, cd, pairs.data() + 2 * (size_t)n);
+  DevTemp<int> t(d->stream);
+  const int* dpairs = t.in(std::move(pairs));
+  if (t.e == hipSuccess && s != d) {
+    t.e = hipEventRecord(s->evfork, s->stream);
+    if (t.e == hipSuccess) t.e = hipStreamWaitEvent(d->stream, s->evfork, 0);
+  }
+  if (t.e == hipSuccess) t.e = hipEventRecord(d->ev0, d->stream);
+  if (t.e != hipSuccess) {  // nothing of the copy is queued yet
+    (void)hipStreamSynchronize(d->stream);
+    undo();
+    (void)rebuild_groups(d, true);
+    return dev_fail("mhpc_copy_problems", t.e);
+  }
+  // (d == s reads its own entries: a source is no destination, so they are the old ones)
+  for (int i = 0; i < n; ++i) {
+    const int a = sp_[i], b = dp[i];
+    d->cmode[b] = s->cmode[a];
+    d->cmd[2 * (size_t)b] = s->cmd[2 * (size_t)a];
+    d->cmd[2 * (size_t)b + 1] = s->cmd[2 * (size_t)a + 1];
+    d->nfresh += (s->fresh[a] ? 1 : 0) - (d->fresh[b] ? 1 : 0);
+    d->fresh[b] = s->fresh[a];
+  }
+  t.e = launch_copy_problems(cs, cd, n, dpairs, nblk, dpairs + 2 * (size_t)n, d->stream);
+  if (t.e == hipSuccess) t.e = hipEventRecord(d->ev1, d->stream);
+  if (t.e == hipSuccess) t.e = hipStreamSynchronize(d->stream);
+  float el = 0;
+  if (t.e == hipSuccess) t.e = hipEventElapsedTime(&el, d->ev0, d->ev1);
+  if (t.e != hipSuccess) {
+    // a failed launch: the destination problems are undefined (as after a failed reset); nothing
+    // of the handle's may stay queued behind it
+    (void)hipStreamSynchronize(d->stream);
+    return dev_fail("mhpc_copy_problems", t.e);
+  }
+  if (ms) *ms = el;
+  return MHPC_OK;
+}
+
 int api_get_problem_desc(Handle* h, int b, mhpc_problem_desc* desc) {
   if (!h || !desc) return fail(MHPC_ERR_INVALID, "null argument");
   if (b < 0 || b >= h->sp.B) return fail(MHPC_ERR_INVALID, "problem out of range");

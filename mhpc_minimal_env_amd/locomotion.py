@@ -371,6 +371,33 @@ class MHPCLocomotion:
         if descs is not None:
             self._refresh_descs()
 
+    # -- copies of live problems: a slot becomes another controller ---------------------------
+    def copy_problems(self, dst_problems, src_problems, src: Optional["MHPCLocomotion"] = None) -> float:
+        """mhpc_copy_problems: problem dst_problems[i] of this handle becomes a copy of problem
+        src_problems[i] of `src` (None: of this handle) as it stands -- warm start, solver state,
+        x0 row, command, parameter set, layout and phase buffers (copying a controller object in
+        the reference).  A source may repeat (one robot forks into several candidates).  Every
+        other problem of both handles keeps its state bit for bit.  Returns the device time of
+        the copy in ms; change the clones' commands / parameter sets / x0 afterwards with the
+        setters."""
+        import ctypes
+        src = self if src is None else src
+        dp = np.ascontiguousarray(dst_problems, dtype=np.int32).reshape(-1)
+        sp = np.ascontiguousarray(src_problems, dtype=np.int32).reshape(-1)
+        if dp.shape != sp.shape:
+            raise ValueError("one source problem per destination problem")
+        ms = ctypes.c_float(0.0)
+        capi.check(capi.lib().mhpc_copy_problems(self._h, capi.iptr(dp), src._h, capi.iptr(sp),
+                                                 int(dp.size), ctypes.byref(ms)),
+                   "mhpc_copy_problems")
+        # the host mirrors follow: the rows update_problem(s) hands back to the device are the
+        # device's own, the last solve's status is the source's, descriptors and commands travel
+        self._x0 = self._x0.copy()
+        self._x0[dp] = self.get_x0()[dp]
+        self.status[dp] = src.status[sp]
+        self._refresh_descs()
+        return float(ms.value)
+
     def lost_problems(self) -> np.ndarray:
         """Problems whose last solve did not end MHPC_SOLVE_OK or left a non-finite cost."""
         J = self.get_scalars()["J"]

@@ -1,4 +1,4 @@
-"""Build gate: the solve's hot kernels keep everything in registers / LDS -- no private
+"""Build gate: the solve's hot kernels and the problem copy keep everything in registers / LDS -- no private
 (scratch) memory.  A scratch load or store uses the VM counter, and on gfx950's single
 in-order counter a wait for it also waits for every global store issued before it (the
 line search's record stores: a per-lane index into the kernel parameter block once made the
@@ -11,7 +11,7 @@ usage: python tools/check_no_scratch.py <file.s> [...]    exit 1 on any hit
 import re
 import sys
 
-HOT = ("k_rollout", "k_bws", "k_partials", "k_init", "k_cost", "k_al_end")
+HOT = ("k_rollout", "k_bws", "k_partials", "k_init", "k_cost", "k_al_end", "k_copy_problems")
 COLD = ("k_cost_grad",)  # debug-info kernel (print_debugInfo), not in the solve
 
 
