@@ -1,0 +1,375 @@
+// The host-side plan of a batch: per-problem layouts and parameter sets -> the groups the kernels
+// run over.  Everything a per-problem change (layouts, gait steps, parameter sets, resets, copies)
+// has to decide before it touches the device is here, as plain C++ with no HIP call and no
+// handle: the descriptor checks, the gait step of one problem, the checks that a layout fits the
+// arrays as they are, the merge of equal parameter sets, and plan_groups, which turns
+// (layout, set) of every problem into a GroupPlan.  The runtime (mhpc_runtime.cpp) validates,
+// plans, and only then commits a plan to the handle and the device (commit_groups); the host check
+// (tests/native/plan_hostcheck.cpp) compiles this header with plain g++.
+//
+// A function that can refuse returns MHPC_ERR_INVALID and sets *msg (a literal); it changes
+// nothing it was given unless its comment says otherwise.
+#pragma once
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <map>
+#include <numeric>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "mhpc_solver.h"
+
+namespace MHPC_NS {
+
+// Per-problem phase layout: the descriptor (gait point) and the phase-buffer rotation of the
+// receding-horizon loop (MHPCLocomotion::update_problem rotates pidx_WB / pidx_FB by one per
+// call, MHPCLocomotion.cpp:111-121: after r calls phase i uses buffer (i + r) mod n).
+struct ProbLayout {
+  mhpc_problem_desc desc;
+  int rot_wb, rot_fb;
+};
+// Algorithmic bytes per problem of one layout
+struct ByteModel {
+  double roll_read = 0, roll_write = 0, roll_term = 0, par = 0, init = 0, cost = 0;
+  double roll_flops = 0;  // one trial rollout (the line search's flop model)
+};
+
+inline int plan_refuse(const char** msg, const char* text) {
+  if (msg) *msg = text;
+  return MHPC_ERR_INVALID;
+}
+
+// ---- descriptors ----------------------------------------------------------------------------
+inline int check_desc(const mhpc_problem_desc* d, const char** msg) {
+  if (!d) return plan_refuse(msg, "null descriptor");
+  const int P = d->n_wb + d->n_fb;
+  if (d->n_wb < 0 || d->n_fb < 0 || P < 1 || P > MHPC_MAX_PHASES)
+    return plan_refuse(msg, "phase count out of range");
+  if (d->precision != 64 && d->precision != 32) return plan_refuse(msg, "precision must be 64 or 32");
+  int NK = 0;
+  for (int p = 0; p < P; ++p) {
+    if (d->mode_seq[p] < 1 || d->mode_seq[p] > 4) return plan_refuse(msg, "mode out of range");
+    if (d->N[p] < 2) return plan_refuse(msg, "each phase needs N >= 2");
+    NK += d->N[p];
+  }
+  if (NK > MHPC_MAX_KNOTS) return plan_refuse(msg, "too many knots");
+  if (!(d->dt_wb > 0) || !(d->dt_fb > 0)) return plan_refuse(msg, "dt must be positive");
+  return MHPC_OK;
+}
+// A descriptor given for some problems of a live handle (mhpc_set_layouts, mhpc_reset_problems):
+// valid, and with the precision and the command of the handle's own descriptor.
+inline int check_layout_desc(const mhpc_problem_desc& d, const mhpc_problem_desc& handle_desc,
+                             const char** msg) {
+  if (int rc = check_desc(&d, msg)) return rc;
+  if (d.precision != handle_desc.precision)
+    return plan_refuse(msg, "a layout's precision differs from the handle's");
+  if (d.vel_cmd != handle_desc.vel_cmd || d.height_cmd != handle_desc.height_cmd)
+    return plan_refuse(msg, "a layout's vel_cmd / height_cmd differs from the handle's");
+  return MHPC_OK;
+}
+
+// A descriptor normalised for comparison (entries past its phases and reserved fields zero)
+inline mhpc_problem_desc norm_desc(const mhpc_problem_desc& in) {
+  mhpc_problem_desc d;
+  memset(&d, 0, sizeof d);
+  d.n_wb = in.n_wb;
+  d.n_fb = in.n_fb;
+  for (int p = 0; p < in.n_wb + in.n_fb; ++p) {
+    d.mode_seq[p] = in.mode_seq[p];
+    d.N[p] = in.N[p];
+  }
+  d.dt_wb = in.dt_wb;
+  d.dt_fb = in.dt_fb;
+  d.vel_cmd = in.vel_cmd;
+  d.height_cmd = in.height_cmd;
+  d.precision = in.precision;
+  return d;
+}
+
+// Phase layout of a descriptor: modes, knot counts and offsets, partials work items, and the
+// phase buffers after rot_wb / rot_fb rotations (MHPCLocomotion::update_problem).
+inline void build_layout(Layout& L, const mhpc_problem_desc& desc, int rot_wb, int rot_fb) {
+  memset(&L, 0, sizeof L);
+  L.P = desc.n_wb + desc.n_fb;
+  L.n_wb = desc.n_wb;
+  int ko = 0, items = 0, items_v = 0;
+  for (int p = 0; p < L.P; ++p) {
+    const bool wb = p < desc.n_wb;
+    L.mode[p] = desc.mode_seq[p];
+    L.N[p] = desc.N[p];
+    L.ko[p] = ko;
+    L.xs[p] = wb ? 14 : 6;
+    L.dt[p] = wb ? desc.dt_wb : desc.dt_fb;
+    L.buf[p] = wb ? (p + rot_wb) % desc.n_wb : desc.n_wb + (p - desc.n_wb + rot_fb) % desc.n_fb;
+    ko += desc.N[p];
+    L.par_knot_off[p] = items;
+    L.par_imp_off[p] = items_v;
+    if (wb) {
+      items += desc.N[p] - 1;
+      items_v += (L.mode[p] == 2 || L.mode[p] == 4) ? 14 : 0;
+    }
+  }
+  for (int p = L.P; p <= MAXP; ++p) {
+    L.par_knot_off[p] = items;
+    L.par_imp_off[p] = items_v;
+  }
+  L.par_knots = items;
+  L.par_imp = items_v;
+  L.NK = ko;
+}
+
+// ---- the byte model -------------------------------------------------------------------------
+// Algorithmic HBM bytes of one problem for each kernel's unit of work.
+constexpr double kB = sizeof(real);  // bytes per element of the solve's arithmetic type
+
+// Line-search flop model per trial knot (SURVEY.md 8d secondary roofline): the reference's
+// dynamics in CasADi's generated-code assignment counts (Dyn_BS / Dyn_FS 2301,
+// Dyn_FL 1441, FBDynamics 44 -- scalar operations incl. loads, so an upper estimate), plus the
+// feedback u = u_nom + eps du + K (x - x_nom) and the Euler step (WB: 14 + 4 * 28 + 8 + 28;
+// SRB: 6 + 4 * 12 + 8 + 12).  The running costs (the second wave) are not counted.
+inline double ro_knot_flops(int mode, bool wb) {
+  if (!wb) return 44 + 74;
+  return (mode == 1 || mode == 3 ? 2301.0 : 1441.0) + 162;
+}
+
+inline ByteModel byte_model(const Layout& L) {
+  ByteModel m;
+  double rr = 14 * 8, rw = 0, rt = 0, pb = 0, ib = L.NK * kB, cb = 0;
+  for (int p = 0; p < L.P; ++p) {
+    const bool wb = p < L.n_wb;
+    const int n = wb ? 14 : 6, N = L.N[p];
+    // nominal x,u (n+4) + K (4n) + du (4) read once per problem (the candidates of a
+    // problem share them)
+    rr += (N - 1) * kB * ((n + 4) + 4 * n + 4);
+    // a storing candidate writes x,u,y of every knot, every candidate x at the last knot
+    rw += (N - 1) * kB * (n + 8);
+    rt += n * kB;
+    m.roll_flops += (N - 1) * ro_knot_flops(L.mode[p], wb);
+    // k_cost: nominal x,u(,y) of every knot + refpos
+    cb += (N - 1) * kB * (n + 4 + (wb ? 4 : 0) + 1) + kB * (n + 1);
+    // k_init: x,u,y written for every knot (WB and SRB)
+    if (!wb) ib += N * kB * 14;
+    if (wb) {
+      const bool imp = L.mode[p] == 2 || L.mode[p] == 4;
+      // x,u read; the record written without its four zero columns (written once at create)
+      pb += (N - 1) * kB * (18 + PS - 4 * 9) + (imp ? kB * (14 + 196) : 0.0);
+      ib += N * kB * 22;
+    }
+  }
+  m.roll_read = rr;
+  m.roll_write = rw;
+  m.roll_term = rt;
+  m.par = pb;
+  m.init = ib;
+  m.cost = cb;
+  return m;
+}
+
+// ---- parameter sets -------------------------------------------------------------------------
+// Parameter sets compare by value, entry by entry (CostParams holds nothing but reals).
+inline bool same_params(const CostParams& a, const CostParams& b) {
+  const real *x = (const real*)&a, *y = (const real*)&b;
+  for (size_t i = 0; i < sizeof(CostParams) / sizeof(real); ++i)
+    if (!(x[i] == y[i])) return false;
+  return true;
+}
+// Merge the sets that compare equal and drop the ones no problem uses (first occurrence
+// kept, order preserved); `of` is renumbered accordingly.
+inline void merge_sets(std::vector<CostParams>& sets, std::vector<int>& of) {
+  std::vector<int> to(sets.size(), -1);
+  std::vector<char> used(sets.size(), 0);
+  for (int s : of) used[s] = 1;
+  std::vector<CostParams> out;
+  for (size_t i = 0; i < sets.size(); ++i) {
+    if (!used[i]) continue;
+    for (size_t j = 0; j < out.size() && to[i] < 0; ++j)
+      if (same_params(out[j], sets[i])) to[i] = (int)j;
+    if (to[i] < 0) {
+      to[i] = (int)out.size();
+      out.push_back(sets[i]);
+    }
+  }
+  for (int& s : of) s = to[s];
+  sets.swap(out);
+}
+
+// ---- a layout against the arrays as they are (mhpc_reset_problems, mhpc_copy_problems) --------
+// Neither call re-strides or reallocates: the layout must fit the knot stride NK and, when the
+// phase-buffer store is live (store_valid), its buffers of nbk knots and its spmax buffers a
+// problem.  copy: the wording of mhpc_copy_problems, whose arrays are the destination's.
+inline int fits_arrays(const ProbLayout& q, int NK, bool store_valid, int nbk, int spmax, bool copy,
+                       const char** msg) {
+  const int P = q.desc.n_wb + q.desc.n_fb;
+  int nk = 0;
+  for (int p = 0; p < P; ++p) {
+    nk += q.desc.N[p];
+    if (store_valid && q.desc.N[p] > nbk)
+      return plan_refuse(msg, copy ? "phase longer than the destination's phase buffers"
+                                   : "phase longer than the phase buffers");
+  }
+  if (nk > NK)
+    return plan_refuse(
+        msg, copy ? "source layout longer than the destination's knot stride (a copy never grows the arrays)"
+                  : "layout longer than the knot stride (a reset never grows the arrays)");
+  if (store_valid && P > spmax)
+    return plan_refuse(msg, copy ? "more phases than the destination's phase-buffer store holds"
+                                 : "more phases than the phase-buffer store holds");
+  return MHPC_OK;
+}
+// Width of the caller's x0 rows: 14 once any problem has a whole-body phase, else 6.
+inline int x0_row_of(const std::vector<ProbLayout>& pl) {
+  for (const ProbLayout& q : pl)
+    if (q.desc.n_wb > 0) return 14;
+  return 6;
+}
+
+// ---- one problem's gait steps (mhpc_update_problems) ------------------------------------------
+// MHPCLocomotion::update_problem's host part, `steps` times: advance the gait by one mode, recompute
+// mode sequence and knot counts (Gait::get_next_mode / get_mode_seq / get_timings, Gait.h:48-77),
+// rotate the WB and SRB phase buffers by one.  nbk: knots of a phase buffer.  q and cmode are the
+// caller's working copies: a refusal leaves them partly advanced.
+inline int advance_gait(ProbLayout& q, int& cmode, const mhpc_gait& gait, int steps, int nbk,
+                        const char** msg) {
+  auto next_mode = [&](int m) {
+    for (int i = 0; i < gait.n_modes; ++i)
+      if (gait.modes[i] == m) return gait.modes[(i + 1) % gait.n_modes];
+    return -1;  // the reference falls off the end of a non-void function here
+  };
+  mhpc_problem_desc& nd = q.desc;
+  const int P = nd.n_wb + nd.n_fb;
+  for (int step = 0; step < steps; ++step) {
+    const int cm = next_mode(cmode);
+    if (cm < 0) return plan_refuse(msg, "current mode is not in the gait");
+    cmode = cm;
+    nd.mode_seq[0] = cm;
+    for (int p = 1; p < P; ++p) nd.mode_seq[p] = next_mode(nd.mode_seq[p - 1]);
+    int NK = 0;
+    for (int p = 0; p < P; ++p) {
+      const float tm = gait.timings[nd.mode_seq[p] - 1];
+      const double dt = p < nd.n_wb ? nd.dt_wb : nd.dt_fb;
+      nd.N[p] = (int)round((double)tm / dt);  // round(float timing / (double) dt)
+      if (nd.N[p] < 2) return plan_refuse(msg, "gait timing gives a phase with N < 2");
+      if (nd.N[p] > nbk) return plan_refuse(msg, "phase longer than the phase buffers");
+      NK += nd.N[p];
+    }
+    if (NK > MHPC_MAX_KNOTS) return plan_refuse(msg, "too many knots");
+    // pidx_WB / pidx_FB: front -> back (MHPCLocomotion.cpp:111-121); kept reduced, so a
+    // long receding-horizon loop never overflows the count
+    q.rot_wb = (q.rot_wb + 1) % std::max(nd.n_wb, 1);
+    q.rot_fb = (q.rot_fb + 1) % std::max(nd.n_fb, 1);
+  }
+  return MHPC_OK;
+}
+
+// ---- groups ---------------------------------------------------------------------------------
+// The groups of a batch: the distinct (layout, set) pairs in use, where a layout is a
+// (descriptor, buffer rotation) pair; longest layout first (its blocks head every launch: the
+// long blocks start first in a mixed batch), layouts of equal length in the order of their first
+// problem, then by set, the problems of each group in batch order.  Group g has its own Layout
+// record (a layout that several sets share is stored once per group, so lays[lid[b]] stays
+// problem b's layout).
+struct GroupPlan {
+  std::vector<Layout> lays;              // [ngrp] each group's layout
+  std::vector<mhpc_problem_desc> ldesc;  // [ngrp] its normalised descriptor
+  std::vector<ByteModel> bym;            // [ngrp] its byte model
+  std::vector<int> gset;                 // [ngrp] each group's parameter set
+  std::vector<int> lid, gidx;            // [B] each problem's group; the problems grouped
+  int nlay = 0;                          // distinct layouts (ngrp counts (layout, set) pairs)
+  int NK = 0;                            // knots of the longest layout
+  // the grouping's fields of SolveParams, under their names there
+  int ngrp = 0, ident = 1, pmax = 0, split_ok = 0, stage_fits = 1;
+  int go[MAXL + 1] = {}, gpk[MAXL] = {}, gpi[MAXL] = {};
+
+  void to_params(SolveParams& sp) const {  // (sp.NK is the arrays' stride: not the plan's to set)
+    sp.ngrp = ngrp;
+    sp.ident = ident;
+    sp.pmax = pmax;
+    sp.split_ok = split_ok;
+    sp.stage_fits = stage_fits;
+    std::copy(go, go + MAXL + 1, sp.go);
+    std::copy(gpk, gpk + MAXL, sp.gpk);
+    std::copy(gpi, gpi + MAXL, sp.gpi);
+  }
+};
+
+// pl [B], pset_of [B] -> out.  Refused, with out as it was, for more than MAXL distinct layouts or
+// more than MAXL (layout, set) pairs.
+inline int plan_groups(const std::vector<ProbLayout>& pl, const std::vector<int>& pset_of,
+                       GroupPlan& out, const char** msg) {
+  const int B = (int)pl.size();
+  std::map<std::string, int> seen;
+  std::vector<ProbLayout> uniq;
+  std::vector<int> first_lid(B);
+  for (int b = 0; b < B; ++b) {
+    ProbLayout k;
+    memset(&k, 0, sizeof k);
+    k.desc = norm_desc(pl[b].desc);
+    k.rot_wb = k.desc.n_wb > 0 ? pl[b].rot_wb % k.desc.n_wb : 0;
+    k.rot_fb = k.desc.n_fb > 0 ? pl[b].rot_fb % k.desc.n_fb : 0;
+    const std::string key((const char*)&k, sizeof k);
+    auto it = seen.find(key);
+    if (it == seen.end()) {
+      if ((int)uniq.size() == MAXL) return plan_refuse(msg, "more than MHPC_MAX_LAYOUTS distinct layouts");
+      it = seen.emplace(key, (int)uniq.size()).first;
+      uniq.push_back(k);
+    }
+    first_lid[b] = it->second;
+  }
+  const int L = (int)uniq.size();
+  std::vector<Layout> lay(L);
+  for (int l = 0; l < L; ++l) build_layout(lay[l], uniq[l].desc, uniq[l].rot_wb, uniq[l].rot_fb);
+  std::vector<int> order(L), rank(L);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return lay[a].NK > lay[c].NK; });
+  for (int l = 0; l < L; ++l) rank[order[l]] = l;
+  // the (layout rank, set) pairs in use, in that order
+  std::map<std::pair<int, int>, int> grp;
+  for (int b = 0; b < B; ++b) grp[{rank[first_lid[b]], pset_of[b]}] = 0;
+  const int G = (int)grp.size();
+  if (G > MAXL)
+    return plan_refuse(msg, "more than MHPC_MAX_LAYOUTS distinct (layout, parameter set) pairs");
+  GroupPlan n;
+  n.lays.resize(G);
+  n.ldesc.resize(G);
+  n.bym.resize(G);
+  n.gset.resize(G);
+  n.nlay = L;
+  int ng = 0;
+  for (auto& kv : grp) {
+    const int g = kv.second = ng++;
+    const Layout& Lg = lay[order[kv.first.first]];
+    n.lays[g] = Lg;
+    n.ldesc[g] = uniq[order[kv.first.first]].desc;
+    n.bym[g] = byte_model(Lg);
+    n.gset[g] = kv.first.second;
+    n.NK = std::max(n.NK, Lg.NK);
+    n.pmax = std::max(n.pmax, Lg.P);
+    if (Lg.n_wb > 0 && Lg.P > Lg.n_wb) n.split_ok = 1;
+    for (int p = 0; p < Lg.P; ++p)
+      if (Lg.N[p] > ST_RMAX) n.stage_fits = 0;
+    n.gpk[g] = Lg.par_knots;
+    n.gpi[g] = Lg.par_imp;
+  }
+  n.lid.resize(B);
+  std::vector<int> cnt(G + 1, 0);
+  for (int b = 0; b < B; ++b) {
+    n.lid[b] = grp[{rank[first_lid[b]], pset_of[b]}];
+    ++cnt[n.lid[b] + 1];
+  }
+  n.ngrp = G;
+  for (int g = 0; g < G; ++g) cnt[g + 1] += cnt[g];
+  for (int g = 0; g <= G; ++g) n.go[g] = cnt[g];
+  n.gidx.resize(B);
+  for (int b = 0; b < B; ++b) {
+    const int pos = cnt[n.lid[b]]++;
+    n.gidx[pos] = b;
+    if (pos != b) n.ident = 0;
+  }
+  out = std::move(n);
+  return MHPC_OK;
+}
+
+}  // namespace MHPC_NS

@@ -9,13 +9,12 @@
 #include <cmath>
 #include <string>
 #include <algorithm>
-#include <map>
-#include <numeric>
 #include <vector>
 
 #include "../../include/mhpc_capi.h"
 #include "mhpc_devtemp.h"
 #include "mhpc_launch.h"
+#include "mhpc_plan.h"
 
 extern thread_local std::string mhpc_g_err;  // mhpc_capi.cpp (mhpc_last_error)
 
@@ -36,24 +35,17 @@ int fail(int code, const std::string& msg) {
     if (e_ != hipSuccess)                                                             \
       return fail(MHPC_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
+// a check or planner of mhpc_plan.h (its trailing argument the message): a refusal goes to fail()
+#define PLANCHK(call, ...)                                 \
+  do {                                                     \
+    const char* msg_ = nullptr;                            \
+    if (int rc_ = call(__VA_ARGS__, &msg_)) return fail(rc_, msg_); \
+  } while (0)
 }  // namespace
 
 enum { K_INIT = 0, K_FULL, K_LS, K_PAR, K_BWS, K_AL, K_BWS_SRB, NKERN };
 static const char* kKernelNames[NKERN] = {"k_init", "k_cost(forward_sweep0)", "k_rollout(linesearch)",
                                           "k_partials", "k_bws", "k_al_end", "k_bws_srb"};
-
-// Per-problem phase layout: the descriptor (gait point) and the phase-buffer rotation of the
-// receding-horizon loop (MHPCLocomotion::update_problem rotates pidx_WB / pidx_FB by one per
-// call, MHPCLocomotion.cpp:111-121: after r calls phase i uses buffer (i + r) mod n).
-struct ProbLayout {
-  mhpc_problem_desc desc;
-  int rot_wb, rot_fb;
-};
-// Algorithmic bytes per problem of one layout
-struct ByteModel {
-  double roll_read = 0, roll_write = 0, roll_term = 0, par = 0, init = 0, cost = 0;
-  double roll_flops = 0;  // one trial rollout (the line search's flop model)
-};
 
 struct Handle {
   mhpc_problem_desc desc;  // the descriptor of mhpc_create (precision, vel, height)
@@ -84,9 +76,7 @@ struct Handle {
   // handle (set together with params_changed; mhpc_rollout_costs looks at this one alone)
   std::vector<CostParams> psets;
   std::vector<int> pset_of;
-  std::vector<int> gset;  // parameter set of each group
   bool sets_changed = false;
-  int nlay = 1;  // distinct layouts in use (the groups are (layout, parameter set) pairs)
   float solve_ms = 0;
   unsigned long long* dcnt = nullptr;  // reduced counters per group [MAXL][NCNT]
   unsigned long long cnt[NCNT] = {};   // their sum over the groups
@@ -97,18 +87,14 @@ struct Handle {
   std::vector<int> evkind;
   double kms[NKERN] = {}, kbytes[NKERN] = {}, kflops[NKERN] = {};
   int64_t klaunch[NKERN] = {};
-  // per-problem layouts and the groups built from them and the parameter sets (rebuild_groups):
-  // each group's layout (host; the device group table is dgrp), each problem's group, the
-  // problems grouped
+  // per-problem layouts, and the plan installed from them and the parameter sets (plan_groups,
+  // mhpc_plan.h; commit_groups): each group's layout, descriptor, byte model and set, each
+  // problem's group, the problems grouped.  The device copies: dgrp, dlid, dgidx.
   std::vector<ProbLayout> pl;
-  std::vector<Layout> lays;
-  std::vector<mhpc_problem_desc> ldesc;  // descriptor of each group's layout
-  std::vector<int> lid, gidx;
+  GroupPlan plan;
   Group* dgrp = nullptr;  // device group table [MAXL]
   int *dgidx = nullptr, *dlid = nullptr;
   Cmd* dcmd = nullptr;
-  // algorithmic byte model per problem of each group's layout
-  std::vector<ByteModel> bym;
   // receding horizon (MHPCLocomotion::update_problem): each problem's current mode, the
   // buffer store [B][spmax][nbk] (allocated at the first update), knot capacity of the
   // packed arrays, and whether the next solve's first forward_sweep(0) must be a real
@@ -140,83 +126,6 @@ struct Handle {
   hipEvent_t evstart = nullptr;
 };
 
-// Phase layout of a descriptor: modes, knot counts and offsets, partials work items, and the
-// phase buffers after rot_wb / rot_fb rotations (MHPCLocomotion::update_problem).
-static void build_layout(Layout& L, const mhpc_problem_desc& desc, int rot_wb, int rot_fb) {
-  memset(&L, 0, sizeof L);
-  L.P = desc.n_wb + desc.n_fb;
-  L.n_wb = desc.n_wb;
-  int ko = 0, items = 0, items_v = 0;
-  for (int p = 0; p < L.P; ++p) {
-    const bool wb = p < desc.n_wb;
-    L.mode[p] = desc.mode_seq[p];
-    L.N[p] = desc.N[p];
-    L.ko[p] = ko;
-    L.xs[p] = wb ? 14 : 6;
-    L.dt[p] = wb ? desc.dt_wb : desc.dt_fb;
-    L.buf[p] = wb ? (p + rot_wb) % desc.n_wb : desc.n_wb + (p - desc.n_wb + rot_fb) % desc.n_fb;
-    ko += desc.N[p];
-    L.par_knot_off[p] = items;
-    L.par_imp_off[p] = items_v;
-    if (wb) {
-      items += desc.N[p] - 1;
-      items_v += (L.mode[p] == 2 || L.mode[p] == 4) ? 14 : 0;
-    }
-  }
-  for (int p = L.P; p <= MAXP; ++p) {
-    L.par_knot_off[p] = items;
-    L.par_imp_off[p] = items_v;
-  }
-  L.par_knots = items;
-  L.par_imp = items_v;
-  L.NK = ko;
-}
-
-// Algorithmic HBM bytes (fp64) of one problem for each kernel's unit of work.
-constexpr double kB = sizeof(real);  // bytes per element of the solve's arithmetic type
-
-// Line-search flop model per trial knot (SURVEY.md 8d secondary roofline): the reference's
-// dynamics in CasADi's generated-code assignment counts (Dyn_BS / Dyn_FS 2301,
-// Dyn_FL 1441, FBDynamics 44 -- scalar operations incl. loads, so an upper estimate), plus the
-// feedback u = u_nom + eps du + K (x - x_nom) and the Euler step (WB: 14 + 4 * 28 + 8 + 28;
-// SRB: 6 + 4 * 12 + 8 + 12).  The running costs (the second wave) are not counted.
-static double ro_knot_flops(int mode, bool wb) {
-  if (!wb) return 44 + 74;
-  return (mode == 1 || mode == 3 ? 2301.0 : 1441.0) + 162;
-}
-
-static ByteModel byte_model(const Layout& L) {
-  ByteModel m;
-  double rr = 14 * 8, rw = 0, rt = 0, pb = 0, ib = L.NK * kB, cb = 0;
-  for (int p = 0; p < L.P; ++p) {
-    const bool wb = p < L.n_wb;
-    const int n = wb ? 14 : 6, N = L.N[p];
-    // nominal x,u (n+4) + K (4n) + du (4) read once per problem (the candidates of a
-    // problem share them)
-    rr += (N - 1) * kB * ((n + 4) + 4 * n + 4);
-    // a storing candidate writes x,u,y of every knot, every candidate x at the last knot
-    rw += (N - 1) * kB * (n + 8);
-    rt += n * kB;
-    m.roll_flops += (N - 1) * ro_knot_flops(L.mode[p], wb);
-    // k_cost: nominal x,u(,y) of every knot + refpos
-    cb += (N - 1) * kB * (n + 4 + (wb ? 4 : 0) + 1) + kB * (n + 1);
-    // k_init: x,u,y written for every knot (WB and SRB)
-    if (!wb) ib += N * kB * 14;
-    if (wb) {
-      const bool imp = L.mode[p] == 2 || L.mode[p] == 4;
-      // x,u read; the record written without its four zero columns (written once at create)
-      pb += (N - 1) * kB * (18 + PS - 4 * 9) + (imp ? kB * (14 + 196) : 0.0);
-      ib += N * kB * 22;
-    }
-  }
-  m.roll_read = rr;
-  m.roll_write = rw;
-  m.roll_term = rt;
-  m.par = pb;
-  m.init = ib;
-  m.cost = cb;
-  return m;
-}
 // backward sweep: per WB knot partials record + x,u,y + refpos read, K,du,G written;
 // per SRB knot x,u + refpos read, K,du,G written; Px read per impact-aware step
 static constexpr double kBwsWbKnot = kB * (PS + 22 + 1 + 56 + 4 + 14);
@@ -235,24 +144,6 @@ const char* api_kernel_name(int k) {
 }
 
 
-static int validate(const mhpc_problem_desc* d) {
-  if (!d) return fail(MHPC_ERR_INVALID, "null descriptor");
-  const int P = d->n_wb + d->n_fb;
-  if (d->n_wb < 0 || d->n_fb < 0 || P < 1 || P > MHPC_MAX_PHASES)
-    return fail(MHPC_ERR_INVALID, "phase count out of range");
-  if (d->precision != 64 && d->precision != 32) return fail(MHPC_ERR_INVALID, "precision must be 64 or 32");
-  int NK = 0;
-  for (int p = 0; p < P; ++p) {
-    if (d->mode_seq[p] < 1 || d->mode_seq[p] > 4) return fail(MHPC_ERR_INVALID, "mode out of range");
-    if (d->N[p] < 2) return fail(MHPC_ERR_INVALID, "each phase needs N >= 2");
-    NK += d->N[p];
-  }
-  if (NK > MHPC_MAX_KNOTS) return fail(MHPC_ERR_INVALID, "too many knots");
-  if (!(d->dt_wb > 0) || !(d->dt_fb > 0)) return fail(MHPC_ERR_INVALID, "dt must be positive");
-  return MHPC_OK;
-}
-
-
 static void free_bufs(Handle* h) {
   DevBufs& d = h->d;
   void* ptrs[] = {d.traj, d.refpos, d.K, d.du, d.G, d.par, d.px, d.x0, d.st, d.out, d.carry,
@@ -263,24 +154,6 @@ static void free_bufs(Handle* h) {
   h->dgrp = nullptr;
   h->dgidx = h->dlid = nullptr;
   h->dcmd = nullptr;
-}
-
-// A descriptor normalised for comparison (entries past its phases and reserved fields zero)
-static mhpc_problem_desc norm_desc(const mhpc_problem_desc& in) {
-  mhpc_problem_desc d;
-  memset(&d, 0, sizeof d);
-  d.n_wb = in.n_wb;
-  d.n_fb = in.n_fb;
-  for (int p = 0; p < in.n_wb + in.n_fb; ++p) {
-    d.mode_seq[p] = in.mode_seq[p];
-    d.N[p] = in.N[p];
-  }
-  d.dt_wb = in.dt_wb;
-  d.dt_fb = in.dt_fb;
-  d.vel_cmd = in.vel_cmd;
-  d.height_cmd = in.height_cmd;
-  d.precision = in.precision;
-  return d;
 }
 
 // The packed per-knot arrays for a knot stride of NK (grown, never shrunk: their content is
@@ -327,8 +200,8 @@ static int ensure_knot_arrays(Handle* h, int NK) {
 
 // The group table (group g: layout lays[g], parameter set gset[g]) to the device.
 static int upload_params(Handle* h) {
-  std::vector<Group> t(h->gset.size());
-  for (size_t g = 0; g < t.size(); ++g) t[g] = Group{h->lays[g], h->psets[h->gset[g]]};
+  std::vector<Group> t(h->plan.gset.size());
+  for (size_t g = 0; g < t.size(); ++g) t[g] = Group{h->plan.lays[g], h->psets[h->plan.gset[g]]};
   h->sp.cw = h->psets[h->pset_of[0]];  // k_init's copy (problem 0's set)
   HIPCHK(hipMemcpyAsync(h->dgrp, t.data(), t.size() * sizeof(Group), hipMemcpyHostToDevice,
                         h->stream));
@@ -336,106 +209,52 @@ static int upload_params(Handle* h) {
   return MHPC_OK;
 }
 
-// Groups from the per-problem layouts and parameter sets: the distinct (layout, set) pairs in
-// use, where a layout is a (descriptor, buffer rotation) pair; longest layout first (its blocks
-// head every launch: the long blocks start first in a mixed batch), then by set, the problems
-// of each group in batch order.  Group g has its own Layout record (a layout that several sets
-// share is stored once per group, so lays[lid[b]] stays problem b's layout) and its parameter
-// record.  Uploads the group table and the grouped order, sets the launch fields of sp, grows the
-// packed arrays if a layout needs it.  A call that would need more than MAXL groups fails
-// before it changes anything.  keep_stride (mhpc_reset_problems, whose caller checked that every
-// layout fits, and the parameter-set calls, which change no layout): the knot stride stays what
-// it is even if the longest layout left, so no array is re-strided, re-zeroed or reallocated and
-// the problems' records stay where they are.
-static int rebuild_groups(Handle* h, bool keep_stride = false) {
-  SolveParams& sp = h->sp;
-  const int B = sp.B;
-  std::map<std::string, int> seen;
-  std::vector<ProbLayout> uniq;
-  std::vector<int> first_lid(B);
-  for (int b = 0; b < B; ++b) {
-    ProbLayout k;
-    memset(&k, 0, sizeof k);
-    k.desc = norm_desc(h->pl[b].desc);
-    k.rot_wb = k.desc.n_wb > 0 ? h->pl[b].rot_wb % k.desc.n_wb : 0;
-    k.rot_fb = k.desc.n_fb > 0 ? h->pl[b].rot_fb % k.desc.n_fb : 0;
-    const std::string key((const char*)&k, sizeof k);
-    auto it = seen.find(key);
-    if (it == seen.end()) {
-      if ((int)uniq.size() == MAXL) return fail(MHPC_ERR_INVALID, "more than MHPC_MAX_LAYOUTS distinct layouts");
-      it = seen.emplace(key, (int)uniq.size()).first;
-      uniq.push_back(k);
-    }
-    first_lid[b] = it->second;
-  }
-  const int L = (int)uniq.size();
-  std::vector<Layout> lay(L);
-  for (int l = 0; l < L; ++l) build_layout(lay[l], uniq[l].desc, uniq[l].rot_wb, uniq[l].rot_fb);
-  std::vector<int> order(L), rank(L);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return lay[a].NK > lay[c].NK; });
-  for (int l = 0; l < L; ++l) rank[order[l]] = l;
-  // the (layout rank, set) pairs in use, in that order
-  std::map<std::pair<int, int>, int> grp;
-  for (int b = 0; b < B; ++b) grp[{rank[first_lid[b]], h->pset_of[b]}] = 0;
-  const int G = (int)grp.size();
-  if (G > MAXL)
-    return fail(MHPC_ERR_INVALID,
-                "more than MHPC_MAX_LAYOUTS distinct (layout, parameter set) pairs");
-  h->lays.resize(G);
-  h->ldesc.resize(G);
-  h->bym.resize(G);
-  h->gset.resize(G);
-  h->nlay = L;
-  int NK = 0, pmax = 0;
-  sp.split_ok = 0;
-  sp.stage_fits = 1;
-  int ng = 0;
-  for (auto& kv : grp) {
-    const int g = kv.second = ng++;
-    const Layout& Lg = lay[order[kv.first.first]];
-    h->lays[g] = Lg;
-    h->ldesc[g] = uniq[order[kv.first.first]].desc;
-    h->bym[g] = byte_model(Lg);
-    h->gset[g] = kv.first.second;
-    NK = std::max(NK, Lg.NK);
-    pmax = std::max(pmax, Lg.P);
-    if (Lg.n_wb > 0 && Lg.P > Lg.n_wb) sp.split_ok = 1;
-    for (int p = 0; p < Lg.P; ++p)
-      if (Lg.N[p] > ST_RMAX) sp.stage_fits = 0;
-    sp.gpk[g] = Lg.par_knots;
-    sp.gpi[g] = Lg.par_imp;
-  }
-  h->lid.resize(B);
-  std::vector<int> cnt(G + 1, 0);
-  for (int b = 0; b < B; ++b) {
-    h->lid[b] = grp[{rank[first_lid[b]], h->pset_of[b]}];
-    ++cnt[h->lid[b] + 1];
-  }
-  sp.ngrp = G;
-  for (int g = 0; g < G; ++g) cnt[g + 1] += cnt[g];
-  for (int g = 0; g <= G; ++g) sp.go[g] = cnt[g];
-  h->gidx.resize(B);
-  sp.ident = 1;
-  for (int b = 0; b < B; ++b) {
-    const int pos = cnt[h->lid[b]]++;
-    h->gidx[pos] = b;
-    if (pos != b) sp.ident = 0;
-  }
-  sp.pmax = pmax;
-  if (!keep_stride) {
-    int rc = ensure_knot_arrays(h, NK);
-    if (rc) return rc;
-    sp.NK = NK;
-  }
-  h->d.grp = h->dgrp;
-  h->d.gidx = h->dgidx;
-  h->d.lid = h->dlid;
-  h->d.cmd = h->dcmd;
-  HIPCHK(hipMemcpyAsync(h->dgidx, h->gidx.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->dlid, h->lid.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+// The installed plan's grouped order, each problem's group and the group table to the device.
+static int upload_plan(Handle* h) {
+  const size_t B = h->sp.B;
+  HIPCHK(hipMemcpyAsync(h->dgidx, h->plan.gidx.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->dlid, h->plan.lid.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return upload_params(h);
+}
+
+// The one way a new grouping reaches a handle: `plan` (plan_groups over the new layouts and sets)
+// and whichever of the per-problem layouts, the parameter sets and the problems' sets it was
+// planned from that differ from the handle's (null: the handle's own).  Grows or re-strides the
+// packed arrays for the plan's longest layout, installs the plan with the launch fields of sp, and
+// uploads the grouped order and the group table.  keep_stride (mhpc_reset_problems and
+// mhpc_copy_problems, whose layouts were checked to fit, and the parameter-set calls, which change
+// no layout): the knot stride stays what it is even if the longest layout left, so no array is
+// re-strided, re-zeroed or reallocated and the problems' records stay where they are.
+// Everything is swapped in: after MHPC_OK the arguments hold what the handle held before (commit
+// them again to go back, as mhpc_copy_problems does).  On an error nothing has changed: a failed
+// allocation leaves the arrays as they were, and after a failed upload the previous plan, layouts,
+// sets and stride are put back here, host and device (as far as the device still answers).
+static int commit_groups(Handle* h, GroupPlan&& plan, bool keep_stride,
+                         std::vector<ProbLayout>* pl = nullptr, std::vector<CostParams>* psets = nullptr,
+                         std::vector<int>* pset_of = nullptr) {
+  const int old_NK = h->sp.NK;
+  if (!keep_stride) {
+    if (int rc = ensure_knot_arrays(h, plan.NK)) return rc;
+    h->sp.NK = plan.NK;
+  }
+  auto exchange = [&] {
+    std::swap(h->plan, plan);
+    if (pl) h->pl.swap(*pl);
+    if (psets) h->psets.swap(*psets);
+    if (pset_of) h->pset_of.swap(*pset_of);
+    h->plan.to_params(h->sp);
+  };
+  exchange();
+  const int rc = upload_plan(h);
+  if (rc) {
+    const std::string why = mhpc_g_err;
+    exchange();
+    if (h->sp.NK != old_NK && ensure_knot_arrays(h, old_NK) == MHPC_OK) h->sp.NK = old_NK;
+    if (!h->plan.gidx.empty()) (void)upload_plan(h);  // (mhpc_create has no previous plan)
+    mhpc_g_err = why;
+  }
+  return rc;
 }
 
 // Host (double) parameter structs <-> the kernels' parameter block (real).
@@ -520,32 +339,6 @@ static int check_constraints(const mhpc_constraint_params* c) {
   return MHPC_OK;
 }
 
-// Parameter sets compare by value, entry by entry (CostParams holds nothing but reals).
-static bool same_params(const CostParams& a, const CostParams& b) {
-  const real *x = (const real*)&a, *y = (const real*)&b;
-  for (size_t i = 0; i < sizeof(CostParams) / sizeof(real); ++i)
-    if (!(x[i] == y[i])) return false;
-  return true;
-}
-// Merge the sets that compare equal and drop the ones no problem uses (first occurrence
-// kept, order preserved); `of` is renumbered accordingly.
-static void merge_sets(std::vector<CostParams>& sets, std::vector<int>& of) {
-  std::vector<int> to(sets.size(), -1);
-  std::vector<char> used(sets.size(), 0);
-  for (int s : of) used[s] = 1;
-  std::vector<CostParams> out;
-  for (size_t i = 0; i < sets.size(); ++i) {
-    if (!used[i]) continue;
-    for (size_t j = 0; j < out.size() && to[i] < 0; ++j)
-      if (same_params(out[j], sets[i])) to[i] = (int)j;
-    if (to[i] < 0) {
-      to[i] = (int)out.size();
-      out.push_back(sets[i]);
-    }
-  }
-  for (int& s : of) s = to[s];
-  sets.swap(out);
-}
 // A handle-wide setter rewrote one half of every set in `ns`: sets that became equal merge (the
 // groups are then rebuilt), otherwise only the device table changes.  On a device error the
 // handle keeps its old sets, host and device (as far as the device still answers).
@@ -554,16 +347,19 @@ static int apply_sets(Handle* h, std::vector<CostParams>& ns) {
   std::vector<int> nof = h->pset_of;
   const size_t n = ns.size();
   merge_sets(ns, nof);
-  h->psets.swap(ns);
-  h->pset_of.swap(nof);
-  // (no layout changes here: the knot stride stays, also one a reset left above the longest layout)
-  const int rc = h->psets.size() != n ? rebuild_groups(h, true) : upload_params(h);
-  if (rc) {
+  if (ns.size() == n) {  // nothing merged: the same groups with new values
     h->psets.swap(ns);
-    h->pset_of.swap(nof);
-    (void)rebuild_groups(h, true);
+    const int rc = upload_params(h);
+    if (rc) {
+      h->psets.swap(ns);
+      (void)upload_params(h);
+    }
+    return rc;
   }
-  return rc;
+  GroupPlan plan;
+  PLANCHK(plan_groups, h->pl, nof, plan);
+  // (no layout changes here: the knot stride stays, also one a reset left above the longest layout)
+  return commit_groups(h, std::move(plan), true, nullptr, &ns, &nof);
 }
 
 int api_set_cost_weights(Handle* h, const mhpc_cost_weights* w) {
@@ -626,15 +422,10 @@ int api_set_param_sets(Handle* h, int n_sets, const mhpc_cost_weights* w,
   if (!changed) return MHPC_OK;  // nothing changes: nothing pending
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->psets.swap(ns);
-  h->pset_of.swap(nof);
+  GroupPlan plan;
+  PLANCHK(plan_groups, h->pl, nof, plan);  // too many (layout, set) pairs: the old sets stay
   // (the knot stride stays as in apply_sets: the records of an initialised handle are live)
-  if ((rc = rebuild_groups(h, true))) {  // too many (layout, set) pairs: keep the old sets
-    h->psets.swap(ns);
-    h->pset_of.swap(nof);
-    (void)rebuild_groups(h, true);
-    return rc;
-  }
+  if ((rc = commit_groups(h, std::move(plan), true, nullptr, &ns, &nof))) return rc;
   if (h->initialized) h->params_changed = h->sets_changed = true;
   return MHPC_OK;
 }
@@ -655,8 +446,7 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
                            int device, Handle** out) {
   if (!out || !opt) return fail(MHPC_ERR_INVALID, "null argument");
   *out = nullptr;
-  int rc = validate(desc);
-  if (rc) return rc;
+  PLANCHK(check_desc, desc);
   if (batch < 1) return fail(MHPC_ERR_INVALID, "batch must be >= 1");
   if (!(opt->alpha > 0 && opt->alpha < 1)) return fail(MHPC_ERR_INVALID, "alpha must be in (0,1)");
   int ndev = 0;
@@ -748,7 +538,14 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
   }
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   int rc2 = e == hipSuccess ? MHPC_OK : fail(MHPC_ERR_DEVICE, std::string("allocation failed: ") + hipGetErrorString(e));
-  if (!rc2) rc2 = rebuild_groups(h);  // one group; allocates the packed arrays
+  if (!rc2) {  // one group; allocates the packed arrays
+    d.grp = h->dgrp;
+    d.gidx = h->dgidx;
+    d.lid = h->dlid;
+    GroupPlan plan;
+    rc2 = plan_groups(h->pl, h->pset_of, plan, nullptr);  // (one layout, one set: never refused)
+    if (!rc2) rc2 = commit_groups(h, std::move(plan), false);
+  }
   if (!rc2) {  // the command array (after the packed arrays: their placement stays as it was)
     const std::vector<Cmd> hcmd(B, Cmd{(real)desc->vel_cmd, (real)desc->height_cmd});
     e = hipMalloc((void**)&h->dcmd, B * sizeof(Cmd));
@@ -768,7 +565,7 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
 }
 
 static int x0_row(const Handle* h) {
-  for (const Layout& L : h->lays)
+  for (const Layout& L : h->plan.lays)
     if (L.n_wb > 0) return 14;
   return 6;
 }
@@ -781,7 +578,7 @@ static std::vector<E> pad_rows(const Handle* h, int first, int count, int n_s, c
   const int r = x0_row(h);
   std::vector<E> out((size_t)count * n_s * 14, E(0));
   for (int b = 0; b < count; ++b) {
-    const int nb = h->lays[h->lid[first + b]].n_wb > 0 ? 14 : 6;
+    const int nb = h->plan.lays[h->plan.lid[first + b]].n_wb > 0 ? 14 : 6;
     for (size_t t = (size_t)b * n_s; t < (size_t)(b + 1) * n_s; ++t)
       std::copy(src + t * r, src + t * r + nb, out.begin() + t * 14);
   }
@@ -853,16 +650,15 @@ static int d2h(Handle* h, void* dst, const void* src, size_t bytes) {
 static int initialize_async(Handle* h) {
   // build_problem binds phase p to buffer p and starts the gait at each problem's first mode
   bool rotated = false;
-  for (int b = 0; b < h->sp.B; ++b) {
-    ProbLayout& q = h->pl[b];
-    rotated = rotated || q.rot_wb != 0 || q.rot_fb != 0;
-    q.rot_wb = q.rot_fb = 0;
-    h->cmode[b] = q.desc.mode_seq[0];
-  }
+  for (const ProbLayout& q : h->pl) rotated = rotated || q.rot_wb != 0 || q.rot_fb != 0;
   if (rotated) {
-    const int rc = rebuild_groups(h);
-    if (rc) return rc;
+    std::vector<ProbLayout> npl = h->pl;
+    for (ProbLayout& q : npl) q.rot_wb = q.rot_fb = 0;
+    GroupPlan plan;
+    PLANCHK(plan_groups, npl, h->pset_of, plan);
+    if (int rc = commit_groups(h, std::move(plan), false, &npl)) return rc;
   }
+  for (int b = 0; b < h->sp.B; ++b) h->cmode[b] = h->pl[b].desc.mode_seq[0];
   const SolveParams& sp = h->sp;
   DevBufs& d = h->d;
   // memory_reset (K / du / G, trajectory tails) on the second stream beside k_init, which
@@ -878,7 +674,7 @@ static int initialize_async(Handle* h) {
     h->kbytes[K_INIT] += (double)sp.B * 4 * MAXP * kB;
   }
   HIPCHK(hipStreamWaitEvent(h->stream, h->evjoin, 0));
-  for (int g = 0; g < sp.ngrp; ++g) h->kbytes[K_INIT] += h->bym[g].init * (sp.go[g + 1] - sp.go[g]);
+  for (int g = 0; g < sp.ngrp; ++g) h->kbytes[K_INIT] += h->plan.bym[g].init * (sp.go[g + 1] - sp.go[g]);
   // the buffer store is zeroed lazily (first update_problem), so a plain initialize + solve
   // pays nothing for it
   h->store_valid = false;
@@ -887,6 +683,22 @@ static int initialize_async(Handle* h) {
   h->nfresh = 0;
   return MHPC_OK;
 }
+
+// ---- call order ---------------------------------------------------------------------------------
+// New x0, commands and constraint parameters reach the problems' references and AL / ReB state only
+// through mhpc_initialize / mhpc_update_problem(s): each setter raises its flag on an initialised
+// handle, those two call mark_current, and the entry points in between refuse with their own
+// message for the flags they look at.
+static void mark_current(Handle* h) {
+  h->x0_changed = h->params_changed = h->sets_changed = h->cmd_changed = false;
+  h->solved = false;
+}
+// commands or constraint parameters pending (sets_changed is only ever raised with params_changed)
+static bool pending(const Handle* h) { return h->cmd_changed || h->params_changed; }
+static const char* const kCmdPending =
+    "commands changed: call mhpc_initialize or mhpc_update_problem first";
+static const char* const kParamsPending =
+    "constraint parameters changed: call mhpc_initialize or mhpc_update_problem first";
 
 int api_initialize(Handle* h) {
   if (!h) return fail(MHPC_ERR_INVALID, "null handle");
@@ -898,11 +710,7 @@ int api_initialize(Handle* h) {
   rc = collect_profile(h);
   if (rc) return rc;
   h->initialized = true;
-  h->x0_changed = false;
-  h->params_changed = false;
-  h->sets_changed = false;
-  h->cmd_changed = false;
-  h->solved = false;
+  mark_current(h);
   return MHPC_OK;
 }
 
@@ -1081,13 +889,13 @@ static int solve_async(Handle* h) {
     nf.resize(B + 1);
     for (int pos = 0; pos < B; ++pos) {
       nf[pos] = nnf;
-      nnf += !h->fresh[h->gidx[pos]];
+      nnf += !h->fresh[h->plan.gidx[pos]];
     }
     nf[B] = nnf;
     std::vector<int> split(B);
     for (int pos = 0; pos < B; ++pos) {
-      const bool f = h->fresh[h->gidx[pos]];
-      split[f ? nnf + pos - nf[pos] : nf[pos]] = h->gidx[pos];
+      const bool f = h->fresh[h->plan.gidx[pos]];
+      split[f ? nnf + pos - nf[pos] : nf[pos]] = h->plan.gidx[pos];
     }
     HIPCHK(hipMemcpyAsync(h->dsplit, split.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1186,11 +994,7 @@ int api_solve(Handle* h, int32_t* status) {
   if (h->solved) return fail(MHPC_ERR_STATE, "solve already ran: call mhpc_initialize or mhpc_update_problem");
   if (h->x0_changed)
     return fail(MHPC_ERR_STATE, "x0 changed: call mhpc_initialize or mhpc_update_problem first");
-  if (h->params_changed)
-    return fail(MHPC_ERR_STATE,
-                "constraint parameters changed: call mhpc_initialize or mhpc_update_problem first");
-  if (h->cmd_changed)
-    return fail(MHPC_ERR_STATE, "commands changed: call mhpc_initialize or mhpc_update_problem first");
+  if (pending(h)) return fail(MHPC_ERR_STATE, h->params_changed ? kParamsPending : kCmdPending);
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipEventRecord(h->ev0, h->stream));
   int rc = solve_async(h);
@@ -1213,7 +1017,7 @@ int api_solve(Handle* h, int32_t* status) {
   const unsigned long long* c = h->cnt;
   for (int g = 0; g < h->sp.ngrp; ++g) {  // per group: its problems' counters x its layout's bytes
     const unsigned long long* cg = h->gcnt[g];
-    const ByteModel& m = h->bym[g];
+    const ByteModel& m = h->plan.bym[g];
     const SolveParams& sp = h->sp;
     h->kbytes[K_FULL] += cg[C_FWD] * m.cost;
     // the trials that store their records (RO_STORE_FIRST; the re-rolls of the others, rare,
@@ -1313,7 +1117,7 @@ static int range_phase_shape(const Handle* h, int phase, int first, int count, i
   if (first < 0 || count < 1 || first > h->sp.B - count)
     return fail(MHPC_ERR_INVALID, "problem range outside the batch");
   for (int b = first; b < first + count; ++b) {
-    const Layout& L = h->lays[h->lid[b]];
+    const Layout& L = h->plan.lays[h->plan.lid[b]];
     if (phase < 0 || phase >= L.P) return fail(MHPC_ERR_INVALID, "bad phase");
     if (b == first) {
       *n = L.xs[phase];
@@ -1333,7 +1137,7 @@ int api_get_phase(Handle* h, int phase, int first, int count, double* x, double*
   int rc = range_phase_shape(h, phase, first, count, &n, &N);
   if (rc) return rc;
   HIPCHK(hipSetDevice(h->device));
-  auto ko = [&](int b) { return h->lays[h->lid[b]].ko[phase]; };
+  auto ko = [&](int b) { return h->plan.lays[h->plan.lid[b]].ko[phase]; };
   return for_runs(first, count, ko, [&](int r0, int nb) {
     const size_t o = (size_t)(r0 - first) * N;
     auto at = [&](double* p, int per) { return p ? p + o * per : nullptr; };
@@ -1355,7 +1159,7 @@ int api_get_scalars(Handle* h, double* J, double* dV_exp, double* viol,
     if (dV_exp) dV_exp[b] = st[b].dV_exp;
     if (viol) viol[b] = st[b].viol;
     // rows of the most phases any layout has; zero past the problem's own phases
-    const int P = h->lays[h->lid[b]].P;
+    const int P = h->plan.lays[h->plan.lid[b]].P;
     for (int p = 0; p < sp.pmax; ++p) {
       if (V_phase) V_phase[b * sp.pmax + p] = p < P ? (double)st[b].V[p] : 0.0;
       if (dV_phase) dV_phase[b * sp.pmax + p] = p < P ? (double)st[b].dV[p] : 0.0;
@@ -1387,8 +1191,7 @@ int api_rollout_costs(Handle* h, int n_eps, const double* eps, double* J,
   if (!h || !eps || !J) return fail(MHPC_ERR_INVALID, "null argument");
   if (!h->initialized) return fail(MHPC_ERR_STATE, "not initialized");
   if (n_eps < 1 || n_eps > MHPC_MAX_ROLLOUT_EPS) return fail(MHPC_ERR_INVALID, "n_eps out of range");
-  if (h->cmd_changed)
-    return fail(MHPC_ERR_STATE, "commands changed: call mhpc_initialize or mhpc_update_problem first");
+  if (h->cmd_changed) return fail(MHPC_ERR_STATE, kCmdPending);
   if (h->sets_changed)
     return fail(MHPC_ERR_STATE,
                 "parameter sets changed: call mhpc_initialize or mhpc_update_problem first");
@@ -1408,11 +1211,7 @@ int api_rollout_costs(Handle* h, int n_eps, const double* eps, double* J,
 // a pending x0 does not matter to the rollouts, which never read the handle's x0.
 static int policy_ready(const Handle* h) {
   if (!h->initialized) return fail(MHPC_ERR_STATE, "not initialized");
-  if (h->cmd_changed)
-    return fail(MHPC_ERR_STATE, "commands changed: call mhpc_initialize or mhpc_update_problem first");
-  if (h->params_changed)
-    return fail(MHPC_ERR_STATE,
-                "constraint parameters changed: call mhpc_initialize or mhpc_update_problem first");
+  if (pending(h)) return fail(MHPC_ERR_STATE, h->cmd_changed ? kCmdPending : kParamsPending);
   return MHPC_OK;
 }
 // Caller rows xs [count][n_s][r] of problems [first, first + count) as the device rows of 14
@@ -1428,7 +1227,7 @@ static int policy_pack(const Handle* h, int first, int count, int n_s, const dou
 }
 static int min_phases(const Handle* h) {
   int P = MAXP;
-  for (const Layout& L : h->lays) P = std::min(P, L.P);
+  for (const Layout& L : h->plan.lays) P = std::min(P, L.P);
   return P;
 }
 
@@ -1504,7 +1303,7 @@ int api_advance_x0(Handle* h, int n_phases, const double* dx) {
   if (rc) return rc;
   if (n_phases < 1 || n_phases > min_phases(h))
     return fail(MHPC_ERR_INVALID, "n_phases out of range");
-  for (const Layout& L : h->lays)
+  for (const Layout& L : h->plan.lays)
     if (L.n_wb > 0 && n_phases - 1 >= L.n_wb)
       return fail(MHPC_ERR_INVALID,
                   "phase n_phases-1 is an SRB phase: its end state cannot start a whole-body horizon");
@@ -1544,9 +1343,9 @@ int api_get_cost_gradients(Handle* h, int phase, int first, int count, double* l
   real *dlx = t.out(lx, (size_t)count * (N - 1) * n), *dph = t.out(Phix, (size_t)count * n);
   // one launch per run of problems of the same group
   if (t.e == hipSuccess)
-    for_runs(first, count, [&](int b) { return h->lid[b]; }, [&](int r0, int nb) {
+    for_runs(first, count, [&](int b) { return h->plan.lid[b]; }, [&](int r0, int nb) {
       const size_t o = (size_t)(r0 - first);
-      t.e = launch_cost_grad(h->sp, h->d, h->lid[r0], phase, N, r0, nb, dlx + o * (N - 1) * n,
+      t.e = launch_cost_grad(h->sp, h->d, h->plan.lid[r0], phase, N, r0, nb, dlx + o * (N - 1) * n,
                              dph + o * n, h->stream);
       return t.e != hipSuccess;
     });
@@ -1560,7 +1359,7 @@ int api_get_cost_gradients(Handle* h, int phase, int first, int count, double* l
 static int ensure_store(Handle* h) {
   if (h->store_valid) return MHPC_OK;
   int nbk = kPhaseBufKnots;
-  for (const Layout& L : h->lays)
+  for (const Layout& L : h->plan.lays)
     for (int p = 0; p < L.P; ++p) nbk = std::max(nbk, L.N[p]);
   const int spmax = h->sp.pmax;
   const size_t bytes = (size_t)h->sp.B * spmax * nbk * kStoreRec * sizeof(real);
@@ -1606,46 +1405,18 @@ int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const in
     if (gi < 0 || gi >= n_gaits) return fail(MHPC_ERR_INVALID, "gait index out of range");
     const int ns = steps ? steps[b] : 1;
     if (ns < 0 || ns > 1024) return fail(MHPC_ERR_INVALID, "steps must be 0..1024");
-    const mhpc_gait& gait = gaits[gi];
-    // Gait::get_next_mode / get_mode_seq / get_timings (Gait.h:48-77)
-    auto next_mode = [&](int m) {
-      for (int i = 0; i < gait.n_modes; ++i)
-        if (gait.modes[i] == m) return gait.modes[(i + 1) % gait.n_modes];
-      return -1;  // the reference falls off the end of a non-void function here
-    };
-    mhpc_problem_desc& nd = npl[b].desc;
-    const int P = nd.n_wb + nd.n_fb;
-    for (int step = 0; step < ns; ++step) {
-      const int cm = next_mode(ncm[b]);
-      if (cm < 0) return fail(MHPC_ERR_INVALID, "current mode is not in the gait");
-      ncm[b] = cm;
-      nd.mode_seq[0] = cm;
-      for (int p = 1; p < P; ++p) nd.mode_seq[p] = next_mode(nd.mode_seq[p - 1]);
-      int NK = 0;
-      for (int p = 0; p < P; ++p) {
-        const float tm = gait.timings[nd.mode_seq[p] - 1];
-        const double dt = p < nd.n_wb ? nd.dt_wb : nd.dt_fb;
-        nd.N[p] = (int)std::round((double)tm / dt);  // round(float timing / (double) dt)
-        if (nd.N[p] < 2) return fail(MHPC_ERR_INVALID, "gait timing gives a phase with N < 2");
-        if (nd.N[p] > h->nbk) return fail(MHPC_ERR_INVALID, "phase longer than the phase buffers");
-        NK += nd.N[p];
-      }
-      if (NK > MHPC_MAX_KNOTS) return fail(MHPC_ERR_INVALID, "too many knots");
-      // pidx_WB / pidx_FB: front -> back (MHPCLocomotion.cpp:111-121); kept reduced, so a
-      // long receding-horizon loop never overflows the count
-      npl[b].rot_wb = (npl[b].rot_wb + 1) % std::max(nd.n_wb, 1);
-      npl[b].rot_fb = (npl[b].rot_fb + 1) % std::max(nd.n_fb, 1);
-    }
+    PLANCHK(advance_gait, npl[b], ncm[b], gaits[gi], ns, h->nbk);
   }
-  // phases write through to their buffers in the reference: save the current layouts
+  // phases write through to their buffers in the reference: save the current layouts (also when
+  // the regrouping below is refused, as ever: the rows are the current solution's either way)
   HIPCHK(launch_store(h->sp, h->d, h->store, h->nbk, h->spmax, 1, h->stream));
-  const std::vector<ProbLayout> opl = h->pl;
-  h->pl = npl;
-  if ((rc = rebuild_groups(h))) {  // too many distinct layouts: keep the old ones
-    h->pl = opl;
-    (void)rebuild_groups(h);
-    return rc;
+  GroupPlan plan;
+  const char* msg = nullptr;
+  if ((rc = plan_groups(npl, h->pset_of, plan, &msg))) {  // too many layouts: the old ones stay
+    (void)hipStreamSynchronize(h->stream);
+    return fail(rc, msg);
   }
+  if ((rc = commit_groups(h, std::move(plan), false, &npl))) return rc;
   h->cmode = ncm;
   for (int b = 0; b < B; ++b)  // a gait step rotates the nominal: no longer k_init's
     if (h->fresh[b] && (steps ? steps[b] : 1) > 0) {
@@ -1657,11 +1428,7 @@ int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const in
   HIPCHK(launch_store(h->sp, h->d, h->store, h->nbk, h->spmax, 0, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->need_full = true;
-  h->solved = false;
-  h->x0_changed = false;
-  h->params_changed = false;
-  h->sets_changed = false;
-  h->cmd_changed = false;
+  mark_current(h);
   return MHPC_OK;
 }
 
@@ -1674,30 +1441,17 @@ int api_update_problem(Handle* h, const mhpc_gait* gait) {
 int api_set_layouts(Handle* h, int n_desc, const mhpc_problem_desc* descs, const int32_t* lop) {
   if (!h || !descs) return fail(MHPC_ERR_INVALID, "null argument");
   if (n_desc < 1 || n_desc > MAXL) return fail(MHPC_ERR_INVALID, "n_desc must be 1..MHPC_MAX_LAYOUTS");
-  for (int i = 0; i < n_desc; ++i) {
-    int rc = validate(&descs[i]);
-    if (rc) return rc;
-    if (descs[i].precision != h->desc.precision)
-      return fail(MHPC_ERR_INVALID, "a layout's precision differs from the handle's");
-    if (descs[i].vel_cmd != h->desc.vel_cmd || descs[i].height_cmd != h->desc.height_cmd)
-      return fail(MHPC_ERR_INVALID, "a layout's vel_cmd / height_cmd differs from the handle's");
-  }
+  for (int i = 0; i < n_desc; ++i) PLANCHK(check_layout_desc, descs[i], h->desc);
   const int B = h->sp.B;
   for (int b = 0; lop && b < B; ++b)
     if (lop[b] < 0 || lop[b] >= n_desc) return fail(MHPC_ERR_INVALID, "layout index out of range");
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  const std::vector<ProbLayout> opl = h->pl;
-  for (int b = 0; b < B; ++b) {
-    const mhpc_problem_desc& d = descs[lop ? lop[b] : b % n_desc];
-    h->pl[b] = ProbLayout{norm_desc(d), 0, 0};
-  }
-  int rc = rebuild_groups(h);
-  if (rc) {
-    h->pl = opl;
-    (void)rebuild_groups(h);
-    return rc;
-  }
+  std::vector<ProbLayout> npl(B);
+  for (int b = 0; b < B; ++b) npl[b] = ProbLayout{norm_desc(descs[lop ? lop[b] : b % n_desc]), 0, 0};
+  GroupPlan plan;
+  PLANCHK(plan_groups, npl, h->pset_of, plan);  // too many layouts or groups: the old ones stay
+  if (int rc = commit_groups(h, std::move(plan), false, &npl)) return rc;
   for (int b = 0; b < B; ++b) h->cmode[b] = h->pl[b].desc.mode_seq[0];
   h->store_valid = false;
   h->initialized = false;
@@ -1716,7 +1470,7 @@ static int reset_launches(Handle* h, const std::vector<int>& order, std::vector<
   SolveParams rs = h->sp;
   rs.ident = 0;
   for (int g = 0; g <= rs.ngrp; ++g) rs.go[g] = 0;
-  for (int b : order) ++rs.go[h->lid[b] + 1];
+  for (int b : order) ++rs.go[h->plan.lid[b] + 1];
   for (int g = 0; g < rs.ngrp; ++g) rs.go[g + 1] += rs.go[g];
   DevTemp<int> ti(h->stream);
   DevTemp<real> tr(h->stream);
@@ -1763,14 +1517,7 @@ int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* 
   if (!descs && n_desc != 0) return fail(MHPC_ERR_INVALID, "n_desc without descriptors");
   if (descs && (n_desc < 1 || n_desc > MAXL))
     return fail(MHPC_ERR_INVALID, "n_desc must be 1..MHPC_MAX_LAYOUTS");
-  for (int i = 0; i < n_desc; ++i) {  // the checks of mhpc_set_layouts
-    int rc = validate(&descs[i]);
-    if (rc) return rc;
-    if (descs[i].precision != h->desc.precision)
-      return fail(MHPC_ERR_INVALID, "a layout's precision differs from the handle's");
-    if (descs[i].vel_cmd != h->desc.vel_cmd || descs[i].height_cmd != h->desc.height_cmd)
-      return fail(MHPC_ERR_INVALID, "a layout's vel_cmd / height_cmd differs from the handle's");
-  }
+  for (int i = 0; i < n_desc; ++i) PLANCHK(check_layout_desc, descs[i], h->desc);
   for (int i = 0; descs && desc_of && i < n; ++i)
     if (desc_of[i] < 0 || desc_of[i] >= n_desc) return fail(MHPC_ERR_INVALID, "layout index out of range");
   const int r = x0_row(h);
@@ -1780,32 +1527,18 @@ int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* 
     if (descs) q.desc = norm_desc(descs[desc_of ? desc_of[i] : i % n_desc]);
     q.rot_wb = q.rot_fb = 0;
     // the arrays stay as they are: the layout must fit the knot stride and the phase buffers
-    const int P = q.desc.n_wb + q.desc.n_fb;
-    int NK = 0;
-    for (int p = 0; p < P; ++p) {
-      NK += q.desc.N[p];
-      if (h->store_valid && q.desc.N[p] > h->nbk)
-        return fail(MHPC_ERR_INVALID, "phase longer than the phase buffers");
-    }
-    if (NK > h->sp.NK)
-      return fail(MHPC_ERR_INVALID, "layout longer than the knot stride (a reset never grows the arrays)");
-    if (h->store_valid && P > h->spmax)
-      return fail(MHPC_ERR_INVALID, "more phases than the phase-buffer store holds");
+    PLANCHK(fits_arrays, q, h->sp.NK, h->store_valid, h->nbk, h->spmax, false);
   }
-  bool any_wb = false;
-  for (const ProbLayout& q : npl) any_wb = any_wb || q.desc.n_wb > 0;
-  if ((any_wb ? 14 : 6) != r) return fail(MHPC_ERR_INVALID, "the x0 row width would change");
+  if (x0_row_of(npl) != r) return fail(MHPC_ERR_INVALID, "the x0 row width would change");
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->pl.swap(npl);
-  int rc = rebuild_groups(h, true);
-  if (rc) {  // too many groups: nothing changed but pl
-    h->pl.swap(npl);
-    return rc;
-  }
+  GroupPlan plan;
+  PLANCHK(plan_groups, npl, h->pset_of, plan);  // too many groups: nothing changed
+  int rc = commit_groups(h, std::move(plan), true, &npl);
+  if (rc) return rc;
   std::vector<int> order(problems, problems + n);
   std::sort(order.begin(), order.end(), [&](int a, int c) {
-    return h->lid[a] != h->lid[c] ? h->lid[a] < h->lid[c] : a < c;
+    return h->plan.lid[a] != h->plan.lid[c] ? h->plan.lid[a] < h->plan.lid[c] : a < c;
   });
   std::vector<real> rows;
   if (x0) {
@@ -1817,7 +1550,7 @@ int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* 
   }
   for (int b : order) {
     h->cmode[b] = h->pl[b].desc.mode_seq[0];
-    h->kbytes[K_INIT] += h->bym[h->lid[b]].init + (h->psets.size() > 1 ? 4 * MAXP * kB : 0.0);
+    h->kbytes[K_INIT] += h->plan.bym[h->plan.lid[b]].init + (h->psets.size() > 1 ? 4 * MAXP * kB : 0.0);
     if (!h->fresh[b]) {
       h->fresh[b] = 1;
       ++h->nfresh;
@@ -1885,29 +1618,16 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
   std::vector<int> nof = d->pset_of;
   for (int i = 0; i < n; ++i) {
     const ProbLayout& q = s->pl[sp_[i]];
-    const int P = q.desc.n_wb + q.desc.n_fb;
-    int NK = 0;
-    for (int p = 0; p < P; ++p) {
-      NK += q.desc.N[p];
-      if (d->store_valid && q.desc.N[p] > d->nbk)
-        return fail(MHPC_ERR_INVALID, "phase longer than the destination's phase buffers");
-    }
-    if (NK > d->sp.NK)
-      return fail(MHPC_ERR_INVALID,
-                  "source layout longer than the destination's knot stride (a copy never grows the arrays)");
-    if (d->store_valid && P > d->spmax)
-      return fail(MHPC_ERR_INVALID, "more phases than the destination's phase-buffer store holds");
+    PLANCHK(fits_arrays, q, d->sp.NK, d->store_valid, d->nbk, d->spmax, true);
     npl[dp[i]] = q;
     nof[dp[i]] = (int)nsets.size();  // the source's set, merged below with the ones it equals
     nsets.push_back(s->psets[s->pset_of[sp_[i]]]);
   }
-  bool any_wb = false;
-  for (const ProbLayout& q : npl) any_wb = any_wb || q.desc.n_wb > 0;
-  if ((any_wb ? 14 : 6) != r) return fail(MHPC_ERR_INVALID, "the x0 row width would change");
+  if (x0_row_of(npl) != r) return fail(MHPC_ERR_INVALID, "the x0 row width would change");
   if (!d->initialized || !s->initialized)
     return fail(MHPC_ERR_STATE, "mhpc_initialize must precede mhpc_copy_problems");
   for (const Handle* h : {d, s})
-    if (h->cmd_changed || h->params_changed || h->sets_changed)
+    if (pending(h))
       return fail(MHPC_ERR_STATE,
                   "commands or parameters pending: call mhpc_initialize or mhpc_update_problem first");
   if (d->need_full != s->need_full || d->solved != s->solved)
@@ -1915,27 +1635,18 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
   merge_sets(nsets, nof);
   HIPCHK(hipSetDevice(d->device));
   HIPCHK(hipStreamSynchronize(d->stream));
-  d->pl.swap(npl);
-  d->psets.swap(nsets);
-  d->pset_of.swap(nof);
-  // Until the launch is queued the destination can go back to what it was: its host layouts and
-  // sets are swapped in, the groups rebuilt, its store created, the lists uploaded -- and on any
-  // failure swapped out again.  The per-problem host entries change only after that.
-  auto undo = [&]() {
-    d->pl.swap(npl);
-    d->psets.swap(nsets);
-    d->pset_of.swap(nof);
-  };
-  int rc = rebuild_groups(d, true);
-  if (rc) {  // too many groups: nothing changed but these three
-    undo();
-    return rc;
-  }
+  GroupPlan plan;
+  PLANCHK(plan_groups, npl, nof, plan);  // too many groups: nothing changed
+  // Until the launch is queued the destination can go back to what it was: the commit swaps its
+  // plan, layouts and sets for the new ones (plan, npl, nsets, nof then hold the old ones), its
+  // store is created, the lists uploaded -- and on any failure the old ones are committed again.
+  // The per-problem host entries change only after that.
+  int rc = commit_groups(d, std::move(plan), true, &npl, &nsets, &nof);
+  if (rc) return rc;
   // a source with phase buffers gives the destination its own, as its first update would (an
   // empty store of the new layouts' shape, which the old layouts fit as well)
   if (s->store_valid && (rc = ensure_store(d))) {
-    undo();
-    (void)rebuild_groups(d, true);
+    (void)commit_groups(d, std::move(plan), true, &npl, &nsets, &nof);
     return rc;
   }
   // the pair list and, behind it, the (run, chunk) table of one pair: one upload
@@ -1956,8 +1667,7 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
   if (t.e == hipSuccess) t.e = hipEventRecord(d->ev0, d->stream);
   if (t.e != hipSuccess) {  // nothing of the copy is queued yet
     (void)hipStreamSynchronize(d->stream);
-    undo();
-    (void)rebuild_groups(d, true);
+    (void)commit_groups(d, std::move(plan), true, &npl, &nsets, &nof);
     return dev_fail("mhpc_copy_problems", t.e);
   }
   // (d == s reads its own entries: a source is no destination, so they are the old ones)
@@ -2037,7 +1747,7 @@ int api_get_reference(Handle* h, int phase, int first, int count, double* xref) 
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(launch_export_ref(h->sp, h->d, first, count, h->stream));
   std::vector<real> buf;
-  auto ko = [&](int b) { return h->lays[h->lid[b]].ko[phase]; };
+  auto ko = [&](int b) { return h->plan.lays[h->plan.lid[b]].ko[phase]; };
   return for_runs(first, count, ko, [&](int r0, int nb) -> int {
     if (int rc = copy_rows(h, h->d.out, KS, ko(r0), N, r0, nb, buf)) return rc;
     double* o = xref + (size_t)(r0 - first) * N * n;
@@ -2049,11 +1759,11 @@ int api_get_reference(Handle* h, int phase, int first, int count, double* xref) 
 
 int api_num_layouts(Handle* h, int* n) {
   if (!h || !n) return fail(MHPC_ERR_INVALID, "null argument");
-  *n = h->nlay;  // (sp.ngrp counts (layout, parameter set) pairs)
+  *n = h->plan.nlay;  // (sp.ngrp counts (layout, parameter set) pairs)
   return MHPC_OK;
 }
 
-// the row length of get_scalars' V_phase / dV_phase (rebuild_groups: sp.pmax)
+// the row length of get_scalars' V_phase / dV_phase (plan_groups: pmax)
 int api_max_phases(Handle* h, int* n) {
   if (!h || !n) return fail(MHPC_ERR_INVALID, "null argument");
   *n = h->sp.pmax;

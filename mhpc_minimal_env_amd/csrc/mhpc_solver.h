@@ -27,11 +27,19 @@
 //   cmd    [B][2]              user command (vel, height) of each problem (mhpc_set_commands),
 //          indexed by problem number: it follows a problem through every regrouping.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "mhpc_real.h"
 
 #include "../../include/mhpc_capi.h"
+
+// (plain g++ compiles this header too: mhpc_plan.h and its host check, tests/native)
+#if defined(__HIPCC__)
+#define MHPC_HOST_DEVICE __host__ __device__
+#else
+#define MHPC_HOST_DEVICE
+#endif
 
 namespace MHPC_NS {
 
@@ -43,10 +51,10 @@ constexpr int PS = 176;       // doubles per knot in par: Jacobians + 14 cost de
 // knot k at (c NK + k) 9 -- then the cost derivatives [NK][14].  A direction's values of
 // consecutive knots are contiguous, so the partials' lanes (consecutive knots) store whole
 // lines; the sweep's lane walks its own column block backwards, one 72-byte piece per knot.
-__host__ __device__ inline size_t par_col(int NK, int b, int c, int kk) {
+MHPC_HOST_DEVICE inline size_t par_col(int NK, int b, int c, int kk) {
   return (size_t)b * NK * PS + ((size_t)c * NK + kk) * 9;
 }
-__host__ __device__ inline size_t par_jac(int NK, int b, int kk) {
+MHPC_HOST_DEVICE inline size_t par_jac(int NK, int b, int kk) {
   return (size_t)b * NK * PS + (size_t)PS_JAC * NK + (size_t)kk * 14;
 }
 constexpr int MAXP = MHPC_MAX_PHASES;

@@ -15,7 +15,7 @@ Reported per batch and call, median and min / max over the repeats:
              memory_reset, which runs beside them on the second stream: their sum, an upper bound
              of the critical path.  For mhpc_initialize it is k_init alone: its batch-wide
              k_reset_arrays on the second stream is not bracketed.
-  host_ms    wall_ms - device_ms: validation, rebuild_groups (a map over the batch's
+  host_ms    wall_ms - device_ms: validation, plan_groups (a map over the batch's
              descriptors), the uploads of the group table, the grouped order and the list, the
              stream synchronisations.  An estimate: the device sum counts overlapped launches
              twice, so it can exceed the wall time of a reset of many problems.
