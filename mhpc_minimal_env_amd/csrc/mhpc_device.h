@@ -1,5 +1,6 @@
 // Device-side helpers shared by the solve kernels: cost weights, references, reduced
-// barrier, foothold planner.  Every helper restates reference code cited at its definition.
+// barrier, running and terminal costs, phase transition, foothold planner.  Every helper
+// restates reference code cited at its definition.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -289,6 +290,76 @@ static __device__ void fb_term_ref(const Cmd& cm, real pos, real* rx) {
   MHPC_NO_FMA_F32
   rx[0] = pos; rx[1] = cm.height; rx[2] = 0; rx[3] = cm.vel; rx[4] = 0; rx[5] = 0;
 }
+
+// Terminal cost of a WB phase (CostBase.cpp:37-47, SinglePhase.cpp:251-275): 0.5 e' Qf e at
+// the terminal state x against the reference at position refT and, at the end of a touchdown
+// phase (modes 2, 4), the constraint value *h and the AL term 50 ((sigma h / 2)^2 + lambda h)
+// of phase p.  *h is written only there: the caller starts it at 0.  sigma and lambda are
+// loaded inside the AL branch (st is not read otherwise); the caller adds the result to the
+// phase value in its own contraction state.
+static __device__ __forceinline__ acc wb_terminal_cost(const CostParams& cw, const Cmd& cm, int mode,
+                                                       real refT, const real* x, bool AL_active,
+                                                       const ProbState* st, int p, real* h) {
+  MHPC_NO_FMA_COST
+  real rx[14];
+  wb_term_ref(cm, mode, refT, rx);
+  acc Phi = 0;
+  for (int i = 0; i < 14; ++i) { const real e = x[i] - rx[i]; Phi += e * cw.wQf[mode - 1][i] * e; }
+  Phi = Phi * acc(0.5);
+  if (ntc_of(mode, true)) {
+    *h = mode == 2 ? wb_touchdown_value<kFront>(x) : wb_touchdown_value<kBack>(x);
+    if (AL_active) {
+      const acc sg = st->sigma[p], lam = st->lambda[p];
+      const acc sh2 = sg * *h / 2;
+      Phi += 50 * (sh2 * sh2 + lam * *h);
+    }
+  }
+  return Phi;
+}
+
+// Terminal cost of an SRB phase (CostBase.cpp:37-47): 0.5 (x - xr)' Qf (x - xr)
+static __device__ __forceinline__ acc fb_terminal_cost(const CostParams& cw, const Cmd& cm, int mode,
+                                                       real refT, const real* x) {
+  MHPC_NO_FMA_COST
+  real rx[6];
+  fb_term_ref(cm, refT, rx);
+  acc Phi = 0;
+  for (int i = 0; i < 6; ++i) { const real e = x[i] - rx[i]; Phi += e * cw.fQf[mode - 1][i] * e; }
+  return Phi * acc(0.5);
+}
+
+// Phase transition after the terminal state of WB phase p (MultiPhaseDDP.cpp:351-379), when a
+// phase follows: the impact map after a touchdown phase (modes 2, 4), then the projection of
+// the 14 WB states to the 6 SRB states when the next phase is an SRB one.  (serial_rollout,
+// mhpc_kernels.hip, spells the same steps out: it hands out the state between the two.)
+static __device__ __forceinline__ void wb_phase_transition(const Layout& L, int p, real* x) {
+  const int mode = L.mode[p];
+  if (p + 1 < L.P) {
+    if (mode == 2 || mode == 4) {
+      real xp[14], lam[2];
+      wb_impact<real>(x, mode == 2 ? kFront : kBack, xp, lam);
+      for (int i = 0; i < 14; ++i) x[i] = xp[i];
+    }
+    if (p + 1 >= L.n_wb) {
+      const real t0 = x[0], t1 = x[1], t2 = x[2], t7 = x[7], t8 = x[8], t9 = x[9];
+      x[0] = t0; x[1] = t1; x[2] = t2; x[3] = t7; x[4] = t8; x[5] = t9;
+    }
+  }
+}
+
+// The knot loops keep the sin / cos constants in registers (SinCosK): VGPR copies, opaque to
+// the compiler, so it keeps them live instead of rematerialising each with two s_mov per use.
+// (A macro: through a function taking the struct by reference the line search's multiplies
+// came out with their operands commuted -- equal results, but not the same kernel text.)
+#ifndef MHPC_RO_VCONST
+#define MHPC_RO_VCONST 1
+#endif
+#if MHPC_RO_VCONST && !defined(MHPC_FP32)
+#define MHPC_PIN_VGPRS(K) \
+  _Pragma("unroll") for (int i_ = 0; i_ < 15; ++i_) asm volatile("" : "+v"((K).c[i_]))
+#else
+#define MHPC_PIN_VGPRS(K) do { } while (0)
+#endif
 
 // FootholdPlanner::get_foothold_location (FootholdPlan.h:26-50), velcmd 1.5 / ground
 // -0.404 hard-coded by the reference (MHPCLocomotion.cpp:25).

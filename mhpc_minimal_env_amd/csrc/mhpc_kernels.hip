@@ -92,10 +92,6 @@ constexpr int RO_RING_PAIR = MHPC_RO_RING_PAIR;
 #ifndef MHPC_RO_PREFETCH
 #define MHPC_RO_PREFETCH 1
 #endif
-// The line search's dynamics keeps the sin / cos constants in registers (SinCosK)
-#ifndef MHPC_RO_VCONST
-#define MHPC_RO_VCONST 1
-#endif
 
 // native 2-wide vector (HIP's double2 class defeats register promotion of arrays of it)
 typedef real sreal2 __attribute__((ext_vector_type(2)));
@@ -302,13 +298,6 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
   // wave 1: store the lane's ring record (n reals, n even) to knot kk of its slot with
   // 2-wide stores (records are aligned to them: KS * sizeof(real))
   auto store_rec = [&](const real* r, int n, int kk, bool running) __attribute__((always_inline)) {
-#ifdef MHPC_RO_NOSTORE  // timing experiments only: results are wrong
-#if MHPC_RO_NOSTORE == 1
-    if (kk >= 0) return;
-#else
-    n = n < 2 * MHPC_RO_NOSTORE ? n : 2 * MHPC_RO_NOSTORE;  // the first pieces only
-#endif
-#endif
     if (running && !full && j >= sp.ro_store && j != nc - 1) return;  // see RO_STORE_FIRST
     real2* o = reinterpret_cast<real2*>(traj_ptr(sp, d, b, slot, kk));
 #pragma unroll
@@ -322,13 +311,8 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
   // the hand-over instead of heading the next knot's dependent chain; the next chunk is
   // dropped into the stage right after the last knot of a chunk has read it.
   real pK[28], pX[14], pU[4], pD[4];
-  // sin / cos constants: VGPR copies (opaque to the compiler, so it keeps them live instead of
-  // rematerialising each with two s_mov per use in the knot loop)
-  SinCosK scK = kSinCosK;
-#if MHPC_RO_VCONST && !defined(MHPC_FP32)
-#pragma unroll
-  for (int i = 0; i < 15; ++i) asm volatile("" : "+v"(scK.c[i]));
-#endif
+  SinCosK scK = kSinCosK;  // sin / cos constants of the knot loop, in VGPRs
+  MHPC_PIN_VGPRS(scK);
   auto prefetch = [&](bool wb, int kk) __attribute__((always_inline)) {
     const int kcc = kk & ((wb ? Stage<true>::CH : Stage<false>::CH) - 1);
     const int KP = wb ? Stage<true>::KP : Stage<false>::KP, TP = wb ? Stage<true>::TP : Stage<false>::TP;
@@ -495,18 +479,7 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
   };
   // phase transition after the phase's terminal state (MultiPhaseDDP.cpp:351-379)
   auto transition = [&](auto WBc, int p) __attribute__((always_inline)) {
-    const int mode = L.mode[p];
-    if (decltype(WBc)::value && p + 1 < L.P) {
-      if (mode == 2 || mode == 4) {
-        real xp[14], lam[2];
-        wb_impact<real>(x, mode == 2 ? kFront : kBack, xp, lam);
-        for (int i = 0; i < 14; ++i) x[i] = xp[i];
-      }
-      if (p + 1 >= L.n_wb) {
-        const real t0 = x[0], t1 = x[1], t2 = x[2], t7 = x[7], t8 = x[8], t9 = x[9];
-        x[0] = t0; x[1] = t1; x[2] = t2; x[3] = t7; x[4] = t8; x[5] = t9;
-      }
-    }
+    if (decltype(WBc)::value) wb_phase_transition(L, p, x);
   };
   // cost side, phase constants: ReB parameters and the staged position references
   struct CostPhase {
@@ -553,15 +526,6 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
 #pragma unroll
     for (int i = 0; i < RING_W; ++i) r[i] = i < n ? ring[sl][i][lane] : real(0.0);
   };
-  // terminal cost of an SRB phase (CostBase.cpp:37-47): 0.5 (x - xr)' Qf (x - xr)
-  auto srb_terminal_cost = [&](int mode, real refT, const real* xe) __attribute__((always_inline)) {
-    MHPC_NO_FMA_COST
-    real rx[6];
-    fb_term_ref(cm, refT, rx);
-    acc Phi = 0;
-    for (int i = 0; i < 6; ++i) { const real e = xe[i] - rx[i]; Phi += e * cw.fQf[mode - 1][i] * e; }
-    return Phi * acc(0.5);
-  };
   // cost side, phase end: terminal cost, touchdown constraint, AL term (SinglePhase.cpp
   // :251-275), the phase value into sV / sH and the terminal record's store
   auto cost_terminal = [&](auto WBc, int p, const CostPhase& c, const real* xe, acc V) __attribute__((always_inline)) {
@@ -573,24 +537,8 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
       return;
     }
     real h = 0;
-    if (wb) {
-      real rx[14];
-      wb_term_ref(cm, mode, c.refT, rx);
-      acc Phi = 0;
-      for (int i = 0; i < 14; ++i) { const real e = xe[i] - rx[i]; Phi += e * cw.wQf[mode - 1][i] * e; }
-      Phi = Phi * acc(0.5);
-      if (ntc_of(mode, true)) {
-        h = mode == 2 ? wb_touchdown_value<kFront>(xe) : wb_touchdown_value<kBack>(xe);
-        if (sp.AL_active) {
-          const acc sg = st->sigma[p], lam = st->lambda[p];
-          const acc sh2 = sg * h / 2;
-          Phi += 50 * (sh2 * sh2 + lam * h);
-        }
-      }
-      V += Phi;
-    } else {
-      V += srb_terminal_cost(mode, c.refT, xe);
-    }
+    if (wb) V += wb_terminal_cost(cw, cm, mode, c.refT, xe, sp.AL_active, st, p, &h);
+    else V += fb_terminal_cost(cw, cm, mode, c.refT, xe);
     J += V;
     viol2 += acc(h) * h;
     sV[p][lane] = V;
@@ -842,171 +790,35 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
 }
 
 // ============================================================================================
-// k_eps_rollout: forward_sweep_dynamics_only (SinglePhase.cpp:117-144) at an arbitrary list
-// of step sizes from the current nominal, gains and AL / ReB state, costs only (no stores,
-// no selection): the trial rollouts of forward_iteration without the Armijo stop -- the
-// C2 workload (256 concurrent rollouts of one nominal).  Lane = (problem, step size).
+// serial_rollout: one lane's state x through phases [0, Pn) of problem b --
+// forward_sweep_dynamics_only (SinglePhase.cpp:117-144) from the problem's current nominal,
+// gains and AL / ReB state: u = (u_nom + eps du) + K (x - x_nom), x+ = x + dt f(x, u), running
+// and terminal costs, phase transitions (MultiPhaseDDP.cpp:351-379).  The one serial rollout
+// beside k_rollout's pipelined knot loop: k_eps_rollout and k_policy_rollout are index
+// arithmetic around it, so their costs from the same state and step size are equal bit for bit
+// (tests/test_gpu_policy.py).  No memory index depends on a state value: a diverged lane
+// produces non-finite numbers and nothing worse.
+// Returns J (the sum of the rolled phases' costs) and viol2 (the sum of their h^2).  Optional
+// outputs:
+// xe [14]: the state after the last rolled phase's transition -- after a WB phase the full state
+// after wb_impact and before the SRB projection, after an SRB phase its 6 entries and zeros,
+// after the problem's last phase (no transition) that phase's terminal state.
+// REC: rec, the records of phase rec_p = Pn - 1 -- entry j (x 0..13, u 14..17, y 18..21) of knot
+// k at rec[(k * PREC_W + j) * rs]; the last knot has no u, y (not written), nor have SRB knots a y.
 // ============================================================================================
-__global__ __launch_bounds__(64) void k_eps_rollout(SolveParams sp, DevBufs d, int n_eps,
-                                                    const real* eps_v, real* Jo,
-                                                    real* vo) {
-  // blocks by group, lanes = (problem of the group, step size)
-  long t0 = 0;
-  const int g = block_group_items(sp, nullptr, n_eps, blockIdx.x, 64, &t0);
-  if (g < 0) return;
-  const Layout& L = layout_of(d, g);
-  const CostParams& cw = params_of(d, g);
-  const long tg = t0 + threadIdx.x;  // item within the group
-  if (tg >= (long)(sp.go[g + 1] - sp.go[g]) * n_eps) return;
-  const int pos = sp.go[g] + (int)(tg / n_eps), e = (int)(tg % n_eps);
-  const int b = prob_at(sp, d, pos);
-  const long t = (long)b * n_eps + e;  // output index [problem][step size]
-  const ProbState* st = &d.st[b];
-  const Cmd cm = cmd_of(d, b);
-  const int nom = st->nom_slot;
-  const real eps = eps_v[e];
-  const bool reb = st->reb_active != 0;
-  real x[14];
-  const real* x0 = d.x0 + (size_t)b * 14;
-  for (int i = 0; i < 14; ++i) x[i] = x0[i];
-  acc J = 0, viol2 = 0;
-  for (int p = 0; p < L.P; ++p) {
-    const int mode = L.mode[p], N = L.N[p], ko = L.ko[p];
-    const real dt = L.dt[p];
-    const real* refpos = d.refpos + (size_t)b * sp.NK + ko;
-    acc V = 0;
-    real h = 0;
-    if (p < L.n_wb) {
-      const real delta = st->delta[p], etq = st->eps_tq[p], egr = st->eps_grf[p];
-      for (int k = 0; k < N - 1; ++k) {
-        const real* nk = traj_ptr(sp, d, b, nom, ko + k);
-        const real* Kk = d.K + ((size_t)b * sp.NK + ko + k) * 56;
-        const real* duk = d.du + ((size_t)b * sp.NK + ko + k) * 4;
-        real u[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const real fb = fb_dot<14>(Kk + i * 14, x, nk);
-          u[i] = (nk[14 + i] + eps * duk[i]) + fb;
-        }
-        real xd[14], y[4];
-        wb_dynamics<real>(x, u, mode, xd, y);
-        V += wb_running_cost(cw, cm, mode, dt, refpos[k], x, u, y, reb, delta, etq, egr);
-#pragma unroll
-        for (int i = 0; i < 14; ++i) x[i] = x[i] + xd[i] * dt;
-      }
-      {
-        MHPC_NO_FMA_COST
-        real rx[14];
-        wb_term_ref(cm, mode, refpos[N - 1], rx);
-        acc Phi = 0;
-        for (int i = 0; i < 14; ++i) { const real ee = x[i] - rx[i]; Phi += ee * cw.wQf[mode - 1][i] * ee; }
-        Phi = Phi * acc(0.5);
-        if (ntc_of(mode, true)) {
-          h = mode == 2 ? wb_touchdown_value<kFront>(x) : wb_touchdown_value<kBack>(x);
-          if (sp.AL_active) {
-            const acc sg = st->sigma[p], lam = st->lambda[p];
-            const acc sh2 = sg * h / 2;
-            Phi += 50 * (sh2 * sh2 + lam * h);
-          }
-        }
-        V += Phi;
-      }
-      if (p + 1 < L.P) {
-        if (mode == 2 || mode == 4) {
-          real xp[14], lam[2];
-          wb_impact<real>(x, mode == 2 ? kFront : kBack, xp, lam);
-          for (int i = 0; i < 14; ++i) x[i] = xp[i];
-        }
-        if (p + 1 >= L.n_wb) {
-          const real t0 = x[0], t1 = x[1], t2 = x[2], t7 = x[7], t8 = x[8], t9 = x[9];
-          x[0] = t0; x[1] = t1; x[2] = t2; x[3] = t7; x[4] = t8; x[5] = t9;
-        }
-      }
-    } else {
-      real f[4], sc[2];
-      plan_foothold(x, dt * N, mode, f);
-      srb_contact(mode, sc);
-      for (int k = 0; k < N - 1; ++k) {
-        const real* nk = traj_ptr(sp, d, b, nom, ko + k);
-        const real* Kk = d.K + ((size_t)b * sp.NK + ko + k) * 56;
-        const real* duk = d.du + ((size_t)b * sp.NK + ko + k) * 4;
-        real u[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const real fb = fb_dot<6>(Kk + i * 6, x, nk);
-          u[i] = (nk[6 + i] + eps * duk[i]) + fb;
-        }
-        real xd[6];
-        srb_dynamics(x, u, f, sc, xd);
-        V += fb_running_cost(cw, cm, mode, dt, refpos[k], x, u);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) x[i] = x[i] + xd[i] * dt;
-      }
-      real rx[6];
-      fb_term_ref(cm, refpos[N - 1], rx);
-      acc Phi = 0;
-      for (int i = 0; i < 6; ++i) { const real ee = x[i] - rx[i]; Phi += ee * cw.fQf[mode - 1][i] * ee; }
-      V += Phi * acc(0.5);
-    }
-    J += V;
-    viol2 += acc(h) * h;
-  }
-  Jo[t] = real(J);
-  vo[t] = real(sqrt(viol2));
-}
-
-// ============================================================================================
-// k_policy_rollout: the solved feedback policy u = u_nom + K (x - x_nom) run from start states
-// of the caller's choosing -- the reference's set_initial_condition(x) followed by
-// forward_sweep_dynamics_only(0) (SinglePhase.cpp:117-144, MultiPhaseDDP.cpp:56-76).  Lane =
-// (problem, sample), the sample index fastest: the lanes of a wave read one problem's nominal
-// record, K, du and refpos at wave-uniform addresses (a wave straddles two problems when
-// n_s is no multiple of 64); blocks by group as k_eps_rollout.  Problems outside
-// [b0, b0 + nb) are skipped.  xs [nb][n_s][14] start states, dx (double [nb][n_s][14], or null)
-// added to them in double; n_phases phases are rolled (0: every phase of the problem); eps
-// is 0 at run time, kept in the control so that it rounds as k_eps_rollout's (the sign of a
-// zero included): the per-knot body is k_eps_rollout's, device function for device function
-// and operation for operation, and J, viol equal mhpc_rollout_costs at step size 0 from the
-// same state bit for bit (tests/test_gpu_policy.py).  No memory index depends on a state
-// value: a diverged sample produces non-finite numbers and nothing worse.
-// Outputs, each optional: Jo, vo [nb][n_s] (sum of the rolled phases' costs, sqrt of the sum of
-// their h^2); xe [nb][n_s][14], the state after the last rolled phase's transition -- after a WB
-// phase the full state after wb_impact and before the SRB projection, after an SRB phase its 6
-// entries and zeros, after the problem's last phase (no transition) that phase's terminal
-// state; xe may alias xs (mhpc_advance_x0): a lane reads its row before it writes it.
-// REC: rec [nb][N][PREC_W][n_s], the records of phase rec_p, which is then the last phase
-// rolled -- entry j (x 0..13, u 14..17, y 18..21) of knot k, the sample fastest so that a
-// wave's stores of one entry coalesce; the last knot has no u, y (not written), nor have SRB
-// knots a y.
-// ============================================================================================
+struct RolloutCost {
+  acc J, viol2;
+};
 template <bool REC>
-__global__ __launch_bounds__(64) void k_policy_rollout(SolveParams sp, DevBufs d, int n_s, int b0,
-                                                       int nb, const real* xs, const double* dx,
-                                                       real eps, int n_phases, int rec_p, real* Jo,
-                                                       real* vo, real* xe_v, real* rec_v) {
-  long t0 = 0;
-  const int g = block_group_items(sp, nullptr, n_s, blockIdx.x, 64, &t0);
-  if (g < 0) return;
-  const Layout& L = layout_of(d, g);
-  const CostParams& cw = params_of(d, g);
-  const long tg = t0 + threadIdx.x;  // item within the group
-  if (tg >= (long)(sp.go[g + 1] - sp.go[g]) * n_s) return;
-  const int pos = sp.go[g] + (int)(tg / n_s), e = (int)(tg % n_s);
-  const int b = prob_at(sp, d, pos);
-  if (b < b0 || b >= b0 + nb) return;
-  const size_t t = (size_t)(b - b0) * n_s + e;  // sample index [problem of the range][sample]
-  real x[14];
-  for (int i = 0; i < 14; ++i) x[i] = xs[t * 14 + i];
-  if (dx)
-    for (int i = 0; i < 14; ++i) x[i] = real((double)x[i] + dx[t * 14 + i]);
-  const int Pn = REC ? rec_p + 1 : (n_phases > 0 && n_phases < L.P ? n_phases : L.P);
+static __device__ __forceinline__ RolloutCost serial_rollout(const SolveParams& sp, const DevBufs& d,
+                                                             const Layout& L, const CostParams& cw,
+                                                             int b, real* x, real eps, int Pn,
+                                                             real* xe, int rec_p, real* rec,
+                                                             size_t rs) {
   const ProbState* st = &d.st[b];
   const Cmd cm = cmd_of(d, b);
   const int nom = st->nom_slot;
   const bool reb = st->reb_active != 0;
-  real* const xe = xe_v ? xe_v + t * 14 : nullptr;
-  real* const rec = REC ? rec_v + (size_t)(b - b0) * L.N[rec_p] * PREC_W * n_s + e : nullptr;
-  const size_t rs = (size_t)n_s;  // stride of one record entry: the sample index is fastest
   acc J = 0, viol2 = 0;
   for (int p = 0; p < Pn; ++p) {
     const int mode = L.mode[p], N = L.N[p], ko = L.ko[p];
@@ -1041,30 +853,16 @@ __global__ __launch_bounds__(64) void k_policy_rollout(SolveParams sp, DevBufs d
         real* r = rec + (size_t)(N - 1) * PREC_W * rs;
         for (int i = 0; i < 14; ++i) r[i * rs] = x[i];
       }
-      {
-        MHPC_NO_FMA_COST
-        real rx[14];
-        wb_term_ref(cm, mode, refpos[N - 1], rx);
-        acc Phi = 0;
-        for (int i = 0; i < 14; ++i) { const real ee = x[i] - rx[i]; Phi += ee * cw.wQf[mode - 1][i] * ee; }
-        Phi = Phi * acc(0.5);
-        if (ntc_of(mode, true)) {
-          h = mode == 2 ? wb_touchdown_value<kFront>(x) : wb_touchdown_value<kBack>(x);
-          if (sp.AL_active) {
-            const acc sg = st->sigma[p], lam = st->lambda[p];
-            const acc sh2 = sg * h / 2;
-            Phi += 50 * (sh2 * sh2 + lam * h);
-          }
-        }
-        V += Phi;
-      }
+      V += wb_terminal_cost(cw, cm, mode, refpos[N - 1], x, sp.AL_active, st, p, &h);
+      // wb_phase_transition, spelled out: xe is the state between its two halves, and with the
+      // helper inlined here as well both rollout kernels measured 1-3 % slower
+      // (profiles/forward_refactor_ab.md)
       if (p + 1 < L.P) {
         if (mode == 2 || mode == 4) {
           real xp[14], lam[2];
           wb_impact<real>(x, mode == 2 ? kFront : kBack, xp, lam);
           for (int i = 0; i < 14; ++i) x[i] = xp[i];
         }
-        // the robot's state after the last rolled phase: post-impact, before the SRB projection
         if (xe && p == Pn - 1)
           for (int i = 0; i < 14; ++i) xe[i] = x[i];
         if (p + 1 >= L.n_wb) {
@@ -1105,6 +903,9 @@ __global__ __launch_bounds__(64) void k_policy_rollout(SolveParams sp, DevBufs d
       }
       if (xe && p == Pn - 1)
         for (int i = 0; i < 14; ++i) xe[i] = i < 6 ? x[i] : real(0.0);
+      // fb_terminal_cost's sum in this function's contraction state: the fp64 build fuses its
+      // multiply-adds here and has always done, so the helper, which does not,
+      // would change the last bits of every cost this rollout returns
       real rx[6];
       fb_term_ref(cm, refpos[N - 1], rx);
       acc Phi = 0;
@@ -1114,9 +915,76 @@ __global__ __launch_bounds__(64) void k_policy_rollout(SolveParams sp, DevBufs d
     J += V;
     viol2 += acc(h) * h;
   }
-  if (Jo) Jo[t] = real(J);
-  if (vo) vo[t] = real(sqrt(viol2));
+  return {J, viol2};
 }
+
+// The lane's (group, problem, item) in a launch of n items per problem, 64 lanes a block, blocks
+// by group (block_group_items), the item index fastest; false: the lane has none.
+static __device__ __forceinline__ bool lane_item(const SolveParams& sp, const DevBufs& d, int n,
+                                                 int* g, int* b, int* e) {
+  long t0 = 0;
+  *g = block_group_items(sp, nullptr, n, blockIdx.x, 64, &t0);
+  if (*g < 0) return false;
+  const long tg = t0 + threadIdx.x;  // item within the group
+  if (tg >= (long)(sp.go[*g + 1] - sp.go[*g]) * n) return false;
+  *b = prob_at(sp, d, sp.go[*g] + (int)(tg / n));
+  *e = (int)(tg % n);
+  return true;
+}
+
+// k_eps_rollout: the trial rollouts of forward_iteration without the Armijo stop, at an
+// arbitrary list of step sizes from x0, costs only (no stores, no selection) -- the C2 workload
+// (256 concurrent rollouts of one nominal).  Lane = (problem, step size).
+__global__ __launch_bounds__(64) void k_eps_rollout(SolveParams sp, DevBufs d, int n_eps,
+                                                    const real* eps_v, real* Jo,
+                                                    real* vo) {
+  int g, b, e;
+  if (!lane_item(sp, d, n_eps, &g, &b, &e)) return;
+  const long t = (long)b * n_eps + e;  // output index [problem][step size]
+  real x[14];
+  const real* x0 = d.x0 + (size_t)b * 14;
+  for (int i = 0; i < 14; ++i) x[i] = x0[i];
+  const Layout& L = layout_of(d, g);
+  const RolloutCost c = serial_rollout<false>(sp, d, L, params_of(d, g), b, x, eps_v[e], L.P,
+                                              nullptr, 0, nullptr, 0);
+  Jo[t] = real(c.J);
+  vo[t] = real(sqrt(c.viol2));
+}
+
+// k_policy_rollout: the solved feedback policy u = u_nom + K (x - x_nom) run from start states
+// of the caller's choosing -- the reference's set_initial_condition(x) followed by
+// forward_sweep_dynamics_only(0) (MultiPhaseDDP.cpp:56-76).  Lane = (problem, sample), the
+// sample index fastest: the lanes of a wave read one problem's nominal record, K, du and refpos
+// at wave-uniform addresses (a wave straddles two problems when n_s is no multiple of 64).
+// Problems outside [b0, b0 + nb) are skipped.  xs [nb][n_s][14] start states, dx (double
+// [nb][n_s][14], or null) added to them in double; n_phases phases are rolled (0: every phase
+// of the problem); eps is 0 at run time, kept in the control so that it rounds as
+// k_eps_rollout's (the sign of a zero included).  Outputs, each optional: Jo, vo [nb][n_s];
+// xe [nb][n_s][14], which may alias xs (mhpc_advance_x0): a lane reads its row before it
+// writes it.  REC: rec [nb][N][PREC_W][n_s] of phase rec_p, which is then the last phase
+// rolled; the sample fastest so that a wave's stores of one entry coalesce.
+template <bool REC>
+__global__ __launch_bounds__(64) void k_policy_rollout(SolveParams sp, DevBufs d, int n_s, int b0,
+                                                       int nb, const real* xs, const double* dx,
+                                                       real eps, int n_phases, int rec_p, real* Jo,
+                                                       real* vo, real* xe_v, real* rec_v) {
+  int g, b, e;
+  if (!lane_item(sp, d, n_s, &g, &b, &e)) return;
+  if (b < b0 || b >= b0 + nb) return;
+  const size_t t = (size_t)(b - b0) * n_s + e;  // sample index [problem of the range][sample]
+  real x[14];
+  for (int i = 0; i < 14; ++i) x[i] = xs[t * 14 + i];
+  if (dx)
+    for (int i = 0; i < 14; ++i) x[i] = real((double)x[i] + dx[t * 14 + i]);
+  const Layout& L = layout_of(d, g);
+  const int Pn = REC ? rec_p + 1 : (n_phases > 0 && n_phases < L.P ? n_phases : L.P);
+  real* const rec = REC ? rec_v + (size_t)(b - b0) * L.N[rec_p] * PREC_W * n_s + e : nullptr;
+  const RolloutCost c = serial_rollout<REC>(sp, d, L, params_of(d, g), b, x, eps, Pn,
+                                            xe_v ? xe_v + t * 14 : nullptr, rec_p, rec, (size_t)n_s);
+  if (Jo) Jo[t] = real(c.J);
+  if (vo) vo[t] = real(sqrt(c.viol2));
+}
+
 
 // ============================================================================================
 // k_cost_grad: the running-cost gradient lx of every knot and the terminal-cost gradient
@@ -1595,10 +1463,7 @@ __global__ __launch_bounds__(64) void k_init(SolveParams sp, DevBufs d, int warm
   const real qnom[4] = {PI / 4, -PI * 7 / 12, PI / 4, -PI * 7 / 12};
   const real Kp[4] = {5 * real(8.0), 5 * real(1.0), 5 * real(12.0), 5 * real(10.0)};
   SinCosK scK = kSinCosK;  // VGPR copies (see k_rollout)
-#if MHPC_RO_VCONST && !defined(MHPC_FP32)
-#pragma unroll
-  for (int i = 0; i < 15; ++i) asm volatile("" : "+v"(scK.c[i]));
-#endif
+  MHPC_PIN_VGPRS(scK);
   for (int p = 0; p < L.n_wb; ++p) {
     const int mode = L.mode[p], N = L.N[p], ko = L.ko[p];
     const real dt = L.dt[p];
@@ -1664,18 +1529,7 @@ __global__ __launch_bounds__(64) void k_init(SolveParams sp, DevBufs d, int warm
     }
     real* oe = traj_ptr(sp, d, b, 0, ko + N - 1);
     if (!back) for (int i = 0; i < 14; ++i) oe[i] = x[i];
-    // phase transition exactly as the forward sweep does it (MultiPhaseDDP.cpp:351-379)
-    if (p + 1 < L.P) {
-      if (mode == 2 || mode == 4) {
-        real xp[14], lam[2];
-        wb_impact<real>(x, mode == 2 ? kFront : kBack, xp, lam);
-        for (int i = 0; i < 14; ++i) x[i] = xp[i];
-      }
-      if (p + 1 >= L.n_wb) {
-        const real t0 = x[0], t1 = x[1], t2 = x[2], t7 = x[7], t8 = x[8], t9 = x[9];
-        x[0] = t0; x[1] = t1; x[2] = t2; x[3] = t7; x[4] = t8; x[5] = t9;
-      }
-    }
+    wb_phase_transition(L, p, x);  // the forward sweep's
   }
   // SRB phases: the reference's first forward_sweep(0) rolls them out with the initial
   // (zero) controls and zero gains -- u = (0 + 0*0) + sum 0*(x - 0) = +0 exactly -- so the
@@ -1757,28 +1611,9 @@ __global__ __launch_bounds__(64) void k_cost(SolveParams sp, DevBufs d, int al_i
     real h = 0;
     for (int k = 0; k < N - 1; ++k) V += sc[ko + k];
     const real* x = traj_ptr(sp, d, b, nom, ko + N - 1);
-    if (p < L.n_wb) {
-      real rx[14];
-      wb_term_ref(cm, mode, refpos[ko + N - 1], rx);
-      acc Phi = 0;
-      for (int i = 0; i < 14; ++i) { const real e = x[i] - rx[i]; Phi += e * cw.wQf[mode - 1][i] * e; }
-      Phi = Phi * acc(0.5);
-      if (ntc_of(mode, true)) {
-        h = mode == 2 ? wb_touchdown_value<kFront>(x) : wb_touchdown_value<kBack>(x);
-        if (sp.AL_active) {
-          const acc s = st->sigma[p], lam = st->lambda[p];
-          const acc sh2 = s * h / 2;
-          Phi += 50 * (sh2 * sh2 + lam * h);
-        }
-      }
-      V += Phi;
-    } else {
-      real rx[6];
-      fb_term_ref(cm, refpos[ko + N - 1], rx);
-      acc Phi = 0;
-      for (int i = 0; i < 6; ++i) { const real e = x[i] - rx[i]; Phi += e * cw.fQf[mode - 1][i] * e; }
-      V += Phi * acc(0.5);
-    }
+    const real refT = refpos[ko + N - 1];
+    if (p < L.n_wb) V += wb_terminal_cost(cw, cm, mode, refT, x, sp.AL_active, st, p, &h);
+    else V += fb_terminal_cost(cw, cm, mode, refT, x);
     sV[p] = V;
     sH[p] = h;
   }
@@ -1936,12 +1771,7 @@ static __device__ __forceinline__ void eval_sin_cos_n(int n, bool vk, const real
   // the knot loops' VGPR copy of the constants (k_rollout); lanes past the last group run the
   // functions too, on zeros: the ballot inside is over the whole wave
   SinCosK scK = kSinCosK;
-#if !defined(MHPC_FP32)
-  if (vk) {
-#pragma unroll
-    for (int i = 0; i < 15; ++i) asm volatile("" : "+v"(scK.c[i]));
-  }
-#endif
+  if (vk) MHPC_PIN_VGPRS(scK);
   const bool live = (g + 1) * N <= n;
   real v[N], s[N], c[N];
 #pragma unroll
@@ -2086,24 +1916,15 @@ static RoShape ro_shape(const SolveParams& sp) {
   const int ppw = 64 / sp.n_cand;
   r.nblk = (int)grid_of(sp, ppw);
   const int ncu = sp.ncu;
-#ifdef MHPC_RO_PIPE
-  r.pipe = MHPC_RO_PIPE;
-#else
   r.pipe = r.nblk <= 2 * ncu;  // measured crossover: beyond it the second
                                // wave per block only competes for issue slots
-#endif
   // staged: ST_PPW problems per wave at most, and every phase within the reference stage
   const bool fits = sp.stage_fits != 0;
   r.st = ppw <= ST_PPW && fits;
   // lane pairs (two lanes per candidate) while the chip has SIMDs to spare for them
   const int ppw2 = std::min(32 / sp.n_cand, RO_PAIR_PPB);
   r.nblk2 = ppw2 > 0 ? (int)grid_of(sp, ppw2) : 0;
-#ifdef MHPC_RO_PAIR_MAX_BLK
-  const int pair_max = MHPC_RO_PAIR_MAX_BLK;
-#else
-  const int pair_max = 2 * ncu;
-#endif
-  r.pair = r.pipe && r.st && ppw2 > 0 && r.nblk2 <= pair_max;
+  r.pair = r.pipe && r.st && ppw2 > 0 && r.nblk2 <= 2 * ncu;
   if (sp.var_ro) {  // forced (mhpc_set_kernel_variant checked that it applies)
     const int v = sp.var_ro;
     r.pair = v == MHPC_VARIANT_RO_PAIR;
@@ -2207,10 +2028,6 @@ hipError_t launch_partials(const SolveParams& sp, const DevBufs& d, hipStream_t 
     if (e == hipSuccess) e = hipStreamWaitEvent(s3, fork, 0);
     if (e != hipSuccess) return e;
   }
-#ifdef MHPC_PAR_IMPACT_FIRST  // experiment: the impact Jacobians ahead of the second group
-  if (ti > 0)
-    hipLaunchKernelGGL(k_partials_impact, dim3(ti), dim3(256), 0, two ? s3 : s, sp, d);
-#endif
   if (tk > 0) {
     constexpr int nt = MHPC_PAR_BLOCK;
     const dim3 grid(tk);
@@ -2221,11 +2038,9 @@ hipError_t launch_partials(const SolveParams& sp, const DevBufs& d, hipStream_t 
       hipLaunchKernelGGL(k_partials<3>, grid, dim3(nt), 0, s, sp, d);
     }
   }
-#ifndef MHPC_PAR_IMPACT_FIRST
   if (ti > 0)
     hipLaunchKernelGGL(k_partials_impact, dim3(ti), dim3(256), 0, two ? s3 : s,
                        sp, d);
-#endif
   if (two) {
     hipError_t e = hipEventRecord(join, s3);
     if (e == hipSuccess) e = hipStreamWaitEvent(s, join, 0);
