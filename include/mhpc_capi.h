@@ -49,6 +49,11 @@
  *                        MultiPhaseDDP.cpp:56-76): the solved feedback policy run from a measured
  *                        state; mhpc_rollout_policy_phase its trajectories, mhpc_advance_x0 the
  *                        same as the next tick's set_initial_condition, mhpc_get_x0 reads _x0
+ *   mhpc_control         one knot of forward_sweep_dynamics_only, u = u_nom + K (x - x_nom)
+ *                        (SinglePhase.cpp:117-144), for every problem at a control step of its own;
+ *                        mhpc_control_device the same on device arrays of the caller's,
+ *                        mhpc_set_x0_device set_initial_condition from one (the reference has
+ *                        neither: its controller is one object on one CPU)
  */
 #ifndef MHPC_CAPI_H
 #define MHPC_CAPI_H
@@ -451,6 +456,67 @@ int mhpc_rollout_policy_phase(mhpc_handle* h, int phase, int first, int count, i
  * whole-body horizon). */
 int mhpc_advance_x0(mhpc_handle* h, int n_phases, const double* dx);
 int mhpc_get_x0(mhpc_handle* h, double* x0);   /* [batch][r], the device's current rows */
+
+/* ---- device-resident control I/O: measured states in, feedback controls out ---------------
+ * What a controller exchanges with the outside every tick: the measured state going in
+ * (set_initial_condition, MultiPhaseDDP.h:24-25) and the control coming out, one knot of
+ * forward_sweep_dynamics_only: u = u_nom + K (x - x_nom) (HSDDPSolver/source/SinglePhase.cpp:
+ * 117-144).  The reference's controller is one object on one CPU and has no such call; a fleet
+ * in a GPU simulator keeps its states and actions in device arrays, and these entry points read
+ * and write them there, with no host copy of states, controls or gains.
+ *  - Control steps.  A problem's policy is addressed by an integer control step j, not by a time.
+ *    Problem b's steps cover its whole-body phases if it has any, else (an SRB-only problem) all
+ *    its phases; phase p contributes N[p] - 1 steps (its last knot has no control), so step j is
+ *    knot j - off_p of the phase p with off_p <= j < off_p + N[p] - 1.  mhpc_num_control_steps
+ *    counts them for one problem.  The map follows the problem's current layout
+ *    (mhpc_update_problem(s) shift it) and nominal trajectory.
+ *  - The state size is n = 14 (whole-body steps) or 6 (SRB-only problem); a problem reads the
+ *    first n entries of its row of r (r as in mhpc_set_x0).
+ *  - Arithmetic: exactly the policy rollouts' control law at that knot,
+ *    (u_nom[i] + 0 * du[i]) + sum_c K[i][c] (x[c] - x_nom[c]) summed in column order: both
+ *    flavours give the bits mhpc_rollout_policy_phase reports for the knot when x is the state that
+ *    rollout had there, in both precisions (tests/test_gpu_control.py).  Inputs are rounded to the
+ *    handle's arithmetic type on the way in, outputs widened for a double buffer or rounded to
+ *    nearest for a float buffer of an fp64 handle.  u is not clamped to the torque limit (the
+ *    reference's rollout does not clamp).
+ *  - Call order: as the policy rollouts.  MHPC_ERR_STATE before mhpc_initialize (or after
+ *    mhpc_set_layouts until the next one) and while commands or constraint parameters are
+ *    pending; a pending x0 does not block them.  Right after mhpc_initialize the policy is the PD
+ *    warm start with zero gains (u == u_nom).  They modify nothing.
+ *  - MHPC_ERR_INVALID, before anything is launched or changed: a null required pointer, a step
+ *    outside 0..n-1 for its problem, dtype not MHPC_DEV_F64 / MHPC_DEV_F32, ldx < r or ldu < 4, a
+ *    device pointer that hipPointerGetAttributes does not report as device memory of the handle's
+ *    device.  mhpc_control also refuses a non-finite entry of x; the device flavours do not
+ *    inspect values: a non-finite input gives a non-finite output and nothing worse (no index
+ *    depends on a value).
+ *  - Streams (device flavours): the library's work is ordered after everything queued on `stream`
+ *    (the caller's hipStream_t; NULL = the null stream) at the call -- an event recorded there,
+ *    which the handle's own stream waits for --, and like every other entry point the call returns
+ *    only after its own work has finished: outputs are then visible to any stream.  The caller's
+ *    stream itself is never synchronised with the host. */
+#define MHPC_DEV_F64 0
+#define MHPC_DEV_F32 1
+int mhpc_num_control_steps(mhpc_handle* h, int problem, int* n);
+
+/* host flavour: step [batch] (NULL = step 0 for every problem), x [batch][r];
+ * outputs, each optional: u [batch][4], x_nom [batch][r] (zero past n), u_nom [batch][4],
+ * K [batch][4][r] row-major (zero past column n).  x may be NULL only if u is NULL. */
+int mhpc_control(mhpc_handle* h, const int32_t* step, const double* x, double* u,
+                 double* x_nom, double* u_nom, double* K);
+
+/* device flavour: step stays a host array; x, u are device arrays of dtype with row strides
+ * ldx >= r, ldu >= 4 in elements (slices of a simulator's state / action tensors);
+ * x_nom, u_nom, K optional, dense, same dtype.  stream: the caller's hipStream_t (NULL = the
+ * null stream). */
+int mhpc_control_device(mhpc_handle* h, const int32_t* step, const void* x, int64_t ldx,
+                        void* u, int64_t ldu, void* x_nom, void* u_nom, void* K, int dtype,
+                        void* stream);
+
+/* mhpc_set_x0 from a device array: rows of r at x0 + b*ld, dtype as above.  Afterwards the handle
+ * is in every respect as after mhpc_set_x0 of the same values (the device rows bit for bit, an
+ * SRB-only problem's row tail zero, x0 pending for the next mhpc_initialize /
+ * mhpc_update_problem(s)).  MHPC_ERR_INVALID for a null or non-device x0, ld < r or a bad dtype. */
+int mhpc_set_x0_device(mhpc_handle* h, const void* x0, int64_t ld, int dtype, void* stream);
 
 /* Per-kernel device timing (HIP events around every launch on the handle's stream) and the
  * algorithmic HBM bytes each kernel must move (model in DESIGN.md §Roofline), accumulated

@@ -266,18 +266,22 @@ class MHPCLocomotion {
 
   // extension: per-problem initial states [batch][x0_width()] (14 when any problem has a
   // whole-body phase -- an SRB-only problem reads the first 6 of its row -- else 6)
-  void set_initial_conditions(const std::vector<double>& x0) { x0_ = x0; }
+  void set_initial_conditions(const std::vector<double>& x0) {
+    x0_ = x0;
+    x0_on_device_ = false;
+  }
   int x0_width() const { return xw_; }
   // MultiPhaseDDP::set_initial_condition for every problem of the batch (same state)
   void set_initial_condition(const std::vector<double>& x0) {
     for (int b = 0; b < batch_; ++b)
       for (int i = 0; i < xw_; ++i) x0_[(size_t)b * xw_ + i] = x0[i];
+    x0_on_device_ = false;
   }
 
   // MHPCLocomotion::update_problem (MHPCLocomotion.cpp:107-158): gait advances one mode,
   // phase buffers rotate (warm start), references follow the current initial condition
   void update_problem() {
-    check(mhpc_set_x0(h_, x0_.data()), "mhpc_set_x0");
+    push_x0();
     check(mhpc_update_problem(h_, &gait_), "mhpc_update_problem");
     refresh_descs();
   }
@@ -302,7 +306,7 @@ class MHPCLocomotion {
                        const std::vector<int32_t>& steps = {}) {
     std::vector<mhpc_gait> gs;
     for (Gait* g : gaits) gs.push_back(g->to_c());
-    check(mhpc_set_x0(h_, x0_.data()), "mhpc_set_x0");
+    push_x0();
     check(mhpc_update_problems(h_, (int)gs.size(), gs.data(),
                                gait_of_problem.empty() ? nullptr : gait_of_problem.data(),
                                steps.empty() ? nullptr : steps.data()),
@@ -431,7 +435,7 @@ class MHPCLocomotion {
     if (!dx.empty() && dx.size() != (size_t)batch_ * xw_)
       throw std::runtime_error("advance_x0: dx must be [batch][x0_width()]");
     check(mhpc_advance_x0(h_, n_phases, dx.empty() ? nullptr : dx.data()), "mhpc_advance_x0");
-    x0_ = get_x0();  // what update_problem() / initialization() hand back
+    x0_on_device_ = true;  // update_problem() / initialization() push nothing over the rows
   }
   // the device's current initial states [batch][x0_width()]
   std::vector<double> get_x0() {
@@ -439,6 +443,58 @@ class MHPCLocomotion {
     check(mhpc_get_x0(h_, x0.data()), "mhpc_get_x0");
     return x0;
   }
+  // ---- device-resident control I/O: measured states in, feedback controls out ---------------
+  // control steps of problem b: the knots with a control of its whole-body phases, or of all its
+  // phases when it is SRB-only (mhpc_num_control_steps)
+  int num_control_steps(int b = 0) {
+    int n = 0;
+    check(mhpc_num_control_steps(h_, b, &n), "mhpc_num_control_steps");
+    return n;
+  }
+  // u = u_nom + K (x - x_nom) of every problem at control step step[b] (empty: step 0) from its
+  // measured state x [batch][x0_width()], one knot of forward_sweep_dynamics_only
+  // (SinglePhase.cpp:117-144), the policy rollouts' arithmetic bit for bit (mhpc_control):
+  // u [batch][4]; with_policy: also x_nom [batch][x0_width()], u_nom [batch][4],
+  // K [batch][4][x0_width()]
+  struct Control { std::vector<double> u, x_nom, u_nom, K; };
+  Control control(const std::vector<int32_t>& step, const std::vector<double>& x,
+                  bool with_policy = false) {
+    if (x.size() != (size_t)batch_ * xw_ || (!step.empty() && step.size() != (size_t)batch_))
+      throw std::runtime_error("control: x must be [batch][x0_width()], step [batch] or empty");
+    Control c;
+    c.u.assign((size_t)batch_ * 4, 0.0);
+    if (with_policy) {
+      c.x_nom.assign((size_t)batch_ * xw_, 0.0);
+      c.u_nom.assign((size_t)batch_ * 4, 0.0);
+      c.K.assign((size_t)batch_ * 4 * xw_, 0.0);
+    }
+    check(mhpc_control(h_, step.empty() ? nullptr : step.data(), x.data(), c.u.data(),
+                       with_policy ? c.x_nom.data() : nullptr, with_policy ? c.u_nom.data() : nullptr,
+                       with_policy ? c.K.data() : nullptr),
+          "mhpc_control");
+    return c;
+  }
+  // the same on device arrays of the caller's (mhpc_control_device): x rows of x0_width() at a
+  // stride of ldx elements, u rows of 4 at ldu, of dtype MHPC_DEV_F64 / MHPC_DEV_F32 (slices of a
+  // simulator's state / action tensors); ordered after everything queued on `stream` (the
+  // caller's hipStream_t, null: the null stream), finished when the call returns
+  void control_device(const std::vector<int32_t>& step, const void* x, int64_t ldx, void* u,
+                      int64_t ldu, int dtype = MHPC_DEV_F64, void* stream = nullptr,
+                      void* x_nom = nullptr, void* u_nom = nullptr, void* K = nullptr) {
+    if (!step.empty() && step.size() != (size_t)batch_)
+      throw std::runtime_error("control_device: step must be [batch] or empty");
+    check(mhpc_control_device(h_, step.empty() ? nullptr : step.data(), x, ldx, u, ldu, x_nom, u_nom,
+                              K, dtype, stream),
+          "mhpc_control_device");
+  }
+  // set_initial_conditions from a device array, at once (mhpc_set_x0_device): rows of x0_width()
+  // at x0 + b * ld; the device rows are then the current ones, update_problem() /
+  // initialization() push no host copy over them
+  void set_x0_device(const void* x0, int64_t ld, int dtype = MHPC_DEV_F64, void* stream = nullptr) {
+    check(mhpc_set_x0_device(h_, x0, ld, dtype, stream), "mhpc_set_x0_device");
+    x0_on_device_ = true;
+  }
+
   // the tracking reference x of phase p for problems [first, first + count): [count][N][xsize]
   // (ReferenceGen.h:53-109; the range's phase must have one shape)
   std::vector<double> get_reference_problems(int p, int first, int count) {
@@ -494,7 +550,7 @@ class MHPCLocomotion {
   }
 
   void initialization() {  // (:47-53)
-    check(mhpc_set_x0(h_, x0_.data()), "mhpc_set_x0");
+    push_x0();
     check(mhpc_initialize(h_), "mhpc_initialize");
     refresh_phases(false);
   }
@@ -644,7 +700,13 @@ class MHPCLocomotion {
   }
   // the reference's default initial condition (MHPCLocomotion.cpp:37-39), projected for a
   // batch without whole-body phases
+  // the host copy of x0 to the device, unless the device rows are the current ones
+  // (set_x0_device, advance_x0)
+  void push_x0() {
+    if (!x0_on_device_) check(mhpc_set_x0(h_, x0_.data()), "mhpc_set_x0");
+  }
   void default_x0() {
+    x0_on_device_ = false;
     const double x0[14] = {0.0927, -0.1093, -0.1542, 1.0957, -2.2033, 0.9742, -1.7098,
                            0.9011, 0.2756,  0.7333,  0.0446, 0.0009,  1.3219, 2.7346};
     const int proj[6] = {0, 1, 2, 7, 8, 9};
@@ -715,6 +777,7 @@ class MHPCLocomotion {
   mhpc_hsddp_option opt_;
   mhpc_handle* h_ = nullptr;
   std::vector<double> x0_;
+  bool x0_on_device_ = false;
   std::vector<int32_t> status_;
   std::vector<std::unique_ptr<SinglePhaseAbstract<TH>>> phase_store_;
   std::vector<mhpc_problem_desc> pdesc_;  // per-problem layouts (empty: all equal desc_)

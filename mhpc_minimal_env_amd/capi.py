@@ -38,6 +38,9 @@ MHPC_VARIANT_SUBBATCH = 3
 MHPC_MAX_SUBBATCH = 4
 MHPC_VARIANT_RO_STORE = 4  # line-search trials storing their records (0 = default)
 MHPC_VARIANT_SWEEP_BITS = 5  # backward-sweep arithmetic: 64 double (default) / 32 float (fp32)
+# element type of a caller's device array (mhpc_control_device, mhpc_set_x0_device)
+MHPC_DEV_F64 = 0
+MHPC_DEV_F32 = 1
 MHPC_SOLVE_OK = 0
 MHPC_SOLVE_REG_ABORT = 1
 MHPC_SOLVE_NONFINITE = 2
@@ -222,6 +225,15 @@ SIGNATURES = [
                                                  ctypes.c_int, ctypes.c_int, _DP, _DP, _DP, _DP]),
     ("mhpc_advance_x0", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _DP]),
     ("mhpc_get_x0", ctypes.c_int, [ctypes.c_void_p, _DP]),
+    ("mhpc_num_control_steps", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_int)]),
+    ("mhpc_control", ctypes.c_int, [ctypes.c_void_p, _IP, _DP, _DP, _DP, _DP, _DP]),
+    ("mhpc_control_device", ctypes.c_int, [ctypes.c_void_p, _IP, ctypes.c_void_p, ctypes.c_int64,
+                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                           ctypes.c_void_p]),
+    ("mhpc_set_x0_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                          ctypes.c_int, ctypes.c_void_p]),
     ("mhpc_destroy", None, [ctypes.c_void_p]),
     ("mhpc_kernel_name", ctypes.c_char_p, [ctypes.c_int]),
     ("mhpc_set_profiling", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),

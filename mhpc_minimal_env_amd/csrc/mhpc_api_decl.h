@@ -21,6 +21,12 @@ int api_rollout_policy_phase(Handle* h, int phase, int first, int count, int n_s
                              const double* xs, double* x, double* u, double* y);
 int api_advance_x0(Handle* h, int n_phases, const double* dx);
 int api_get_x0(Handle* h, double* x0);
+int api_num_control_steps(Handle* h, int b, int* n);
+int api_control(Handle* h, const int32_t* step, const double* x, double* u, double* x_nom,
+                double* u_nom, double* K);
+int api_control_device(Handle* h, const int32_t* step, const void* x, int64_t ldx, void* u,
+                       int64_t ldu, void* x_nom, void* u_nom, void* K, int dtype, void* stream);
+int api_set_x0_device(Handle* h, const void* x0, int64_t ld, int dtype, void* stream);
 int api_get_cost_gradients(Handle* h, int phase, int first, int count, double* lx, double* Phix);
 int api_update_problem(Handle* h, const mhpc_gait* gait);
 int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const int32_t* gait_of,

@@ -141,6 +141,22 @@ extern "C" int mhpc_advance_x0(mhpc_handle* h, int n_phases, const double* dx) {
   FWD(advance_x0, n_phases, dx);
 }
 extern "C" int mhpc_get_x0(mhpc_handle* h, double* x0) { FWD(get_x0, x0); }
+extern "C" int mhpc_num_control_steps(mhpc_handle* h, int problem, int* n) {
+  FWD(num_control_steps, problem, n);
+}
+extern "C" int mhpc_control(mhpc_handle* h, const int32_t* step, const double* x, double* u,
+                            double* x_nom, double* u_nom, double* K) {
+  FWD(control, step, x, u, x_nom, u_nom, K);
+}
+extern "C" int mhpc_control_device(mhpc_handle* h, const int32_t* step, const void* x, int64_t ldx,
+                                   void* u, int64_t ldu, void* x_nom, void* u_nom, void* K,
+                                   int dtype, void* stream) {
+  FWD(control_device, step, x, ldx, u, ldu, x_nom, u_nom, K, dtype, stream);
+}
+extern "C" int mhpc_set_x0_device(mhpc_handle* h, const void* x0, int64_t ld, int dtype,
+                                  void* stream) {
+  FWD(set_x0_device, x0, ld, dtype, stream);
+}
 extern "C" int mhpc_get_cost_gradients(mhpc_handle* h, int phase, double* lx, double* Phix) {
   FWD(get_cost_gradients, phase, 0, batch_of(h), lx, Phix);
 }

@@ -30,6 +30,20 @@ static __device__ __forceinline__ real* traj_ptr(const SolveParams& sp, const De
 
 static __device__ __forceinline__ int ntc_of(int mode, bool wb) { return wb && (mode == 2 || mode == 4); }
 
+// Feedback term K[i] (x - x_nom) of the line-search control (SinglePhase.cpp forward sweep,
+// u = u_nom + eps du + K dx), summed in column order.  (Summing the two halves of the row
+// separately -- a chain half as long -- measured no faster: profiles/r02_ab_wt_layout.txt.)
+// Shared by the rollouts (mhpc_kernels.hip) and the one-knot control law of mhpc_control
+// (mhpc_control.hip), whose u must equal a rollout's bit for bit.
+template <int N>
+__device__ __forceinline__ real fb_dot(const real* Kr, const real* x, const real* nk) {
+  MHPC_NO_FMA_F32  // as in the kernels that call it (fp32 line search uncontracted)
+  real fb = 0;
+#pragma unroll
+  for (int c = 0; c < N; ++c) fb += Kr[c] * (x[c] - nk[c]);
+  return fb;
+}
+
 // ---- groups: (layout, parameter set) pairs ------------------------------------------------
 // A launch over the batch enumerates its blocks group by group: group g (problems
 // gidx[go[g] .. go[g+1]), record grp[g]) takes ceil(n_g / per) blocks of `per` problems, so every
@@ -68,6 +82,19 @@ static __device__ __forceinline__ int block_group_items(const SolveParams& sp, c
 // Problem index at gidx position pos.
 static __device__ __forceinline__ int prob_at(const SolveParams& sp, const DevBufs& d, int pos) {
   return sp.ident ? pos : d.gidx[pos];
+}
+// The lane's (group, problem, item) in a launch of n items per problem, 64 lanes a block, blocks
+// by group (block_group_items), the item index fastest; false: the lane has none.
+static __device__ __forceinline__ bool lane_item(const SolveParams& sp, const DevBufs& d, int n,
+                                                 int* g, int* b, int* e) {
+  long t0 = 0;
+  *g = block_group_items(sp, nullptr, n, blockIdx.x, 64, &t0);
+  if (*g < 0) return false;
+  const long tg = t0 + threadIdx.x;  // item within the group
+  if (tg >= (long)(sp.go[*g + 1] - sp.go[*g]) * n) return false;
+  *b = prob_at(sp, d, sp.go[*g] + (int)(tg / n));
+  *e = (int)(tg % n);
+  return true;
 }
 // Record of group g, read through the constant address space: the table never changes during a
 // launch, so every field a wave-uniform index selects is a scalar load (s_load), as a

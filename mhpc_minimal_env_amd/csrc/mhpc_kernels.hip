@@ -49,17 +49,8 @@ using real2 = float2;
 using real2 = double2;
 #endif
 
-// Feedback term K[i] (x - x_nom) of the line-search control (SinglePhase.cpp forward sweep,
-// u = u_nom + eps du + K dx), summed in column order.  (Summing the two halves of the row
-// separately -- a chain half as long -- measured no faster: profiles/r02_ab_wt_layout.txt.)
-template <int N>
-__device__ __forceinline__ real fb_dot(const real* Kr, const real* x, const real* nk) {
-  MHPC_NO_FMA_F32  // as in the kernels that call it (fp32 line search uncontracted)
-  real fb = 0;
-#pragma unroll
-  for (int c = 0; c < N; ++c) fb += Kr[c] * (x[c] - nk[c]);
-  return fb;
-}
+// (fb_dot, the feedback term of the line-search control, is in mhpc_device.h: mhpc_control.hip
+// calls it too)
 
 // Line-search trials whose running knot records are stored (j < RO_STORE_FIRST, and the last
 // trial, which the reference adopts when none is accepted); every trial stores its terminal
@@ -918,19 +909,7 @@ static __device__ __forceinline__ RolloutCost serial_rollout(const SolveParams& 
   return {J, viol2};
 }
 
-// The lane's (group, problem, item) in a launch of n items per problem, 64 lanes a block, blocks
-// by group (block_group_items), the item index fastest; false: the lane has none.
-static __device__ __forceinline__ bool lane_item(const SolveParams& sp, const DevBufs& d, int n,
-                                                 int* g, int* b, int* e) {
-  long t0 = 0;
-  *g = block_group_items(sp, nullptr, n, blockIdx.x, 64, &t0);
-  if (*g < 0) return false;
-  const long tg = t0 + threadIdx.x;  // item within the group
-  if (tg >= (long)(sp.go[*g + 1] - sp.go[*g]) * n) return false;
-  *b = prob_at(sp, d, sp.go[*g] + (int)(tg / n));
-  *e = (int)(tg % n);
-  return true;
-}
+// (lane_item, the lane's (group, problem, item) in the launches below, is in mhpc_device.h)
 
 // k_eps_rollout: the trial rollouts of forward_iteration without the Armijo stop, at an
 // arbitrary list of step sizes from x0, costs only (no stores, no selection) -- the C2 workload

@@ -84,6 +84,19 @@ int copy_block_table(const CopySide& src, const CopySide& dst, int* out);
 hipError_t launch_copy_problems(const CopySide& src, const CopySide& dst, int n, const int* pairs,
                                 int nblk, const int* blocks, hipStream_t s);
 
+// ---- mhpc_control.hip -----------------------------------------------------------------------
+// Control I/O through device arrays of the caller's element type (dtype MHPC_DEV_F64 / _F32).
+// launch_control: u = u_nom + K (x - x_nom) at control step step[b] of every problem (step on the
+// device, null: step 0; the step map is mhpc_control_map.h and the host has checked every step
+// against it).  x rows at a stride of ldx, u rows at ldu, in elements; x_nom [B][r], u_nom [B][4],
+// K [B][4][r] dense; every output may be null, x only when u is.
+hipError_t launch_control(const SolveParams& sp, const DevBufs& d, const int* step, const void* x,
+                          long ldx, void* u, long ldu, void* x_nom, void* u_nom, void* K, int r,
+                          int dtype, hipStream_t s);
+// launch_x0_in: the handle's x0 rows of 14 from rows at x0 + b * ld (mhpc_set_x0's padding)
+hipError_t launch_x0_in(const SolveParams& sp, const DevBufs& d, const void* x0, long ld, int dtype,
+                        hipStream_t s);
+
 // ---- mhpc_bws.hip ---------------------------------------------------------------------------
 hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, real update_reg, int part,
                       hipStream_t s);

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/mhpc_capi.h"
+#include "mhpc_control_map.h"
 #include "mhpc_devtemp.h"
 #include "mhpc_launch.h"
 #include "mhpc_plan.h"
@@ -124,6 +125,12 @@ struct Handle {
   };
   std::vector<SubStreams> subs;
   hipEvent_t evstart = nullptr;
+  // control I/O (mhpc_control*, mhpc_set_x0_device): the problems' control steps on the device
+  // [B] with the host copy the upload reads, and the event that orders the handle's stream behind
+  // the caller's; all created at the first call that needs them
+  int* dstep = nullptr;
+  std::vector<int> hstep;
+  hipEvent_t evctl = nullptr;
 };
 
 // backward sweep: per WB knot partials record + x,u,y + refpos read, K,du,G written;
@@ -1332,6 +1339,130 @@ int api_get_x0(Handle* h, double* x0) {
   return MHPC_OK;
 }
 
+// ---- device-resident control I/O (k_control, k_x0_in: mhpc_control.hip) ---------------------
+// Every check of the control entry points that needs no device: the call order (policy_ready),
+// the steps against the map the kernel runs (mhpc_control_map.h) on each problem's own layout.
+static int control_ready(const Handle* h, const int32_t* step) {
+  if (int rc = policy_ready(h)) return rc;
+  for (int b = 0; step && b < h->sp.B; ++b) {
+    const Layout& L = h->plan.lays[h->plan.lid[b]];
+    mhpc_ctrl::Knot q;
+    if (!mhpc_ctrl::knot_of(L.P, L.n_wb, L.N, L.ko, step[b], &q))
+      return fail(MHPC_ERR_INVALID, "control step outside 0..mhpc_num_control_steps - 1");
+  }
+  return MHPC_OK;
+}
+// A caller's device array: device memory of the handle's device, as hipPointerGetAttributes
+// reports it (a host pointer, registered or not, or managed memory is refused).
+static int check_device_ptr(const Handle* h, const void* p, const char* what) {
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();  // (an unknown pointer is an error of the query, not of the device)
+    return fail(MHPC_ERR_INVALID, std::string(what) + " is not device memory");
+  }
+  if (at.type != hipMemoryTypeDevice || at.device != h->device)
+    return fail(MHPC_ERR_INVALID, std::string(what) + " is not device memory of the handle's device");
+  return MHPC_OK;
+}
+static int check_dev_dtype(int dtype) {
+  if (dtype != MHPC_DEV_F64 && dtype != MHPC_DEV_F32)
+    return fail(MHPC_ERR_INVALID, "dtype must be MHPC_DEV_F64 or MHPC_DEV_F32");
+  return MHPC_OK;
+}
+// The handle's stream behind everything queued on the caller's stream at this call: an event
+// recorded there (created at the first such call), no host-side wait.
+static int wait_for_caller(Handle* h, void* stream) {
+  if (!h->evctl) HIPCHK(hipEventCreateWithFlags(&h->evctl, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(h->evctl, (hipStream_t)stream));
+  HIPCHK(hipStreamWaitEvent(h->stream, h->evctl, 0));
+  return MHPC_OK;
+}
+// The steps to the handle's device array [B] (allocated at the first call with steps, after every
+// other array of the handle: their placement stays as it was); *dstep null for null steps.
+static int upload_steps(Handle* h, const int32_t* step, const int** dstep) {
+  *dstep = nullptr;
+  if (!step) return MHPC_OK;
+  if (!h->dstep) HIPCHK(hipMalloc((void**)&h->dstep, (size_t)h->sp.B * sizeof(int)));
+  h->hstep.assign(step, step + h->sp.B);  // (the copy may outlive a call that fails after it)
+  HIPCHK(hipMemcpyAsync(h->dstep, h->hstep.data(), (size_t)h->sp.B * sizeof(int),
+                        hipMemcpyHostToDevice, h->stream));
+  *dstep = h->dstep;
+  return MHPC_OK;
+}
+
+int api_num_control_steps(Handle* h, int b, int* n) {
+  if (!h || !n) return fail(MHPC_ERR_INVALID, "null argument");
+  if (b < 0 || b >= h->sp.B) return fail(MHPC_ERR_INVALID, "problem out of range");
+  const Layout& L = h->plan.lays[h->plan.lid[b]];
+  *n = mhpc_ctrl::n_steps(L.P, L.n_wb, L.N);
+  return MHPC_OK;
+}
+
+// Host flavour: the arrays staged through device temporaries of double, the same kernel.
+int api_control(Handle* h, const int32_t* step, const double* x, double* u, double* x_nom,
+                double* u_nom, double* K) {
+  if (!h) return fail(MHPC_ERR_INVALID, "null handle");
+  if (u && !x) return fail(MHPC_ERR_INVALID, "null x");
+  int rc = control_ready(h, step);
+  if (rc) return rc;
+  const size_t B = h->sp.B, r = x0_row(h);
+  for (size_t i = 0; x && i < B * r; ++i)
+    if (!std::isfinite(x[i])) return fail(MHPC_ERR_INVALID, "x must be finite");
+  HIPCHK(hipSetDevice(h->device));
+  const int* dstep;
+  if ((rc = upload_steps(h, step, &dstep))) return rc;
+  DevTemp<double> t(h->stream);
+  const double* dx = u ? t.in(x, B * r) : nullptr;
+  double* du = u ? t.out(u, B * 4) : nullptr;
+  double* dxn = x_nom ? t.out(x_nom, B * r) : nullptr;
+  double* dun = u_nom ? t.out(u_nom, B * 4) : nullptr;
+  double* dK = K ? t.out(K, B * 4 * r) : nullptr;
+  if (t.e == hipSuccess)
+    t.e = launch_control(h->sp, h->d, dstep, dx, (long)r, du, 4, dxn, dun, dK, (int)r, MHPC_DEV_F64,
+                         h->stream);
+  if (t.fetch() != hipSuccess) return dev_fail("mhpc_control", t.e);
+  return MHPC_OK;
+}
+
+int api_control_device(Handle* h, const int32_t* step, const void* x, int64_t ldx, void* u,
+                       int64_t ldu, void* x_nom, void* u_nom, void* K, int dtype, void* stream) {
+  if (!h) return fail(MHPC_ERR_INVALID, "null handle");
+  if (u && !x) return fail(MHPC_ERR_INVALID, "null x");
+  int rc = control_ready(h, step);
+  if (rc) return rc;
+  if ((rc = check_dev_dtype(dtype))) return rc;
+  const int r = x0_row(h);
+  if (u && (ldx < r || ldu < 4)) return fail(MHPC_ERR_INVALID, "ldx < r or ldu < 4");
+  HIPCHK(hipSetDevice(h->device));
+  const void* ptrs[] = {u ? x : nullptr, u, x_nom, u_nom, K};
+  const char* names[] = {"x", "u", "x_nom", "u_nom", "K"};
+  for (int i = 0; i < 5; ++i)
+    if (ptrs[i] && (rc = check_device_ptr(h, ptrs[i], names[i]))) return rc;
+  const int* dstep;
+  if ((rc = upload_steps(h, step, &dstep))) return rc;
+  if ((rc = wait_for_caller(h, stream))) return rc;
+  HIPCHK(launch_control(h->sp, h->d, dstep, u ? x : nullptr, (long)ldx, u, (long)ldu, x_nom, u_nom,
+                        K, r, dtype, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return MHPC_OK;
+}
+
+int api_set_x0_device(Handle* h, const void* x0, int64_t ld, int dtype, void* stream) {
+  if (!h || !x0) return fail(MHPC_ERR_INVALID, "null argument");
+  int rc = check_dev_dtype(dtype);
+  if (rc) return rc;
+  if (ld < x0_row(h)) return fail(MHPC_ERR_INVALID, "ld < r");
+  HIPCHK(hipSetDevice(h->device));
+  if ((rc = check_device_ptr(h, x0, "x0"))) return rc;
+  if ((rc = wait_for_caller(h, stream))) return rc;
+  HIPCHK(launch_x0_in(h->sp, h->d, x0, (long)ld, dtype, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->x0_set = true;
+  h->x0_changed = true;  // as after mhpc_set_x0
+  return MHPC_OK;
+}
+
 int api_get_cost_gradients(Handle* h, int phase, int first, int count, double* lx, double* Phix) {
   if (!h) return fail(MHPC_ERR_INVALID, "null handle");
   if (!h->initialized) return fail(MHPC_ERR_STATE, "not initialized");
@@ -1877,6 +2008,8 @@ void api_destroy(Handle* h) {
   if (h->dcnt) (void)hipFree(h->dcnt);
   if (h->store) (void)hipFree(h->store);
   if (h->dsplit) (void)hipFree(h->dsplit);
+  if (h->dstep) (void)hipFree(h->dstep);
+  if (h->evctl) (void)hipEventDestroy(h->evctl);
   for (hipEvent_t e : h->evpool) (void)hipEventDestroy(e);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);

@@ -283,6 +283,13 @@ class MHPCLocomotion:
         n0 = self._x0_row()
         x0 = X0_DEFAULT if n0 == 14 else X0_DEFAULT[STATE_PROJ_ROWS]
         self._x0 = np.tile(x0, (self.batch, 1)).astype(np.float64)
+        self._x0_on_device = False
+
+    def _push_x0(self):
+        """The host copy of x0 to the device (mhpc_set_x0) -- unless the device rows are the
+        current ones (set_initial_condition_device, advance_x0): then there is nothing to push."""
+        if not self._x0_on_device:
+            capi.check(capi.lib().mhpc_set_x0(self._h, capi.dptr(self._x0)), "mhpc_set_x0")
 
     # -- lifecycle ---------------------------------------------------------------------
     def set_initial_condition(self, x0: np.ndarray):
@@ -290,10 +297,22 @@ class MHPCLocomotion:
         if x0.shape[1] != self._x0_row():
             raise ValueError("x0 has the wrong state size for phase 0")
         self._x0 = x0
+        self._x0_on_device = False
+
+    def set_initial_condition_device(self, t):
+        """mhpc_set_x0_device: the initial states from a torch tensor [batch][r] on the handle's
+        device (float32 or float64, inner stride 1, any row stride: a slice of a simulator's state
+        tensor), read on the current torch stream's order, at once.  The device rows are then the
+        current ones: initialization() / update_problem(s) push no host copy over them;
+        get_x0() reads them back for those who want the values."""
+        ptr, ld, dtype, stream = self._device_rows(t, self._x0_row(), "x0")
+        capi.check(capi.lib().mhpc_set_x0_device(self._h, ptr, ld, dtype, stream),
+                   "mhpc_set_x0_device")
+        self._x0_on_device = True
 
     def initialization(self):
         L = capi.lib()
-        capi.check(L.mhpc_set_x0(self._h, capi.dptr(self._x0)), "mhpc_set_x0")
+        self._push_x0()
         capi.check(L.mhpc_initialize(self._h), "mhpc_initialize")
 
     def solve_mhpc(self) -> np.ndarray:
@@ -305,7 +324,7 @@ class MHPCLocomotion:
         gait advances one mode, the phase buffers rotate (warm start of the next solve), the
         references follow the x0 given to set_initial_condition."""
         L = capi.lib()
-        capi.check(L.mhpc_set_x0(self._h, capi.dptr(self._x0)), "mhpc_set_x0")
+        self._push_x0()
         g = (gait or self.gait).to_c()
         capi.check(L.mhpc_update_problem(self._h, __import__("ctypes").byref(g)),
                    "mhpc_update_problem")
@@ -332,7 +351,7 @@ class MHPCLocomotion:
         set_initial_condition for every problem."""
         import ctypes
         L = capi.lib()
-        capi.check(L.mhpc_set_x0(self._h, capi.dptr(self._x0)), "mhpc_set_x0")
+        self._push_x0()
         gs = (capi.GaitC * len(gaits))(*[g.to_c() for g in gaits])
         gop = (None if gait_of_problem is None
                else np.ascontiguousarray(gait_of_problem, dtype=np.int32))
@@ -365,7 +384,7 @@ class MHPCLocomotion:
         capi.check(capi.lib().mhpc_reset_problems(self._h, int(pr.size), capi.iptr(pr),
                                                   capi.dptr(x0), 0 if descs is None else len(descs),
                                                   arr, capi.iptr(dof)), "mhpc_reset_problems")
-        if x0 is not None:  # what the next update_problem(s) hands back to the device
+        if x0 is not None and not self._x0_on_device:  # what the next update_problem(s) hands back
             self._x0 = self._x0.copy()
             self._x0[pr] = x0
         if descs is not None:
@@ -392,8 +411,9 @@ class MHPCLocomotion:
                    "mhpc_copy_problems")
         # the host mirrors follow: the rows update_problem(s) hands back to the device are the
         # device's own, the last solve's status is the source's, descriptors and commands travel
-        self._x0 = self._x0.copy()
-        self._x0[dp] = self.get_x0()[dp]
+        if not self._x0_on_device:
+            self._x0 = self._x0.copy()
+            self._x0[dp] = self.get_x0()[dp]
         self.status[dp] = src.status[sp]
         self._refresh_descs()
         return float(ms.value)
@@ -690,15 +710,101 @@ class MHPCLocomotion:
     def advance_x0(self, n_phases: int = 1, dx=None):
         """Device-side closed loop (mhpc_advance_x0): every problem's x0 becomes the end state
         of one policy rollout over n_phases phases from x0 + dx (dx [batch][r] or None), with
-        no host copy of states.  update_problem() / initialization() follow, as after
-        set_initial_condition."""
+        no host copy of states (get_x0() reads them back).  update_problem() / initialization()
+        follow, as after set_initial_condition."""
         if dx is not None:
             dx = np.ascontiguousarray(dx, dtype=np.float64)
             if dx.shape != (self.batch, self._x0_row()):
                 raise ValueError("dx must be [batch][x0 row length]")
         capi.check(capi.lib().mhpc_advance_x0(self._h, int(n_phases), capi.dptr(dx)),
                    "mhpc_advance_x0")
-        self._x0 = self.get_x0()  # what update_problem() / initialization() hand back
+        self._x0_on_device = True  # update_problem() / initialization() push nothing over them
+
+    # -- device-resident control I/O: measured states in, feedback controls out ----------------
+    def num_control_steps(self, b: int = 0) -> int:
+        """Control steps of problem b (mhpc_num_control_steps): the knots with a control of its
+        whole-body phases, or of all its phases when it is SRB-only."""
+        import ctypes
+        n = ctypes.c_int(0)
+        capi.check(capi.lib().mhpc_num_control_steps(self._h, int(b), ctypes.byref(n)),
+                   "mhpc_num_control_steps")
+        return n.value
+
+    def _device_rows(self, t, cols: int, name: str):
+        """(pointer, row stride, dtype code, stream) of a torch tensor [batch][cols] on the
+        handle's device; ValueError for anything the library could not address."""
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+        if t.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{name} must be float32 or float64")
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"{name} must be on the handle's device")
+        if t.dim() != 2 or tuple(t.shape) != (self.batch, cols):
+            raise ValueError(f"{name} must be [batch][{cols}]")
+        if t.stride(1) != 1 or t.stride(0) < cols:
+            raise ValueError(f"{name} must have an inner stride of 1 and a row stride >= {cols}")
+        dtype = capi.MHPC_DEV_F32 if t.dtype == torch.float32 else capi.MHPC_DEV_F64
+        stream = torch.cuda.current_stream(t.device).cuda_stream
+        return t.data_ptr(), int(t.stride(0)), dtype, stream
+
+    def control(self, step, x, want=("u",), out=None) -> dict:
+        """The feedback control of every problem at control step step[b] (an int for every problem,
+        or [batch]; None: step 0) from its measured state x [batch][r]:
+        u = u_nom + K (x - x_nom), the policy rollouts' arithmetic at that knot bit for bit.
+        x: a numpy array (mhpc_control) or a torch tensor on the handle's device, float32 or
+        float64, inner stride 1 (mhpc_control_device, on the current torch stream's order);
+        returns a dict of the same kind with the entries of `want`: "u" [batch][4], "x_nom"
+        [batch][r], "u_nom" [batch][4], "K" [batch][4][r].  out: for tensors, {"u": tensor
+        [batch][4]} to write u into a slice of the caller's own action tensor."""
+        r, B = self._x0_row(), self.batch
+        want = tuple(want)
+        if not want or any(k not in ("u", "x_nom", "u_nom", "K") for k in want):
+            raise ValueError('want: some of "u", "x_nom", "u_nom", "K"')
+        st = None
+        if step is not None:
+            st = np.asarray(step)
+            if not np.issubdtype(st.dtype, np.integer):
+                raise ValueError("step must be an int or [batch] ints")
+            if st.ndim == 0:
+                st = np.full(B, int(st))
+            if st.shape != (B,):
+                raise ValueError("step must be an int or [batch] ints")
+            st = np.ascontiguousarray(st, dtype=np.int32)
+        shapes = {"u": (B, 4), "x_nom": (B, r), "u_nom": (B, 4), "K": (B, 4, r)}
+        L = capi.lib()
+        if isinstance(x, np.ndarray) or x is None:
+            if out is not None:
+                raise ValueError("out is for torch tensors")
+            if "u" in want:
+                if x is None:
+                    raise ValueError("u needs x")
+                x = np.ascontiguousarray(x, dtype=np.float64)
+                if x.shape != (B, r):
+                    raise ValueError("x must be [batch][x0 row length]")
+            res = {k: np.zeros(shapes[k]) for k in want}
+            capi.check(L.mhpc_control(self._h, capi.iptr(st), capi.dptr(x) if "u" in want else None,
+                                      *[capi.dptr(res.get(k)) for k in ("u", "x_nom", "u_nom", "K")]),
+                       "mhpc_control")
+            return res
+        import torch
+        xp, ldx, dtype, stream = self._device_rows(x, r, "x")
+        res = {}
+        for k in want:
+            if k == "u" and out is not None and "u" in out:
+                res[k] = out["u"]
+                if res[k].dtype != x.dtype:
+                    raise ValueError("out['u'] must have x's dtype")
+            else:
+                res[k] = torch.empty(shapes[k], dtype=x.dtype, device=x.device)
+        up, ldu = None, 4
+        if "u" in res:
+            up, ldu, _, _ = self._device_rows(res["u"], 4, "u")
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        capi.check(L.mhpc_control_device(self._h, capi.iptr(st), xp, ldx, up, ldu, ptr("x_nom"),
+                                         ptr("u_nom"), ptr("K"), dtype, stream),
+                   "mhpc_control_device")
+        return res
 
     def get_x0(self) -> np.ndarray:
         """The device's current initial states [batch][r] (mhpc_get_x0)."""

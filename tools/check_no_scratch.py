@@ -11,7 +11,8 @@ usage: python tools/check_no_scratch.py <file.s> [...]    exit 1 on any hit
 import re
 import sys
 
-HOT = ("k_rollout", "k_bws", "k_partials", "k_init", "k_cost", "k_al_end", "k_copy_problems")
+HOT = ("k_rollout", "k_bws", "k_partials", "k_init", "k_cost", "k_al_end", "k_copy_problems",
+       "k_control", "k_x0_in")  # the last two: the per-tick control I/O (mhpc_control.hip)
 COLD = ("k_cost_grad",)  # debug-info kernel (print_debugInfo), not in the solve
 
 
