@@ -38,6 +38,10 @@
  *                        fleet (MHPCLocomotion.cpp:47-53): the listed problems only
  *   mhpc_copy_problems   copy construction / assignment of a controller object (every member of
  *                        MHPCLocomotion and its MultiPhaseDDP): problems copied between slots
+ *   mhpc_tick_problems   set_initial_condition + update_problem + solve_mhpc of single controllers
+ *                        of the fleet (MHPCLocomotion.cpp:107-158,167-195), each when its own gait
+ *                        mode ends: the listed problems only; mhpc_reserve_knots the room that
+ *                        memory_alloc's N_TIMESTEPS_MAX buffers give every controller
  *   mhpc_set_commands    MHPCUserParameters::usrcmd of every controller (vel, height), which
  *                        build_problem / update_problem hand to ReferenceGen
  *                        (MHPCLocomotion.cpp:98-103): per-problem user commands in one batch;
@@ -246,6 +250,60 @@ int mhpc_update_problems(mhpc_handle* h, int n_gaits, const mhpc_gait* gaits,
  *  - Device work is proportional to n, not to the batch. */
 int mhpc_reset_problems(mhpc_handle* h, int n, const int32_t* problems, const double* x0,
                         int n_desc, const mhpc_problem_desc* descs, const int32_t* desc_of);
+/* ---- per-problem ticks: update and solve the listed problems, and nobody else -------------
+ * In the reference every robot is its own MHPCLocomotion and ticks when its own gait mode ends:
+ * set_initial_condition(x), update_problem() (MHPCLocomotion.cpp:107-158), solve_mhpc()
+ * (:167-195); the other robots never notice.  One MPC tick of the n listed problems: for listed
+ * problem i its x0 row, steps[i] update_problem steps of gaits[gait_of[i]], then the solve.
+ * problems: n distinct problem numbers, 1 <= n <= batch, in any order.  x0: [n][r] rows in list
+ * order (r as in mhpc_set_x0; an SRB-only problem reads its first 6 entries), finite; NULL keeps
+ * each listed problem's current device row (what mhpc_set_x0_device or mhpc_advance_x0 left
+ * there).  gait_of: [n], NULL = gaits[0]; n_gaits in 1..MHPC_MAX_LAYOUTS.  steps: [n], each in
+ * 0..1024, NULL = one step each; with steps[i] = 0 the problem keeps its layout and is re-solved
+ * from its new x0 (what mhpc_update_problems does for such a problem); gaits may be NULL only when
+ * every step is 0.  status: optional, [n] in list order (mhpc_solve_status).  ms: optional, device
+ * time of the whole tick (HIP events).
+ *  - A listed problem is afterwards, bit for bit, what it would be after mhpc_set_x0 of that row,
+ *    mhpc_update_problems with those steps and mhpc_solve in a handle of its own with the same
+ *    descriptor history, command, parameter set and options: the nominal trajectory and every
+ *    slot, K / du / G, the partials, impact Jacobians and sweep carry, the whole solver state, the
+ *    position references (generated from the problem's current command), the layout with its
+ *    rotated buffers and gait point, its rows of the phase-buffer store -- in fp64 and in fp32
+ *    (tests/test_gpu_tick.py).  For a problem that mhpc_reset_problems made fresh and that takes 0
+ *    steps the first forward_sweep(0) is the cost evaluation, as in mhpc_solve.
+ *  - Every unlisted problem keeps its device state bit for bit: every array above, its x0 row, its
+ *    store rows.  So a tick never re-strides or reallocates: a listed problem whose new layout has
+ *    more knots than the current stride, or a phase longer than the phase buffers, is refused
+ *    before anything changes (mhpc_reserve_knots makes room beforehand).  The first tick or update
+ *    after an mhpc_initialize still zeroes the phase-buffer store once: the only batch-proportional
+ *    device work.
+ *  - MHPC_ERR_STATE unless the handle is initialised and its last batch-wide step was a solve, and
+ *    while constraint parameters or parameter sets are pending.  A pending x0 does not block the
+ *    call and stays pending.  Pending commands do not block it either: the tick applies the listed
+ *    problems' current commands and clears their part of the pending state (commands are pending
+ *    per problem: mhpc_set_commands marks the problems whose value changed, mhpc_initialize /
+ *    mhpc_update_problem[s] clear every mark, a tick the listed ones; the other entry points
+ *    refuse while any problem is marked).  The call-order state is otherwise unchanged: solved.
+ *  - mhpc_get_counters (solve_ms included) and the per-kernel byte / flop accounting afterwards
+ *    describe the tick's solve: sums over the listed problems.
+ *  - MHPC_ERR_INVALID, before anything is launched or changed: a null required pointer; n out of
+ *    range; a duplicate or out-of-range problem; a bad gait or gait index; a step count out of
+ *    range; a non-finite x0 entry; a current mode that is not in the gait, a phase with N < 2 or
+ *    too many knots (mhpc_update_problems' refusals); a layout that does not fit the arrays; more
+ *    than MHPC_MAX_LAYOUTS groups.  A refused call changes nothing.
+ *  - MHPC_ERR_DEVICE: a failed launch leaves the listed problems undefined, as a failed
+ *    mhpc_reset_problems does (reset them).
+ *  - Device work is proportional to n, not to the batch.  The host plan and the group-table upload
+ *    stay O(batch), as for a reset; when every step is 0 no layout changes and both are skipped. */
+int mhpc_tick_problems(mhpc_handle* h, int n, const int32_t* problems, const double* x0,
+                       int n_gaits, const mhpc_gait* gaits, const int32_t* gait_of,
+                       const int32_t* steps, int32_t* status, float* ms);
+/* Floor of the per-problem knot stride of the packed arrays, knots in 1..MHPC_MAX_KNOTS: from
+ * this call on the stride is max(longest layout, knots) wherever it may change, so a fleet created
+ * at one gait point can later tick into a longer layout (1 WB + 2 SRB phases of the default gait:
+ * 260 knots at mode 1, 280 at mode 2).  After mhpc_create / mhpc_set_layouts and before
+ * mhpc_initialize: MHPC_ERR_STATE on an initialised handle.  Results do not depend on the stride. */
+int mhpc_reserve_knots(mhpc_handle* h, int knots);
 /* ---- copies of live problems: a slot becomes another controller, warm start and all -------
  * In the reference a controller is an object and copying it is copying the object.  Here dst
  * problem dst_problems[i] becomes a copy of src problem src_problems[i], i < n, as the source

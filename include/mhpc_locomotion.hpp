@@ -329,6 +329,44 @@ class MHPCLocomotion {
       std::copy(x0.begin() + i * xw_, x0.begin() + (i + 1) * xw_, x0_.begin() + (size_t)pr[i] * xw_);
     refresh_descs();
   }
+  // extension: one MPC tick of the listed problems and of nobody else -- set_initial_condition +
+  // update_problem + solve_mhpc on single controllers of a fleet, each when its own gait mode ends
+  // (mhpc_tick_problems).  x0 [problems.size()][x0_width()] in list order, empty: each listed
+  // problem keeps its current device row; listed problem i takes steps[i] gait steps (empty: one
+  // each) of gaits[gait_of[i]] (empty: gaits[0]; no gaits: this controller's own gait).  Every
+  // other problem keeps its state bit for bit.  Returns the listed problems' status in list order
+  // (also kept in status()); ms: the device time of the whole tick.
+  std::vector<int32_t> tick_problems(const std::vector<int>& problems, const std::vector<double>& x0 = {},
+                                     const std::vector<Gait*>& gaits = {},
+                                     const std::vector<int32_t>& gait_of = {},
+                                     const std::vector<int32_t>& steps = {}, float* ms = nullptr) {
+    if (!x0.empty() && x0.size() != problems.size() * (size_t)xw_)
+      throw std::runtime_error("tick_problems: x0 must be [problems][x0_width()]");
+    if ((!gait_of.empty() && gait_of.size() != problems.size()) ||
+        (!steps.empty() && steps.size() != problems.size()))
+      throw std::runtime_error("tick_problems: one gait index / step count per listed problem");
+    const std::vector<int32_t> pr(problems.begin(), problems.end());
+    std::vector<mhpc_gait> gs;
+    for (Gait* g : gaits) gs.push_back(g->to_c());
+    if (gs.empty()) gs.push_back(gait_);
+    std::vector<int32_t> st(pr.size(), 0);
+    check(mhpc_tick_problems(h_, (int)pr.size(), pr.data(), x0.empty() ? nullptr : x0.data(),
+                             (int)gs.size(), gs.data(), gait_of.empty() ? nullptr : gait_of.data(),
+                             steps.empty() ? nullptr : steps.data(), st.data(), ms),
+          "mhpc_tick_problems");
+    status_.resize(batch_, 0);
+    for (size_t i = 0; i < pr.size(); ++i) {
+      status_[pr[i]] = st[i];
+      if (!x0.empty() && !x0_on_device_)  // what update_problem(s) hands back
+        std::copy(x0.begin() + i * xw_, x0.begin() + (i + 1) * xw_, x0_.begin() + (size_t)pr[i] * xw_);
+    }
+    refresh_descs();
+    refresh_phases(true);
+    return st;
+  }
+  // extension: floor of the knot stride of the packed arrays, so that later ticks can step into
+  // longer layouts (mhpc_reserve_knots); before initialization()
+  void reserve_knots(int knots) { check(mhpc_reserve_knots(h_, knots), "mhpc_reserve_knots"); }
   // extension: copying controller objects -- problem dst_problems[i] of this fleet becomes a copy
   // of problem src_problems[i] of `src` (nullptr: of this fleet) as it stands: warm start, solver
   // state, x0 row, command, parameter set, layout and phase buffers.  A source may repeat (one

@@ -209,6 +209,10 @@ SIGNATURES = [
                                              ctypes.POINTER(ProblemDesc)]),
     ("mhpc_reset_problems", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _IP, _DP, ctypes.c_int,
                                            ctypes.POINTER(ProblemDesc), _IP]),
+    ("mhpc_tick_problems", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _IP, _DP, ctypes.c_int,
+                                          ctypes.POINTER(GaitC), _IP, _IP, _IP,
+                                          ctypes.POINTER(ctypes.c_float)]),
+    ("mhpc_reserve_knots", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("mhpc_copy_problems", ctypes.c_int, [ctypes.c_void_p, _IP, ctypes.c_void_p, _IP, ctypes.c_int,
                                           ctypes.POINTER(ctypes.c_float)]),
     ("mhpc_set_commands", ctypes.c_int, [ctypes.c_void_p, _DP, _DP]),

@@ -31,6 +31,10 @@ int api_get_cost_gradients(Handle* h, int phase, int first, int count, double* l
 int api_update_problem(Handle* h, const mhpc_gait* gait);
 int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const int32_t* gait_of,
                         const int32_t* steps);
+int api_tick_problems(Handle* h, int n, const int32_t* problems, const double* x0, int n_gaits,
+                      const mhpc_gait* gaits, const int32_t* gait_of, const int32_t* steps,
+                      int32_t* status, float* ms);
+int api_reserve_knots(Handle* h, int knots);
 int api_set_layouts(Handle* h, int n_desc, const mhpc_problem_desc* descs, const int32_t* lop);
 int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* x0, int n_desc,
                        const mhpc_problem_desc* descs, const int32_t* desc_of);

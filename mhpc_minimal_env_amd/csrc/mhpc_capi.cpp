@@ -172,6 +172,12 @@ extern "C" int mhpc_update_problems(mhpc_handle* h, int n_gaits, const mhpc_gait
                                     const int32_t* gait_of_problem, const int32_t* steps) {
   FWD(update_problems, n_gaits, gaits, gait_of_problem, steps);
 }
+extern "C" int mhpc_tick_problems(mhpc_handle* h, int n, const int32_t* problems, const double* x0,
+                                  int n_gaits, const mhpc_gait* gaits, const int32_t* gait_of,
+                                  const int32_t* steps, int32_t* status, float* ms) {
+  FWD(tick_problems, n, problems, x0, n_gaits, gaits, gait_of, steps, status, ms);
+}
+extern "C" int mhpc_reserve_knots(mhpc_handle* h, int knots) { FWD(reserve_knots, knots); }
 extern "C" int mhpc_set_layouts(mhpc_handle* h, int n_desc, const mhpc_problem_desc* descs,
                                 const int32_t* layout_of_problem) {
   FWD(set_layouts, n_desc, descs, layout_of_problem);

@@ -1,4 +1,4 @@
-// What the kernel translation units (mhpc_kernels.hip, mhpc_bws.hip) export to the host
+// What the kernel translation units (mhpc_kernels.hip, mhpc_bws.hip, ...) export to the host
 // runtime: the launchers, the launch-shape queries, and the record widths the host unpacks.
 // Included by both kernel files and by mhpc_runtime.cpp, so a prototype that no longer matches
 // its definition fails to compile instead of failing to link.
@@ -83,6 +83,16 @@ struct CopySide {
 int copy_block_table(const CopySide& src, const CopySide& dst, int* out);
 hipError_t launch_copy_problems(const CopySide& src, const CopySide& dst, int n, const int* pairs,
                                 int nblk, const int* blocks, hipStream_t s);
+
+// ---- mhpc_tick.hip --------------------------------------------------------------------------
+// list-driven device code of mhpc_tick_problems: the phase-buffer save (save = 1: the nominal slot
+// of each listed problem to its store rows) / load (store rows to slot 0, K, du, G; a phase's last
+// knot to every slot) by each problem's own layout d.grp[d.lid[b]], and the listed problems'
+// status words to status [n] on the device, in list order
+hipError_t launch_store_list(const SolveParams& sp, const DevBufs& d, int n, const int* list,
+                             real* store, int nbk, int spmax, int save, hipStream_t s);
+hipError_t launch_status_list(const DevBufs& d, int n, const int* list, int32_t* status,
+                              hipStream_t s);
 
 // ---- mhpc_control.hip -----------------------------------------------------------------------
 // Control I/O through device arrays of the caller's element type (dtype MHPC_DEV_F64 / _F32).

@@ -372,4 +372,59 @@ inline int plan_groups(const std::vector<ProbLayout>& pl, const std::vector<int>
   return MHPC_OK;
 }
 
+// ---- the scope of a solve (mhpc_solve: the batch; mhpc_tick_problems: a list) -----------------
+// What the solve schedule runs over: `order`, the scope's problems by group, then problem number
+// (the scope's gidx), and go[], each group's range of positions in it (a group with no problem in
+// the scope is an empty range).  The scope of the whole batch is the plan's own gidx / go[].
+// With fresh problems in a solve that starts with the real rollout, that first op runs as two
+// launches over `split`: the rolled-out problems first, then the fresh ones (k_cost), each in the
+// order of `order`, so a contiguous range of positions stays contiguous and grouped in both
+// halves.  nf[pos] = problems before position pos that are not fresh (nf[n] = nnf, their total).
+struct SolveScope {
+  std::vector<int> order;
+  int ngrp = 0;
+  int go[MAXL + 1] = {};
+  std::vector<int> split, nf;
+  int nnf = 0;
+  int size() const { return (int)order.size(); }
+};
+// plan: the installed plan; list: n distinct problems of it in any order; fresh: [B] flags by
+// problem number (empty: none fresh).
+inline SolveScope solve_scope(const GroupPlan& plan, const std::vector<int>& list,
+                              const std::vector<char>& fresh) {
+  SolveScope s;
+  s.ngrp = plan.ngrp;
+  s.order = list;
+  std::sort(s.order.begin(), s.order.end(), [&](int a, int c) {
+    return plan.lid[a] != plan.lid[c] ? plan.lid[a] < plan.lid[c] : a < c;
+  });
+  for (int b : s.order) ++s.go[plan.lid[b] + 1];
+  for (int g = 0; g < plan.ngrp; ++g) s.go[g + 1] += s.go[g];
+  const int n = s.size();
+  s.nf.resize(n + 1);
+  for (int pos = 0; pos < n; ++pos) {
+    s.nf[pos] = s.nnf;
+    s.nnf += !(!fresh.empty() && fresh[s.order[pos]]);
+  }
+  s.nf[n] = s.nnf;
+  s.split.resize(n);
+  for (int pos = 0; pos < n; ++pos) {
+    const bool f = !fresh.empty() && fresh[s.order[pos]];
+    s.split[f ? s.nnf + pos - s.nf[pos] : s.nf[pos]] = s.order[pos];
+  }
+  return s;
+}
+// A sub-batch's share of a scope: positions [b0, b1), each group's range clipped to them.
+inline void scope_clip(const int* go, int ngrp, int b0, int b1, int* out) {
+  for (int g = 0; g <= ngrp; ++g) out[g] = std::min(std::max(go[g], b0), b1);
+}
+// The two halves of ranges go[] (a scope's, or a sub-batch's clipped ones) as ranges of `split`:
+// gof the rolled-out problems, goc the fresh ones.
+inline void scope_split(const SolveScope& s, const int* go, int* gof, int* goc) {
+  for (int g = 0; g <= s.ngrp; ++g) {
+    gof[g] = s.nf[go[g]];
+    goc[g] = s.nnf + go[g] - s.nf[go[g]];
+  }
+}
+
 }  // namespace MHPC_NS

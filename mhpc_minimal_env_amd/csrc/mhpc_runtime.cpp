@@ -71,6 +71,11 @@ struct Handle {
   // between is refused like one after new constraint parameters
   std::vector<double> cmd;
   bool cmd_changed = false;
+  // ... per problem: cmd_mark[b] = problem b's command changed since its references were last
+  // generated (mhpc_initialize / mhpc_update_problem(s) clear every mark, mhpc_tick_problems the
+  // listed problems'); ncmd counts the marks and cmd_changed is "any problem marked"
+  std::vector<char> cmd_mark;
+  int ncmd = 0;
   // parameter sets (mhpc_set_param_sets): the distinct sets in use, as the kernels read them
   // (real), and each problem's set by problem number; psets[pset_of[0]] is what the handle-wide
   // getters report.  sets_changed: a mixed call changed some problem's values on an initialised
@@ -103,6 +108,7 @@ struct Handle {
   std::vector<int> cmode;
   real* store = nullptr;
   int nbk = 0, nk_cap = 0, spmax = 0;
+  int nk_floor = 0;  // mhpc_reserve_knots: floor of the knot stride wherever it may change
   bool need_full = false;
   bool store_valid = false;  // store zeroed since the last initialize (memory_reset)
   // problems whose nominal k_init wrote since the last solve (mhpc_reset_problems) and no gait
@@ -131,6 +137,8 @@ struct Handle {
   int* dstep = nullptr;
   std::vector<int> hstep;
   hipEvent_t evctl = nullptr;
+  // mhpc_tick_problems: the events around the whole tick (ev0 / ev1 bracket its solve schedule)
+  hipEvent_t evt0 = nullptr, evt1 = nullptr;
 };
 
 // backward sweep: per WB knot partials record + x,u,y + refpos read, K,du,G written;
@@ -241,9 +249,10 @@ static int commit_groups(Handle* h, GroupPlan&& plan, bool keep_stride,
                          std::vector<ProbLayout>* pl = nullptr, std::vector<CostParams>* psets = nullptr,
                          std::vector<int>* pset_of = nullptr) {
   const int old_NK = h->sp.NK;
-  if (!keep_stride) {
-    if (int rc = ensure_knot_arrays(h, plan.NK)) return rc;
-    h->sp.NK = plan.NK;
+  if (!keep_stride) {  // the longest layout, or the floor of mhpc_reserve_knots
+    const int NK = std::max(plan.NK, h->nk_floor);
+    if (int rc = ensure_knot_arrays(h, NK)) return rc;
+    h->sp.NK = NK;
   }
   auto exchange = [&] {
     std::swap(h->plan, plan);
@@ -507,6 +516,7 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
   }
   h->pl.assign(batch, ProbLayout{h->desc, 0, 0});
   h->fresh.assign(batch, 0);
+  h->cmd_mark.assign(batch, 0);
   h->cmode.assign(batch, desc->mode_seq[0]);
 
   DevBufs& d = h->d;
@@ -698,6 +708,8 @@ static int initialize_async(Handle* h) {
 // message for the flags they look at.
 static void mark_current(Handle* h) {
   h->x0_changed = h->params_changed = h->sets_changed = h->cmd_changed = false;
+  std::fill(h->cmd_mark.begin(), h->cmd_mark.end(), 0);
+  h->ncmd = 0;
   h->solved = false;
 }
 // commands or constraint parameters pending (sets_changed is only ever raised with params_changed)
@@ -747,17 +759,28 @@ struct SolveBlock {
   bool mixed = false;
   SolveParams spf, spc;
 };
-// The block's two halves for a mixed OP_FULL: nf[pos] = problems before gidx position pos that
-// are not fresh, nnf their total (dsplit: those first, then the fresh ones, each in gidx order,
-// so a contiguous range of positions stays contiguous and grouped in both halves).
-static void split_block(SolveBlock& k, const std::vector<int>& nf, int nnf) {
+// What one run of the solve schedule covers (solve_async): the whole batch (mhpc_solve) or a list
+// of problems (mhpc_tick_problems).  sp is a copy of the handle's with the scope's go[] ranges and
+// ident (a list: ident = 0, go[] counted over the list), d the handle's arrays with gidx the
+// scope's order on the device; the launch variants and ro_store follow the scope's problem count
+// through this copy, never through Handle::sp.
+struct Scope {
+  SolveParams sp;
+  DevBufs d;
+  int n = 0;           // problems of the scope
+  bool full = false;   // the first op is the real rollout (a rotated nominal, a new x0)
+  // ... with fresh problems in the scope (Handle::fresh): that op splits into the rolled-out
+  // problems and the fresh ones (k_cost) over ss->split (mhpc_plan.h, solve_scope)
+  bool mixed = false;
+  const SolveScope* ss = nullptr;
+};
+// The block's two halves for a mixed OP_FULL (scope_split over the block's positions; dsplit: the
+// rolled-out problems first, then the fresh ones, each in the scope's order).
+static void split_block(SolveBlock& k, const SolveScope& ss) {
   k.mixed = true;
   k.spf = k.spc = k.sp;
   k.spf.ident = k.spc.ident = 0;
-  for (int g = 0; g <= k.sp.ngrp; ++g) {
-    k.spf.go[g] = nf[k.sp.go[g]];
-    k.spc.go[g] = nnf + k.sp.go[g] - nf[k.sp.go[g]];
-  }
+  scope_split(ss, k.sp.go, k.spf.go, k.spc.go);
 }
 
 // Problems [b0, b0 + sp.B) of the handle's arrays as the kernels index them (b * per-problem
@@ -780,7 +803,7 @@ static DevBufs block_bufs(const DevBufs& d, const SolveParams& sp, size_t b0) {
   return o;
 }
 
-static std::vector<SolveOp> solve_ops(const Handle* h) {
+static std::vector<SolveOp> solve_ops(const Handle* h, bool full) {
   const mhpc_hsddp_option& o = h->opt;
   std::vector<SolveOp> ops;
   int n_al = 0;
@@ -789,7 +812,7 @@ static std::vector<SolveOp> solve_ops(const Handle* h) {
   for (int ddp = 1; ddp <= o.max_DDP_iter; ++ddp) max_ddp = ddp;
   for (int al = 1; al <= n_al; ++al) {
     // forward_sweep(0); a real rollout for the rotated nominal of update_problem
-    ops.push_back({al == 1 && h->need_full ? OP_FULL : OP_COST, al, 0, 0});
+    ops.push_back({al == 1 && full ? OP_FULL : OP_COST, al, 0, 0});
     ops.push_back({OP_PAR, al, 0, 0});
     for (int ddp = 1; ddp <= max_ddp; ++ddp) {
       ops.push_back({OP_BWS, al, ddp, max_ddp});
@@ -856,10 +879,10 @@ static int issue_op(Handle* h, const SolveBlock& k, const SolveOp& op) {
   return MHPC_OK;
 }
 
-static int sub_batches(const Handle* h) {
+static int sub_batches(const Handle* h, int problems) {
   int n = h->nsub_req;
   if (n == 0) n = 1;  // automatic: one block (DESIGN.md §3 has the measured A/B)
-  return std::min(n, h->sp.B);
+  return std::min(n, problems);
 }
 
 static int ensure_sub_streams(Handle* h, int n) {
@@ -880,37 +903,24 @@ static int ensure_sub_streams(Handle* h, int n) {
   return MHPC_OK;
 }
 
-static int solve_async(Handle* h) {
-  // stored line-search trials for this batch's launch shape (unless set by the caller)
-  if (!h->ro_store_req) h->sp.ro_store = ro_store_auto(h->sp);
-  const std::vector<SolveOp> ops = solve_ops(h);
+static int solve_async(Handle* h, Scope& sc) {
+  // stored line-search trials for this scope's launch shape (unless set by the caller)
+  if (!h->ro_store_req) sc.sp.ro_store = ro_store_auto(sc.sp);
+  const std::vector<SolveOp> ops = solve_ops(h, sc.full);
   const int nops = (int)ops.size();
-  const int nsub = sub_batches(h);
+  const int nsub = sub_batches(h, sc.n);
   int rc;
   // fresh problems in a solve that starts with the real rollout: the split order to the device
-  const bool mixed = h->need_full && h->nfresh > 0;
-  std::vector<int> nf;
-  int nnf = 0;
+  const bool mixed = sc.mixed;
   if (mixed) {
-    const int B = h->sp.B;
-    nf.resize(B + 1);
-    for (int pos = 0; pos < B; ++pos) {
-      nf[pos] = nnf;
-      nnf += !h->fresh[h->plan.gidx[pos]];
-    }
-    nf[B] = nnf;
-    std::vector<int> split(B);
-    for (int pos = 0; pos < B; ++pos) {
-      const bool f = h->fresh[h->plan.gidx[pos]];
-      split[f ? nnf + pos - nf[pos] : nf[pos]] = h->plan.gidx[pos];
-    }
-    HIPCHK(hipMemcpyAsync(h->dsplit, split.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->dsplit, sc.ss->split.data(), (size_t)sc.n * sizeof(int),
+                          hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   if (nsub <= 1) {
-    SolveBlock k{h->sp,       h->d,      h->stream,  h->stream2, h->stream3,
+    SolveBlock k{sc.sp,       sc.d,      h->stream,  h->stream2, h->stream3,
                  h->evfork,   h->evjoin, h->evpfork, h->evpjoin};
-    if (mixed) split_block(k, nf, nnf);
+    if (mixed) split_block(k, *sc.ss);
     for (const SolveOp& op : ops)
       if ((rc = issue_op(h, k, op))) {
         // an issue failure may leave launches queued on the second / third stream (the
@@ -928,17 +938,18 @@ static int solve_async(Handle* h) {
     if ((rc = ensure_sub_streams(h, nsub))) return rc;
     HIPCHK(hipEventRecord(h->evstart, h->stream));
     std::vector<SolveBlock> blk(nsub);
-    // even partition: every block non-empty (sub_batches() <= B), sizes differ by <= 1
-    const int B = h->sp.B;
+    // even partition of the scope's positions: every block non-empty (sub_batches() <= n), sizes
+    // differ by <= 1
+    const int B = sc.n;
     for (int s = 0; s < nsub; ++s) {
       const Handle::SubStreams& ss = h->subs[s];
       SolveBlock& k = blk[s];
       const int b0 = (int)((int64_t)s * B / nsub), b1 = (int)((int64_t)(s + 1) * B / nsub);
-      // the block's problems: gidx positions [b0, b1) (each group's range clipped to them);
+      // the block's problems: the scope's positions [b0, b1) (each group's range clipped to them);
       // the arrays stay the handle's (gidx holds absolute problem indices)
-      k.sp = h->sp;
-      for (int g = 0; g <= k.sp.ngrp; ++g) k.sp.go[g] = std::min(std::max(h->sp.go[g], b0), b1);
-      k.d = h->d;
+      k.sp = sc.sp;
+      scope_clip(sc.sp.go, sc.sp.ngrp, b0, b1, k.sp.go);
+      k.d = sc.d;
       k.s1 = ss.s1;
       k.s2 = ss.s2;
       k.fork = ss.fork;
@@ -946,7 +957,7 @@ static int solve_async(Handle* h) {
       k.s3 = ss.s3;
       k.pfork = ss.pfork;
       k.pjoin = ss.pjoin;
-      if (mixed) split_block(k, nf, nnf);
+      if (mixed) split_block(k, *sc.ss);
       HIPCHK(hipStreamWaitEvent(k.s1, h->evstart, 0));
     }
     // block s runs `lag` launches behind block s - 1 (its first launch waits on the gate
@@ -990,42 +1001,42 @@ static int solve_async(Handle* h) {
     HIPCHK(ej);
   }
   // totals of the per-problem counters per group (tiny reduction, NCNT words each)
-  HIPCHK(hipMemsetAsync(h->dcnt, 0, (size_t)h->sp.ngrp * NCNT * sizeof(unsigned long long), h->stream));
-  HIPCHK(launch_reduce_counters(h->sp, h->d, h->dcnt, h->stream));
+  HIPCHK(hipMemsetAsync(h->dcnt, 0, (size_t)sc.sp.ngrp * NCNT * sizeof(unsigned long long), h->stream));
+  HIPCHK(launch_reduce_counters(sc.sp, sc.d, h->dcnt, h->stream));
   return MHPC_OK;
 }
 
-int api_solve(Handle* h, int32_t* status) {
-  if (!h) return fail(MHPC_ERR_INVALID, "null handle");
-  if (!h->initialized) return fail(MHPC_ERR_STATE, "mhpc_initialize must precede mhpc_solve");
-  if (h->solved) return fail(MHPC_ERR_STATE, "solve already ran: call mhpc_initialize or mhpc_update_problem");
-  if (h->x0_changed)
-    return fail(MHPC_ERR_STATE, "x0 changed: call mhpc_initialize or mhpc_update_problem first");
-  if (pending(h)) return fail(MHPC_ERR_STATE, h->params_changed ? kParamsPending : kCmdPending);
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipEventRecord(h->ev0, h->stream));
-  int rc = solve_async(h);
-  if (rc) return rc;
-  HIPCHK(hipEventRecord(h->ev1, h->stream));
-  HIPCHK(hipMemcpyAsync(h->gcnt, h->dcnt, (size_t)h->sp.ngrp * NCNT * sizeof(unsigned long long),
-                        hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+// The scope of the whole batch: the handle's own sp / gidx; the first op the real rollout after an
+// update_problem (need_full), split when a reset left fresh problems (ss: the caller's storage).
+static Scope batch_scope(Handle* h, SolveScope& ss) {
+  Scope sc;
+  sc.sp = h->sp;
+  sc.d = h->d;
+  sc.n = h->sp.B;
+  sc.full = h->need_full;
+  sc.mixed = h->need_full && h->nfresh > 0;
+  if (sc.mixed) {
+    ss = solve_scope(h->plan, h->plan.gidx, h->fresh);
+    sc.ss = &ss;
+  }
+  return sc;
+}
+
+// After a scope's solve has drained: its counters (per group, summed over the scope's problems)
+// and their byte / flop accounting, the profile.
+static int account_solve(Handle* h, const Scope& sc) {
   for (int i = 0; i < NCNT; ++i) {
     h->cnt[i] = 0;
-    for (int g = 0; g < h->sp.ngrp; ++g) h->cnt[i] += h->gcnt[g][i];
+    for (int g = 0; g < sc.sp.ngrp; ++g) h->cnt[i] += h->gcnt[g][i];
   }
   HIPCHK(hipEventElapsedTime(&h->solve_ms, h->ev0, h->ev1));
-  h->solved = true;
-  h->need_full = false;
-  std::fill(h->fresh.begin(), h->fresh.end(), 0);
-  h->nfresh = 0;
-  rc = collect_profile(h);
+  const int rc = collect_profile(h);
   if (rc) return rc;
   const unsigned long long* c = h->cnt;
-  for (int g = 0; g < h->sp.ngrp; ++g) {  // per group: its problems' counters x its layout's bytes
+  for (int g = 0; g < sc.sp.ngrp; ++g) {  // per group: its problems' counters x its layout's bytes
     const unsigned long long* cg = h->gcnt[g];
     const ByteModel& m = h->plan.bym[g];
-    const SolveParams& sp = h->sp;
+    const SolveParams& sp = sc.sp;
     h->kbytes[K_FULL] += cg[C_FWD] * m.cost;
     // the trials that store their records (RO_STORE_FIRST; the re-rolls of the others, rare,
     // are not counted)
@@ -1042,6 +1053,32 @@ int api_solve(Handle* h, int32_t* status) {
   h->kflops[K_BWS_SRB] += fb1 * kFlopFbKnot;
   h->kbytes[K_BWS] += c[C_BWS_KNOTS_WB] * kBwsWbKnot + fb * kBwsFbKnot + c[C_PX_READS] * kBwsPx;
   h->kflops[K_BWS] += c[C_BWS_KNOTS_WB] * kFlopWbKnot + fb * kFlopFbKnot + c[C_PX_READS] * kFlopPx;
+  return MHPC_OK;
+}
+
+int api_solve(Handle* h, int32_t* status) {
+  if (!h) return fail(MHPC_ERR_INVALID, "null handle");
+  if (!h->initialized) return fail(MHPC_ERR_STATE, "mhpc_initialize must precede mhpc_solve");
+  if (h->solved) return fail(MHPC_ERR_STATE, "solve already ran: call mhpc_initialize or mhpc_update_problem");
+  if (h->x0_changed)
+    return fail(MHPC_ERR_STATE, "x0 changed: call mhpc_initialize or mhpc_update_problem first");
+  if (pending(h)) return fail(MHPC_ERR_STATE, h->params_changed ? kParamsPending : kCmdPending);
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipEventRecord(h->ev0, h->stream));
+  SolveScope ss;
+  Scope sc = batch_scope(h, ss);
+  int rc = solve_async(h, sc);
+  h->sp.ro_store = sc.sp.ro_store;  // (the batch's own choice stays visible in the handle's sp)
+  if (rc) return rc;
+  HIPCHK(hipEventRecord(h->ev1, h->stream));
+  HIPCHK(hipMemcpyAsync(h->gcnt, h->dcnt, (size_t)h->sp.ngrp * NCNT * sizeof(unsigned long long),
+                        hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->solved = true;
+  h->need_full = false;
+  std::fill(h->fresh.begin(), h->fresh.end(), 0);
+  h->nfresh = 0;
+  if ((rc = account_solve(h, sc))) return rc;
   if (status) {
     std::vector<ProbState> st(h->sp.B);
     D2H(st.data(), h->d.st, st.size() * sizeof(ProbState));
@@ -1487,12 +1524,22 @@ int api_get_cost_gradients(Handle* h, int phase, int first, int count, double* l
 // The phase-buffer store of the receding-horizon loop, [B][spmax][nbk][SREC], zeroed at its
 // first use after an initialize (the reference's memory_reset of its phase buffers); sized for
 // the current layouts (buffers of N_TIMESTEPS_MAX = 110 knots, or the longest phase).
+// The store's shape as ensure_store makes it (or has made it): knots a buffer, buffers a problem.
+static void store_shape(const Handle* h, int* nbk_out, int* spmax_out) {
+  int nbk = h->nbk, spmax = h->spmax;
+  if (!h->store_valid) {
+    nbk = kPhaseBufKnots;
+    for (const Layout& L : h->plan.lays)
+      for (int p = 0; p < L.P; ++p) nbk = std::max(nbk, L.N[p]);
+    spmax = h->sp.pmax;
+  }
+  *nbk_out = nbk;
+  *spmax_out = spmax;
+}
 static int ensure_store(Handle* h) {
   if (h->store_valid) return MHPC_OK;
-  int nbk = kPhaseBufKnots;
-  for (const Layout& L : h->plan.lays)
-    for (int p = 0; p < L.P; ++p) nbk = std::max(nbk, L.N[p]);
-  const int spmax = h->sp.pmax;
+  int nbk, spmax;
+  store_shape(h, &nbk, &spmax);
   const size_t bytes = (size_t)h->sp.B * spmax * nbk * kStoreRec * sizeof(real);
   if (!h->store || nbk != h->nbk || spmax != h->spmax) {
     if (h->store) HIPCHK(hipFree(h->store));
@@ -1503,6 +1550,18 @@ static int ensure_store(Handle* h) {
   }
   HIPCHK(hipMemsetAsync(h->store, 0, bytes, h->stream));
   h->store_valid = true;
+  return MHPC_OK;
+}
+
+static int check_gaits(int n_gaits, const mhpc_gait* gaits) {
+  if (n_gaits < 1 || n_gaits > MAXL) return fail(MHPC_ERR_INVALID, "n_gaits must be 1..MHPC_MAX_LAYOUTS");
+  for (int gi = 0; gi < n_gaits; ++gi) {
+    const mhpc_gait& g = gaits[gi];
+    if (g.n_modes < 1 || g.n_modes > MHPC_MAX_PHASES)
+      return fail(MHPC_ERR_INVALID, "gait needs 1..16 modes");
+    for (int i = 0; i < g.n_modes; ++i)
+      if (g.modes[i] < 1 || g.modes[i] > 4) return fail(MHPC_ERR_INVALID, "gait mode out of range");
+  }
   return MHPC_OK;
 }
 
@@ -1517,14 +1576,7 @@ int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const in
                         const int32_t* steps) {
   if (!h || !gaits) return fail(MHPC_ERR_INVALID, "null argument");
   if (!h->initialized) return fail(MHPC_ERR_STATE, "mhpc_initialize must precede mhpc_update_problem");
-  if (n_gaits < 1 || n_gaits > MAXL) return fail(MHPC_ERR_INVALID, "n_gaits must be 1..MHPC_MAX_LAYOUTS");
-  for (int gi = 0; gi < n_gaits; ++gi) {
-    const mhpc_gait& g = gaits[gi];
-    if (g.n_modes < 1 || g.n_modes > MHPC_MAX_PHASES)
-      return fail(MHPC_ERR_INVALID, "gait needs 1..16 modes");
-    for (int i = 0; i < g.n_modes; ++i)
-      if (g.modes[i] < 1 || g.modes[i] > 4) return fail(MHPC_ERR_INVALID, "gait mode out of range");
-  }
+  if (int rc = check_gaits(n_gaits, gaits)) return rc;
   HIPCHK(hipSetDevice(h->device));
   int rc = ensure_store(h);
   if (rc) return rc;
@@ -1565,6 +1617,171 @@ int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const in
 
 int api_update_problem(Handle* h, const mhpc_gait* gait) {
   return api_update_problems(h, 1, gait, nullptr, nullptr);
+}
+
+// ---- per-problem ticks (mhpc_tick_problems) ---------------------------------------------------
+// In the reference every robot is its own MHPCLocomotion and ticks when its own gait mode ends:
+// set_initial_condition + update_problem (MHPCLocomotion.cpp:107-158) + solve_mhpc (:167-195), and
+// no other robot notices.  Here: the listed problems take their x0 rows and gait steps, their
+// references and AL / ReB state are regenerated from their current commands, and the solve
+// schedule runs over them alone (a Scope of the list); each comes out bit for bit as after
+// mhpc_set_x0 + mhpc_update_problems + mhpc_solve in a handle of its own, and every other
+// problem's device records stay bit for bit.  Like mhpc_reset_problems it never re-strides or
+// reallocates; everything that can refuse the call is decided on working copies before the handle
+// or the device is touched.  Device work is proportional to n (but the one-off zeroing of the
+// phase-buffer store); the host plan and the group-table upload stay O(batch) and are skipped
+// when no listed problem takes a step.
+int api_tick_problems(Handle* h, int n, const int32_t* problems, const double* x0, int n_gaits,
+                      const mhpc_gait* gaits, const int32_t* gait_of, const int32_t* steps,
+                      int32_t* status, float* ms) {
+  if (!h || !problems) return fail(MHPC_ERR_INVALID, "null argument");
+  if (!h->initialized) return fail(MHPC_ERR_STATE, "mhpc_initialize must precede mhpc_tick_problems");
+  if (!h->solved)
+    return fail(MHPC_ERR_STATE, "mhpc_solve must precede mhpc_tick_problems (the last batch-wide step was no solve)");
+  if (h->params_changed) return fail(MHPC_ERR_STATE, kParamsPending);
+  const int B = h->sp.B;
+  if (n < 1 || n > B) return fail(MHPC_ERR_INVALID, "n must be 1..batch");
+  std::vector<char> listed(B, 0);
+  bool any_step = false;
+  for (int i = 0; i < n; ++i) {
+    const int b = problems[i];
+    if (b < 0 || b >= B) return fail(MHPC_ERR_INVALID, "problem out of range");
+    if (listed[b]) return fail(MHPC_ERR_INVALID, "problem listed twice");
+    listed[b] = 1;
+    const int ns = steps ? steps[i] : 1;
+    if (ns < 0 || ns > 1024) return fail(MHPC_ERR_INVALID, "steps must be 0..1024");
+    any_step = any_step || ns > 0;
+  }
+  if (!gaits && any_step) return fail(MHPC_ERR_INVALID, "gaits may be null only when every step is 0");
+  int rc;
+  if (gaits && (rc = check_gaits(n_gaits, gaits))) return rc;
+  for (int i = 0; gaits && gait_of && i < n; ++i)
+    if (gait_of[i] < 0 || gait_of[i] >= n_gaits) return fail(MHPC_ERR_INVALID, "gait index out of range");
+  const int r = x0_row(h);
+  for (size_t i = 0; x0 && i < (size_t)n * r; ++i)
+    if (!std::isfinite(x0[i])) return fail(MHPC_ERR_INVALID, "x0 must be finite");
+  // the listed problems' gait steps on working copies; the arrays stay as they are, so each new
+  // layout must fit the knot stride and the phase buffers (as the store is, or will be made)
+  int nbk, spmax;
+  store_shape(h, &nbk, &spmax);
+  std::vector<ProbLayout> npl;
+  std::vector<int> ncm;
+  GroupPlan plan;
+  if (any_step) {
+    npl = h->pl;
+    ncm = h->cmode;
+    for (int i = 0; i < n; ++i) {
+      const int b = problems[i], ns = steps ? steps[i] : 1;
+      if (ns == 0) continue;
+      PLANCHK(advance_gait, npl[b], ncm[b], gaits[gait_of ? gait_of[i] : 0], ns, nbk);
+      PLANCHK(fits_arrays, npl[b], h->sp.NK, true, nbk, spmax, false);
+    }
+    PLANCHK(plan_groups, npl, h->pset_of, plan);  // too many groups: nothing changed
+  }
+  const GroupPlan& np = any_step ? plan : h->plan;
+  // the scope: the list by its groups after the commit; fresh (mhpc_reset_problems) and no step:
+  // the first forward_sweep(0) stays the cost evaluation
+  std::vector<char> fr(B, 0);
+  for (int i = 0; i < n; ++i) fr[problems[i]] = h->fresh[problems[i]] && (steps ? steps[i] : 1) == 0;
+  const std::vector<int> list(problems, problems + n);
+  const SolveScope ss = solve_scope(np, list, fr);
+  std::vector<real> rows;
+  if (x0) {  // in list order, padded as mhpc_set_x0 pads them
+    rows.assign((size_t)n * 14, real(0));
+    for (int i = 0; i < n; ++i) {
+      const int nb = h->pl[problems[i]].desc.n_wb > 0 ? 14 : 6;
+      std::copy(x0 + (size_t)i * r, x0 + (size_t)i * r + nb, rows.begin() + (size_t)i * 14);
+    }
+  }
+  // ---- nothing of the handle or the device has changed up to here ----
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (!h->evt0) HIPCHK(hipEventCreate(&h->evt0));
+  if (!h->evt1) HIPCHK(hipEventCreate(&h->evt1));
+  DevTemp<int> ti(h->stream);
+  DevTemp<real> tr(h->stream);
+  const int* dlist = ti.in(std::vector<int>(list));
+  const int* dorder = ti.in(std::vector<int>(ss.order));
+  int* dstatus = status ? ti.alloc(n) : nullptr;
+  const real* drows = rows.empty() ? nullptr : tr.in(std::move(rows));
+  if (ti.e != hipSuccess) return dev_fail("mhpc_tick_problems", ti.e);
+  if (tr.e != hipSuccess) return dev_fail("mhpc_tick_problems", tr.e);
+  // from here a failure leaves the listed problems undefined (as a failed mhpc_reset_problems);
+  // nothing of the handle's may stay queued behind it
+  auto run = [&]() -> int {
+    HIPCHK(hipEventRecord(h->evt0, h->stream));
+    if (drows) HIPCHK(launch_scatter_x0(h->d, n, dlist, drows, h->stream));
+    if (int rc = ensure_store(h)) return rc;
+    // phases write through to their buffers in the reference: the listed problems' current
+    // solutions under their layouts before the commit
+    HIPCHK(launch_store_list(h->sp, h->d, n, dlist, h->store, h->nbk, h->spmax, 1, h->stream));
+    if (any_step) {
+      if (int rc = commit_groups(h, std::move(plan), true, &npl)) return rc;
+      for (int i = 0; i < n; ++i) h->cmode[problems[i]] = ncm[problems[i]];
+    }
+    Scope sc;
+    sc.sp = h->sp;
+    sc.sp.ident = 0;
+    std::copy(ss.go, ss.go + MAXL + 1, sc.sp.go);
+    sc.d = h->d;
+    sc.d.gidx = dorder;
+    sc.n = n;
+    sc.full = true;
+    sc.mixed = ss.nnf < n;
+    sc.ss = &ss;
+    HIPCHK(launch_reset(sc.sp, sc.d, h->stream));  // refs from x0 and the command, AL/ReB init, nom_slot = 0
+    if (h->psets.size() > 1) HIPCHK(launch_init_params(sc.sp, sc.d, h->stream));
+    HIPCHK(launch_store_list(h->sp, h->d, n, dlist, h->store, h->nbk, h->spmax, 0, h->stream));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    if (int rc = solve_async(h, sc)) return rc;
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    if (dstatus) HIPCHK(launch_status_list(h->d, n, dlist, dstatus, h->stream));
+    HIPCHK(hipEventRecord(h->evt1, h->stream));
+    HIPCHK(hipMemcpyAsync(h->gcnt, h->dcnt, (size_t)sc.sp.ngrp * NCNT * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, h->stream));
+    if (dstatus)
+      HIPCHK(hipMemcpyAsync(status, dstatus, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (ms) HIPCHK(hipEventElapsedTime(ms, h->evt0, h->evt1));
+    return account_solve(h, sc);
+  };
+  rc = run();
+  // the listed problems have their references and their solve, whatever came of it: no longer
+  // fresh, no command pending
+  for (int i = 0; i < n; ++i) {
+    const int b = problems[i];
+    if (h->fresh[b]) {
+      h->fresh[b] = 0;
+      --h->nfresh;
+    }
+    if (h->cmd_mark[b]) {
+      h->cmd_mark[b] = 0;
+      --h->ncmd;
+    }
+  }
+  h->cmd_changed = h->ncmd > 0;
+  if (rc) {
+    const std::string why = mhpc_g_err;
+    for (hipStream_t q : {h->stream3, h->stream2, h->stream}) (void)hipStreamSynchronize(q);
+    mhpc_g_err = why;
+  }
+  return rc;
+}
+
+// Floor of the knot stride of the packed arrays: a fleet created at one gait point can then tick
+// into a longer layout (mhpc_tick_problems never re-strides).  Before mhpc_initialize only: the
+// arrays hold nothing yet, so the stride is set here and kept by every later commit that may
+// re-stride (commit_groups).
+int api_reserve_knots(Handle* h, int knots) {
+  if (!h) return fail(MHPC_ERR_INVALID, "null handle");
+  if (h->initialized) return fail(MHPC_ERR_STATE, "mhpc_reserve_knots must precede mhpc_initialize");
+  if (knots < 1 || knots > MHPC_MAX_KNOTS) return fail(MHPC_ERR_INVALID, "knots must be 1..MHPC_MAX_KNOTS");
+  HIPCHK(hipSetDevice(h->device));
+  const int NK = std::max(h->plan.NK, knots);
+  if (int rc = ensure_knot_arrays(h, NK)) return rc;
+  h->sp.NK = NK;
+  h->nk_floor = knots;
+  return MHPC_OK;
 }
 
 // Per-problem phase layouts (the batch axis over gait schedules): problem b gets
@@ -1854,8 +2071,15 @@ int api_set_commands(Handle* h, const double* vel, const double* height) {
   for (size_t b = 0; b < B; ++b) hc[b] = Cmd{(real)nc[2 * b], (real)nc[2 * b + 1]};
   HIPCHK(hipMemcpyAsync(h->dcmd, hc.data(), B * sizeof(Cmd), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  if (h->initialized) {  // the problems whose value changed: pending until their next references
+    for (size_t b = 0; b < B; ++b)
+      if ((nc[2 * b] != h->cmd[2 * b] || nc[2 * b + 1] != h->cmd[2 * b + 1]) && !h->cmd_mark[b]) {
+        h->cmd_mark[b] = 1;
+        ++h->ncmd;
+      }
+    h->cmd_changed = h->ncmd > 0;
+  }
   h->cmd = nc;
-  if (h->initialized) h->cmd_changed = true;
   return MHPC_OK;
 }
 int api_get_commands(Handle* h, double* vel, double* height) {
@@ -2010,6 +2234,8 @@ void api_destroy(Handle* h) {
   if (h->dsplit) (void)hipFree(h->dsplit);
   if (h->dstep) (void)hipFree(h->dstep);
   if (h->evctl) (void)hipEventDestroy(h->evctl);
+  if (h->evt0) (void)hipEventDestroy(h->evt0);
+  if (h->evt1) (void)hipEventDestroy(h->evt1);
   for (hipEvent_t e : h->evpool) (void)hipEventDestroy(e);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);

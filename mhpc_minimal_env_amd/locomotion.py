@@ -390,6 +390,51 @@ class MHPCLocomotion:
         if descs is not None:
             self._refresh_descs()
 
+    # -- per-problem ticks: update and solve the listed problems only --------------------------
+    def tick_problems(self, problems, x0=None, gaits=None, gait_of=None, steps=None) -> np.ndarray:
+        """mhpc_tick_problems: one MPC tick of the listed problems and of nobody else -- the
+        reference's set_initial_condition + update_problem + solve_mhpc on single controllers of
+        a fleet, each when its own gait mode ends.  x0 [len(problems)][r] in list order (None:
+        each keeps its current device row); listed problem i takes steps[i] gait steps (None: one)
+        of gaits[gait_of[i]] (None: gaits[0]; gaits None: the handle's gait, or no gait at all
+        when every step is 0).  Each listed problem comes out as after the three calls in a
+        handle of its own; every other problem keeps its state bit for bit.  Returns the listed
+        problems' status in list order (also written to self.status[problems]); self.last_tick_ms
+        is the device time of the whole tick."""
+        import ctypes
+        pr = np.ascontiguousarray(problems, dtype=np.int32).reshape(-1)
+        if x0 is not None:
+            x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).reshape(pr.size, -1))
+            if x0.shape[1] != self._x0_row():
+                raise ValueError("x0 must be [len(problems)][x0 row length]")
+        st = None if steps is None else np.ascontiguousarray(steps, dtype=np.int32).reshape(-1)
+        if st is not None and st.shape != pr.shape:
+            raise ValueError("steps must have one entry per listed problem")
+        gop = None if gait_of is None else np.ascontiguousarray(gait_of, dtype=np.int32).reshape(-1)
+        if gop is not None and gop.shape != pr.shape:
+            raise ValueError("gait_of must have one entry per listed problem")
+        if gaits is None and not (st is not None and not st.any()):
+            gaits = [self.gait]
+        gs = None if gaits is None else (capi.GaitC * len(gaits))(*[g.to_c() for g in gaits])
+        status = np.zeros(pr.size, dtype=np.int32)
+        ms = ctypes.c_float(0.0)
+        capi.check(capi.lib().mhpc_tick_problems(self._h, int(pr.size), capi.iptr(pr), capi.dptr(x0),
+                                                 0 if gaits is None else len(gaits), gs,
+                                                 capi.iptr(gop), capi.iptr(st), capi.iptr(status),
+                                                 ctypes.byref(ms)), "mhpc_tick_problems")
+        self.last_tick_ms = float(ms.value)
+        self.status[pr] = status
+        if x0 is not None and not self._x0_on_device:  # what the next update_problem(s) hands back
+            self._x0 = self._x0.copy()
+            self._x0[pr] = x0
+        self._refresh_descs()
+        return status
+
+    def reserve_knots(self, knots: int):
+        """mhpc_reserve_knots: floor of the knot stride of the packed arrays, so that later ticks
+        can step into longer layouts; before initialization()."""
+        capi.check(capi.lib().mhpc_reserve_knots(self._h, int(knots)), "mhpc_reserve_knots")
+
     # -- copies of live problems: a slot becomes another controller ---------------------------
     def copy_problems(self, dst_problems, src_problems, src: Optional["MHPCLocomotion"] = None) -> float:
         """mhpc_copy_problems: problem dst_problems[i] of this handle becomes a copy of problem
