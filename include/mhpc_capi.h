@@ -46,6 +46,10 @@
  *                        build_problem / update_problem hand to ReferenceGen
  *                        (MHPCLocomotion.cpp:98-103): per-problem user commands in one batch;
  *                        mhpc_get_commands reads them back
+ *   mhpc_set_option_sets MultiPhaseDDP::_option of every controller (MultiPhaseDDP.h,
+ *                        MHPC_CompoundTypes.h:196-212): per-problem iteration budgets, thresholds
+ *                        and AL / ReB switches in one batch; mhpc_set_options `_option = o` on every
+ *                        controller, mhpc_get_options / mhpc_get_problem_options read them back
  *   mhpc_get_reference_problems  ReferenceGen::generate_ref's ms_ref_*[p][k].x
  *                        (ReferenceGen.h:53-109): the tracking reference the costs use
  *   mhpc_rollout_policy  set_initial_condition(x) + forward_sweep_dynamics_only(0)
@@ -71,6 +75,7 @@ extern "C" {
 #define MHPC_MAX_PHASES 16
 #define MHPC_MAX_KNOTS 1024
 #define MHPC_MAX_LAYOUTS 32   /* distinct phase layouts (gait schedules) per handle */
+#define MHPC_MAX_OPTION_SETS 32 /* distinct mhpc_hsddp_option records per handle */
 #define MHPC_TRACE_LEN 64
 
 typedef enum {
@@ -313,9 +318,13 @@ int mhpc_reserve_knots(mhpc_handle* h, int knots);
  *    records and impact Jacobians, the solver state (status, trace, counters, AL / ReB values, the
  *    option values a solve rewrites), the x0 row on the device, the position references, the
  *    layout with its phase-buffer rotation and gait point, the problem's rows of the phase-buffer
- *    store -- and, unlike mhpc_reset_problems, the command and the parameter set: a clone that kept
- *    the destination's would not be a clone (the source's set joins dst's sets under
- *    mhpc_set_param_sets' merge rules; change either afterwards with the setters).  After the call
+ *    store -- and, unlike mhpc_reset_problems, the command, the parameter set and the option set: a
+ *    clone that kept the destination's would not be a clone (the source's parameter set joins dst's
+ *    sets under mhpc_set_param_sets' merge rules; change either afterwards with the setters).  The
+ *    option set travels as an index: inside one handle the destination takes the source's; between
+ *    handles the source problem's record (every field) must already be one of dst's option sets
+ *    (mhpc_set_option_sets) -- the copy never adds a record to dst's table, so it never changes
+ *    dst's launch schedule.  After the call
  *    every getter reports for the destination what it reports for the source, and every later
  *    mhpc_solve / mhpc_update_problem(s) / mhpc_advance_x0 of the destination equals the source's
  *    under the same inputs, bit for bit, in both precisions (tests/test_gpu_copy.py).
@@ -328,11 +337,13 @@ int mhpc_reserve_knots(mhpc_handle* h, int knots);
  *  - MHPC_ERR_INVALID, before anything changes: a null pointer; n < 1 or n > dst's batch; a
  *    problem number out of range; a destination listed twice (a source may repeat: one to many);
  *    with dst == src a number that is both a source and a destination; handles of different
- *    precision, device, mhpc_hsddp_option (every field) or backward-sweep arithmetic
+ *    precision, device, alpha (the line-search grid) or backward-sweep arithmetic
  *    (MHPC_VARIANT_SWEEP_BITS 32 on one side only: the one kernel variant that changes results;
  *    every other variant computes the same bits and may differ); a source layout with more knots than
  *    dst's knot stride or -- once dst's store exists -- more phases or a longer phase than it holds;
- *    x0 rows of different width (14 vs 6); more than MHPC_MAX_LAYOUTS (layout, set) groups.
+ *    x0 rows of different width (14 vs 6); more than MHPC_MAX_LAYOUTS (layout, set) groups; a
+ *    source problem whose option record is none of dst's (two handles whose options differ in any
+ *    field have no common record).
  *  - MHPC_ERR_STATE: either handle before mhpc_initialize, or with commands, constraint parameters
  *    or parameter sets pending, or the two handles at different points of the call order (one just
  *    solved, the other just initialized or updated).  A pending x0 is allowed: the device's current
@@ -451,6 +462,61 @@ int mhpc_get_problem_params(mhpc_handle* h, int problem, mhpc_cost_weights* w,
                             mhpc_constraint_params* c);
 /* Distinct sets in use (1 for a fresh handle). */
 int mhpc_num_param_sets(mhpc_handle* h, int* n);
+
+/* ---- per-problem option sets: the batch axis over iteration budgets and thresholds ---------
+ * In the reference every MHPCLocomotion owns its MultiPhaseDDP::_option (MultiPhaseDDP.h,
+ * MHPC_CompoundTypes.h:196-212), so a fleet of controllers is also a fleet of option values: a
+ * robot just reset wants the full AL x DDP budget, the warm robots ticking beside it one AL
+ * iteration and one or two DDP iterations.  Problem b solves with sets[set_of_problem[b]] (host
+ * array of n_sets records, 1 <= n_sets <= MHPC_MAX_OPTION_SETS); set_of_problem == NULL:
+ * b % n_sets.  mhpc_set_options gives every problem one record.  A handle starts with one set,
+ * the option given to mhpc_create.
+ *  - Sets belong to the problem number: they survive mhpc_set_layouts, mhpc_update_problem(s),
+ *    mhpc_reset_problems and ticks, as commands and parameter sets do.
+ *  - Merging: records that are equal in every field, bit for bit, are merged and records no
+ *    problem uses are dropped; mhpc_num_option_sets counts what is left.  At most
+ *    MHPC_MAX_OPTION_SETS distinct records may be in use: a call that would exceed it is
+ *    MHPC_ERR_INVALID.  mhpc_get_options reports problem 0's record, mhpc_get_problem_options
+ *    problem b's (the reserved field zero).
+ *  - alpha stays handle-wide: it fixes the line-search grid and with it the trajectory slots and
+ *    the arrays' shape.  A record whose alpha differs bitwise from the one given to mhpc_create
+ *    is MHPC_ERR_INVALID.  Every other field is validated as mhpc_create validates it: every real
+ *    field finite, iteration budgets at most 2^20.
+ *  - Options are no grouping dimension: problems of different sets share launches, blocks and
+ *    waves, and each reads its own record in its control flow.  They do not count against
+ *    MHPC_MAX_LAYOUTS.  Each problem's arithmetic is the one it gets in a handle created with its
+ *    record, bit for bit, in both precisions and every launch variant
+ *    (tests/test_gpu_option_sets.py).
+ *  - The launch schedule of a solve runs to the largest max_AL_iter and max_DDP_iter among the
+ *    problems it covers -- the batch for mhpc_solve, the list for mhpc_tick_problems -- and a
+ *    problem with a smaller budget sits the rest out, as it would in a handle of its own
+ *    (max_DDP_iter = 0: no sweep and no line search; max_AL_iter = 0: only the final AL update,
+ *    and mhpc_initialize / mhpc_reset_problems leave that problem's SRB phases at zero states, as
+ *    the reference's initialization() does -- only the first forward sweep rolls them out.  If
+ *    such a problem is given AL iterations between mhpc_initialize and the first mhpc_solve, that
+ *    solve starts with the real rollout for it; the handle then counts as one whose next solve
+ *    starts with a rollout, as after mhpc_update_problem, which is what mhpc_copy_problems
+ *    compares between two handles).
+ *    A tick that lists only budget-(1,1) problems issues a schedule of that length.
+ *  - Giving a problem a record is the reference's `_option = o` on that controller.  The fields a
+ *    solve does not rewrite (budgets, thresholds, gamma, update_relax, update_ReB,
+ *    update_regularization, AL_active; smooth_active is carried and reported) take effect at that
+ *    problem's next solve or tick; mhpc_rollout_costs and the policy rollouts read the current
+ *    AL_active.  ReB_active and update_penalty are rewritten inside a solve
+ *    (MultiPhaseDDP.cpp:178-183, 273-277): for a problem whose record changed in any field they
+ *    are overwritten with the new record's values.  A problem whose record did not change keeps
+ *    its whole device state bit for bit, and a call that changes no problem changes nothing.
+ *    mhpc_initialize and mhpc_reset_problems restore each problem's own record.
+ *  - Nothing becomes pending: the calls are allowed before and after mhpc_initialize and between
+ *    any two other calls.  Device work is proportional to the number of changed problems.
+ *  - A refused call changes nothing. */
+int mhpc_set_options(mhpc_handle* h, const mhpc_hsddp_option* opt);   /* every problem */
+int mhpc_get_options(mhpc_handle* h, mhpc_hsddp_option* opt);         /* problem 0's */
+int mhpc_set_option_sets(mhpc_handle* h, int n_sets, const mhpc_hsddp_option* sets,
+                         const int32_t* set_of_problem);
+int mhpc_get_problem_options(mhpc_handle* h, int problem, mhpc_hsddp_option* opt);
+/* Distinct option sets in use (1 for a fresh handle). */
+int mhpc_num_option_sets(mhpc_handle* h, int* n);
 
 /* Running-cost gradient lx of knots 0..N-2 ([batch][N-1][n]) and terminal-cost gradient Phix
  * ([batch][n]) of `phase` as the last partials evaluation left them: the reference's

@@ -222,11 +222,7 @@ class MHPCLocomotion {
     static_assert(sizeof(TH) == 8, "only the double instantiation exists (as in the reference)");
     const int np = params->n_wbphase + params->n_fbphase;
     desc_ = build_desc(params, gait);
-    opt_ = mhpc_hsddp_option{option.alpha, option.gamma, option.update_penalty,
-                             option.update_relax, option.update_regularization,
-                             option.update_ReB, option.max_DDP_iter, option.max_AL_iter,
-                             option.DDP_thresh, option.AL_thresh, option.AL_active,
-                             option.ReB_active, option.smooth_active, 0};
+    opt_ = option_to_c(option);
     check(mhpc_create(&desc_, &opt_, batch_, device, &h_), "mhpc_create");
     _option = option;
     _n_phases = np;
@@ -260,6 +256,20 @@ class MHPCLocomotion {
       d.N[p] = (int)std::round((double)tim[p] / (p < d.n_wb ? d.dt_wb : d.dt_fb));
     }
     return d;
+  }
+  static mhpc_hsddp_option option_to_c(const HSDDP_OPTION<TH>& o) {
+    return mhpc_hsddp_option{o.alpha, o.gamma, o.update_penalty, o.update_relax, o.update_regularization,
+                             o.update_ReB, o.max_DDP_iter, o.max_AL_iter, o.DDP_thresh, o.AL_thresh,
+                             o.AL_active, o.ReB_active, o.smooth_active, 0};
+  }
+  static HSDDP_OPTION<TH> option_from_c(const mhpc_hsddp_option& c) {
+    HSDDP_OPTION<TH> o;
+    o.alpha = c.alpha; o.gamma = c.gamma; o.update_penalty = c.update_penalty;
+    o.update_relax = c.update_relax; o.update_regularization = c.update_regularization;
+    o.update_ReB = c.update_ReB; o.max_DDP_iter = c.max_DDP_iter; o.max_AL_iter = c.max_AL_iter;
+    o.DDP_thresh = c.DDP_thresh; o.AL_thresh = c.AL_thresh; o.AL_active = c.AL_active != 0;
+    o.ReB_active = c.ReB_active != 0; o.smooth_active = c.smooth_active != 0;
+    return o;
   }
   MHPCLocomotion(const MHPCLocomotion&) = delete;
   MHPCLocomotion& operator=(const MHPCLocomotion&) = delete;
@@ -705,6 +715,40 @@ class MHPCLocomotion {
   int num_param_sets() {
     int n = 0;
     check(mhpc_num_param_sets(h_, &n), "mhpc_num_param_sets");
+    return n;
+  }
+
+  // extension: per-problem option sets -- every controller of the reference owns its
+  // MultiPhaseDDP::_option.  set_options: `_option = o` on every controller; set_option_sets:
+  // problem b gets options[set_of_problem[b]] (b % n for an empty vector), 1..MHPC_MAX_OPTION_SETS
+  // records that share the constructor's alpha.  Allowed at any point of the call order; the next
+  // solve or tick reads the new records, and its launch schedule runs to the largest budgets among
+  // the problems it covers (mhpc_set_option_sets).
+  void set_options(const HSDDP_OPTION<TH>& option) {
+    const mhpc_hsddp_option o = option_to_c(option);
+    check(mhpc_set_options(h_, &o), "mhpc_set_options");
+    _option = option;
+  }
+  HSDDP_OPTION<TH> get_options() { return get_problem_options(0); }
+  void set_option_sets(const std::vector<HSDDP_OPTION<TH>>& options,
+                       const std::vector<int32_t>& set_of_problem = {}) {
+    if (!set_of_problem.empty() && (int)set_of_problem.size() != batch_)
+      throw std::runtime_error("set_option_sets: one set index per problem expected");
+    std::vector<mhpc_hsddp_option> os;
+    for (const HSDDP_OPTION<TH>& o : options) os.push_back(option_to_c(o));
+    check(mhpc_set_option_sets(h_, (int)os.size(), os.data(),
+                               set_of_problem.empty() ? nullptr : set_of_problem.data()),
+          "mhpc_set_option_sets");
+    _option = get_options();
+  }
+  HSDDP_OPTION<TH> get_problem_options(int b) {
+    mhpc_hsddp_option o;
+    check(mhpc_get_problem_options(h_, b, &o), "mhpc_get_problem_options");
+    return option_from_c(o);
+  }
+  int num_option_sets() {
+    int n = 0;
+    check(mhpc_num_option_sets(h_, &n), "mhpc_num_option_sets");
     return n;
   }
 

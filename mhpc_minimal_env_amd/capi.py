@@ -17,6 +17,7 @@ MHPC_MAX_PHASES = 16
 MHPC_MAX_KNOTS = 1024
 MHPC_MAX_LAYOUTS = 32
 MHPC_MAX_PARAM_SETS = 32
+MHPC_MAX_OPTION_SETS = 32
 MHPC_TRACE_LEN = 64
 MHPC_NUM_KERNELS = 7
 MHPC_MAX_ROLLOUT_EPS = 4096
@@ -258,6 +259,13 @@ SIGNATURES = [
                                                ctypes.POINTER(CostWeights),
                                                ctypes.POINTER(ConstraintParams)]),
     ("mhpc_num_param_sets", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
+    ("mhpc_set_options", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HsddpOption)]),
+    ("mhpc_get_options", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HsddpOption)]),
+    ("mhpc_set_option_sets", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.POINTER(HsddpOption), _IP]),
+    ("mhpc_get_problem_options", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int,
+                                                ctypes.POINTER(HsddpOption)]),
+    ("mhpc_num_option_sets", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     ("mhpc_eval_wb_dynamics", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _DP, _DP,
                                              _DP, _DP]),
     ("mhpc_eval_wb_dynamics_pair", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _DP,

@@ -61,5 +61,10 @@ int api_set_param_sets(Handle* h, int n_sets, const mhpc_cost_weights* w,
                        const mhpc_constraint_params* c, const int32_t* set_of);
 int api_get_problem_params(Handle* h, int b, mhpc_cost_weights* w, mhpc_constraint_params* c);
 int api_num_param_sets(Handle* h, int* n);
+int api_set_options(Handle* h, const mhpc_hsddp_option* o);
+int api_get_options(Handle* h, mhpc_hsddp_option* o);
+int api_set_option_sets(Handle* h, int n_sets, const mhpc_hsddp_option* sets, const int32_t* set_of);
+int api_get_problem_options(Handle* h, int b, mhpc_hsddp_option* o);
+int api_num_option_sets(Handle* h, int* n);
 void api_destroy(Handle* h);
 }  // namespace API_NS

@@ -384,6 +384,7 @@ struct RowCtx {
   // the problem's user command, loaded once per launch where the row picks up its problem's
   // state; every phase folds it into its lanes' fixed reference (rxc) at phase start
   Cmd cm;
+  int al_on;   // the problem's AL_active
 };
 
 __device__ __forceinline__ bool go(const RowCtx& r) { return r.live && !r.failed; }
@@ -1257,7 +1258,7 @@ __device__ void terminal_value(const SolveParams& sp, const DevBufs& d, const La
   const breal pos = d.refpos[(size_t)rc.b * sp.NK + ko + N - 1];
   const breal cvel = rc.cm.vel, chgt = rc.cm.height;  // (the sweep's arithmetic type)
   const real* xe = traj_ptr(sp, d, rc.b, rc.nom, ko + N - 1);
-  const bool al = wb && ntc_of(mode, true) && sp.AL_active && st->al_partials;
+  const bool al = wb && ntc_of(mode, true) && rc.al_on && st->al_partials;
   if (al && rc.lt == 0) {
     real hx[14], Hs[3][3], h;  // (the model's type)
     if (mode == 2) wb_touchdown_compact<kFront>(xe, &h, hx, Hs);
@@ -1450,7 +1451,7 @@ __device__ void zero_value(RowLds& rl, RowCtx& rc) {
 // the same attempts with the same regularisation, bit for bit.
 template <int RPW, int PART, int RPP>
 __global__ __launch_bounds__(64, PART == 1 ? MHPC_BWS_SRB_WAVES : 1) void k_bws(SolveParams sp, DevBufs d,
-                                                                    real update_reg) {
+                                                                    int al_iter, int ddp_iter) {
   static_assert(RPP == 1 || (RPP == 2 && RPW == 2 && PART != 1), "row layout");
   __shared__ BwsLds sh;
   BWS_T(tk0);
@@ -1469,7 +1470,10 @@ __global__ __launch_bounds__(64, PART == 1 ? MHPC_BWS_SRB_WAVES : 1) void k_bws(
   const bool inb = q < RPW && gb.p0 + q < gb.p1;
   rc.b = prob_at(sp, d, inb ? gb.p0 + q : gb.p0);  // a spare row shadows the block's first problem
   ProbState* st = &d.st[rc.b];
-  rc.act = inb && st->active && st->ddp_active;
+  // (the row's own problem: its iteration caps, and below its regularisation factor -- rows of
+  // one wave may hold problems of different option sets)
+  rc.al_on = al_active_of(sp, d, rc.b);
+  rc.act = inb && st->active && st->ddp_active && in_op(sp, d, rc.b, al_iter, ddp_iter);
   if (!__builtin_amdgcn_ballot_w64(rc.act)) return;
   RowLds& rl = sh.r[q];
   rc.nom = st->nom_slot;
@@ -1498,6 +1502,7 @@ __global__ __launch_bounds__(64, PART == 1 ? MHPC_BWS_SRB_WAVES : 1) void k_bws(
       }
       pending = rc.live && rc.failed;
       if (pending) {  // the next attempt, as PART 0 would start it
+        const real update_reg = opt_of(d, rc.b).update_regularization;
         rc.reg = fmax(rc.reg * update_reg, breal(1e-03));
         ++bws_iter;
         if (rc.reg > 1000) {
@@ -1542,6 +1547,7 @@ __global__ __launch_bounds__(64, PART == 1 ? MHPC_BWS_SRB_WAVES : 1) void k_bws(
     }
     pending = rc.live && rc.failed && !aborted;
     if (pending) {
+      const real update_reg = opt_of(d, rc.b).update_regularization;
       rc.reg = fmax(rc.reg * update_reg, breal(1e-03));  // MultiPhaseDDP.cpp:218
       ++bws_iter;
       if (rc.reg > 1000) {
@@ -1597,7 +1603,7 @@ int bws_auto_variant(int B) {
   return B <= MHPC_BWS_PAIRS_MAX_B ? MHPC_VARIANT_BWS_PAIRS2 : MHPC_VARIANT_BWS_ROWS4;
 }
 
-hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, real update_reg, int part,
+hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter, int part,
                       hipStream_t s) {
   const int v = sp.var_bws ? sp.var_bws : bws_auto_variant(launch_problems(sp));
   const int rpw = v == MHPC_VARIANT_BWS_ROWS1 ? 1 : (v == MHPC_VARIANT_BWS_ROWS2 ||
@@ -1606,15 +1612,15 @@ hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, real update_reg, 
   const dim3 grid4(bws_grid(sp, 4));
 #define MHPC_LAUNCH_BWS(R)                                                                    \
   do {                                                                                        \
-    if (part == 1) hipLaunchKernelGGL((k_bws<R, 1, 1>), grid, dim3(64), 0, s, sp, d, update_reg); \
-    else if (part == 2) hipLaunchKernelGGL((k_bws<R, 2, 1>), grid, dim3(64), 0, s, sp, d, update_reg); \
-    else hipLaunchKernelGGL((k_bws<R, 0, 1>), grid, dim3(64), 0, s, sp, d, update_reg);           \
+    if (part == 1) hipLaunchKernelGGL((k_bws<R, 1, 1>), grid, dim3(64), 0, s, sp, d, al_iter, ddp_iter); \
+    else if (part == 2) hipLaunchKernelGGL((k_bws<R, 2, 1>), grid, dim3(64), 0, s, sp, d, al_iter, ddp_iter); \
+    else hipLaunchKernelGGL((k_bws<R, 0, 1>), grid, dim3(64), 0, s, sp, d, al_iter, ddp_iter);           \
   } while (0)
   if (v == MHPC_VARIANT_BWS_PAIRS2) {
     // the SRB half keeps one row per problem (its knot is short; four problems per wave)
-    if (part == 1) hipLaunchKernelGGL((k_bws<4, 1, 1>), grid4, dim3(64), 0, s, sp, d, update_reg);
-    else if (part == 2) hipLaunchKernelGGL((k_bws<2, 2, 2>), grid, dim3(64), 0, s, sp, d, update_reg);
-    else hipLaunchKernelGGL((k_bws<2, 0, 2>), grid, dim3(64), 0, s, sp, d, update_reg);
+    if (part == 1) hipLaunchKernelGGL((k_bws<4, 1, 1>), grid4, dim3(64), 0, s, sp, d, al_iter, ddp_iter);
+    else if (part == 2) hipLaunchKernelGGL((k_bws<2, 2, 2>), grid, dim3(64), 0, s, sp, d, al_iter, ddp_iter);
+    else hipLaunchKernelGGL((k_bws<2, 0, 2>), grid, dim3(64), 0, s, sp, d, al_iter, ddp_iter);
   } else if (rpw == 1) MHPC_LAUNCH_BWS(1);
   else if (rpw == 2) MHPC_LAUNCH_BWS(2);
   else MHPC_LAUNCH_BWS(4);

@@ -306,6 +306,16 @@ extern "C" int mhpc_get_problem_params(mhpc_handle* h, int problem, mhpc_cost_we
   FWD(get_problem_params, problem, w, c);
 }
 extern "C" int mhpc_num_param_sets(mhpc_handle* h, int* n) { FWD(num_param_sets, n); }
+extern "C" int mhpc_set_options(mhpc_handle* h, const mhpc_hsddp_option* o) { FWD(set_options, o); }
+extern "C" int mhpc_get_options(mhpc_handle* h, mhpc_hsddp_option* o) { FWD(get_options, o); }
+extern "C" int mhpc_set_option_sets(mhpc_handle* h, int n_sets, const mhpc_hsddp_option* sets,
+                                    const int32_t* set_of_problem) {
+  FWD(set_option_sets, n_sets, sets, set_of_problem);
+}
+extern "C" int mhpc_get_problem_options(mhpc_handle* h, int problem, mhpc_hsddp_option* o) {
+  FWD(get_problem_options, problem, o);
+}
+extern "C" int mhpc_num_option_sets(mhpc_handle* h, int* n) { FWD(num_option_sets, n); }
 extern "C" void mhpc_destroy(mhpc_handle* h) {
   if (!h) return;
   try {

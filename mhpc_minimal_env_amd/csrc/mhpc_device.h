@@ -114,6 +114,30 @@ static __device__ __forceinline__ const CostParams& params_of(const DevBufs& d, 
 // cost code and the sweep fold it into their per-lane references, never a load per knot).
 static __device__ __forceinline__ Cmd cmd_of(const DevBufs& d, int b) { return d.cmd[b]; }
 
+// Option record of problem b: read where the per-problem control flow needs a field (per lane:
+// the problems of a wave may differ), never inside a knot loop.  The only index that depends on
+// it is this table lookup (oid[b] < MAXO by the host's construction).
+static __device__ __forceinline__ const OptRec& opt_of(const DevBufs& d, int b) {
+  return d.opt[d.oid[b]];
+}
+// Problem b takes part in op (al, ddp) of a solve schedule: the schedule of a scope runs to the
+// largest caps among its problems, and a problem with smaller ones sits the rest out exactly as in
+// a handle of its own, where those ops are never issued.
+static __device__ __forceinline__ bool in_op(const OptRec& o, int al, int ddp) {
+  return al <= o.n_al && ddp <= o.max_ddp;
+}
+// The same for problem b of a launch of the solve schedule: an op within the scope's smallest caps
+// (uniform, from the parameter block) takes everybody and reads nothing.
+static __device__ __forceinline__ bool in_op(const SolveParams& sp, const DevBufs& d, int b, int al,
+                                             int ddp) {
+  if (al <= sp.min_n_al && ddp <= sp.min_max_ddp) return true;
+  return in_op(opt_of(d, b), al, ddp);
+}
+// AL_active of problem b in such a launch: the scope's common value, or the record's.
+static __device__ __forceinline__ bool al_active_of(const SolveParams& sp, const DevBufs& d, int b) {
+  return sp.al_uniform >= 0 ? sp.al_uniform != 0 : opt_of(d, b).AL_active != 0;
+}
+
 // Natural log of a positive argument (the barrier's g > delta > 0 and delta itself).  fp64:
 // the fdlibm algorithm (e_log.c: x = 2^k (1 + f) with sqrt(2)/2 <= 1 + f < sqrt(2),
 // s = f / (2 + f), a degree-14 odd polynomial in s), < 1 ulp on every positive finite argument,

@@ -199,7 +199,7 @@ __device__ unsigned long long g_ro_cyc[11];
 template <bool PIPE, bool ST, bool PAIR>
 __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, DevBufs d,
                                                              int al_iter, int ddp_iter,
-                                                             int max_ddp, int full) {
+                                                             int full) {
   MHPC_NO_FMA_F32
   const int nc = full ? 1 : sp.n_cand;
   // (a staged re-roll, mode 2: one lane per problem and the stage's ST_PPW problems a block)
@@ -219,6 +219,10 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
   const bool in = lp < ppw && gb.p0 + lp < gb.p1;
   const int b = in ? prob_at(sp, d, gb.p0 + lp) : 0;
   const Cmd cm = cmd_of(d, b);  // the problem's user command (cost side)
+  // its option record's slot and AL_active, picked up beside the state words: read where they are
+  // used they would put a load (or two) behind every phase end of the cost wave
+  const int oslot = d.oid[b];
+  const bool al_on = al_active_of(sp, d, b);
 
   // ring of RD knot records; the waves meet at a barrier every RD / 2 records
   constexpr int RD = PIPE ? (PAIR ? RO_RING_PAIR : 2) : 1;
@@ -252,7 +256,8 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
       nom = st->reroll_nom;
       slot = st->nom_slot;
     } else {
-      run = st->active && (full || st->ddp_active);
+      // (the problem's own iteration caps: it sits out the ops a handle of its own never issues)
+      run = st->active && (full || st->ddp_active) && in_op(sp, d, b, al_iter, ddp_iter);
       nom = st->nom_slot;
       slot = j < nom ? j : j + 1;
     }
@@ -528,7 +533,7 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
       return;
     }
     real h = 0;
-    if (wb) V += wb_terminal_cost(cw, cm, mode, c.refT, xe, sp.AL_active, st, p, &h);
+    if (wb) V += wb_terminal_cost(cw, cm, mode, c.refT, xe, al_on, st, p, &h);
     else V += fb_terminal_cost(cw, cm, mode, c.refT, xe);
     J += V;
     viol2 += acc(h) * h;
@@ -728,7 +733,7 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
       for (int p = 0; p < L.P; ++p) { st->V[p] = sV[p][lane]; st->h[p] = sH[p][lane]; }
       st->nom_slot = slot;
       st->par_slot = slot;
-      st->par_al = sp.AL_active ? 1 : 0;
+      st->par_al = al_on ? 1 : 0;
       st->ls_nt = 0;
       for (int p = 0; p < L.P; ++p) { st->par_sigma[p] = st->sigma[p]; st->par_lambda[p] = st->lambda[p]; }
       st->al_iter = al_iter;
@@ -742,10 +747,12 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
   }
   if (w1 && run && j == 0) {
     const acc cost_prev = st->J;
+    const OptRec& o = d.opt[oslot];  // the problem's own gamma, threshold and DDP cap (per lane)
+    const real gamma = o.gamma;
     int sel = nc - 1, nls = nc + 1;
     for (int c = 0; c < nc; ++c) {
       const real e = sp.eps[c];
-      const acc rhs = cost_prev + sp.gamma * e * (1 - e / 2) * st->dV_exp;
+      const acc rhs = cost_prev + gamma * e * (1 - e / 2) * st->dV_exp;
       if (sJ[lane + c] <= rhs) { sel = c; nls = c + 1; break; }
     }
     const int sl = lane + sel;
@@ -756,7 +763,7 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
     st->viol = sViol[sl];
     for (int p = 0; p < L.P; ++p) { st->V[p] = sV[p][sl]; st->h[p] = sH[p][sl]; }
     st->nom_slot = sel < nom ? sel : sel + 1;
-    const bool conv = cost_prev - st->J < sp.DDP_thresh;
+    const bool conv = cost_prev - st->J < o.DDP_thresh;
     if (st->ntrace < TRACE)
       st->trace[st->ntrace++] = (al_iter << 24) | (st->reb_active << 23) | ((conv ? 1 : 0) << 22) |
                                 ((nls & 0xff) << 8) | (st->bws_iter & 0xff);
@@ -774,7 +781,7 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) void k_rollout(SolveParams sp, Dev
       st->par_slot = st->nom_slot;  // forward_sweep_partials_only (no AL terms, B1)
       st->par_al = 0;
       st->ls_nt = 0;
-      if (ddp_iter < max_ddp) st->cnt[C_PAR_RUN]++;
+      if (ddp_iter < o.max_ddp) st->cnt[C_PAR_RUN]++;
       else st->ddp_active = 0;
     }
   }
@@ -810,6 +817,7 @@ static __device__ __forceinline__ RolloutCost serial_rollout(const SolveParams& 
   const Cmd cm = cmd_of(d, b);
   const int nom = st->nom_slot;
   const bool reb = st->reb_active != 0;
+  const bool al_on = opt_of(d, b).AL_active != 0;  // the problem's current AL_active
   acc J = 0, viol2 = 0;
   for (int p = 0; p < Pn; ++p) {
     const int mode = L.mode[p], N = L.N[p], ko = L.ko[p];
@@ -844,7 +852,7 @@ static __device__ __forceinline__ RolloutCost serial_rollout(const SolveParams& 
         real* r = rec + (size_t)(N - 1) * PREC_W * rs;
         for (int i = 0; i < 14; ++i) r[i * rs] = x[i];
       }
-      V += wb_terminal_cost(cw, cm, mode, refpos[N - 1], x, sp.AL_active, st, p, &h);
+      V += wb_terminal_cost(cw, cm, mode, refpos[N - 1], x, al_on, st, p, &h);
       // wb_phase_transition, spelled out: xe is the state between its two halves, and with the
       // helper inlined here as well both rollout kernels measured 1-3 % slower
       // (profiles/forward_refactor_ab.md)
@@ -1019,7 +1027,7 @@ __global__ void k_cost_grad(SolveParams sp, DevBufs d, int g, int p, int b0, int
         v[i] = cw.wQf[mode - 1][i] * (x[i] - rx[i]);
         if (al) v[i] += 50 * (s * s / 2 * hx[i] * h + lam * hx[i]);
       }
-      if (ntc_of(mode, true) && sp.AL_active) {  // trials of the last line search
+      if (ntc_of(mode, true) && opt_of(d, b).AL_active) {  // trials of the last line search
         const real s2 = st->ls_sigma[p], lam2 = st->ls_lambda[p];
         for (int j = 0; j < st->ls_nt; ++j) {
           const int slot = j < st->ls_nom ? j : j + 1;
@@ -1183,7 +1191,8 @@ __device__ __forceinline__ void partials_knot(const real* nk, real* rec, int NK)
 #define MHPC_PAR_BLOCK 128
 #endif
 template <int G>
-__global__ __launch_bounds__(MHPC_PAR_BLOCK, MHPC_PAR_MINB) void k_partials(SolveParams sp, DevBufs d) {
+__global__ __launch_bounds__(MHPC_PAR_BLOCK, MHPC_PAR_MINB) void k_partials(SolveParams sp, DevBufs d,
+                                                                              int al_iter, int ddp_iter) {
   // blocks by group, lanes = (problem of the group, WB knot)
   long t0 = 0;
   const int g = block_group_items(sp, sp.gpk, 0, blockIdx.x, MHPC_PAR_BLOCK, &t0);
@@ -1196,7 +1205,7 @@ __global__ __launch_bounds__(MHPC_PAR_BLOCK, MHPC_PAR_MINB) void k_partials(Solv
   const int it = (int)(t - (long)i0 * L.par_knots);
   const int b = prob_at(sp, d, sp.go[g] + i0);
   const ProbState* st = &d.st[b];
-  if (!(st->active && st->ddp_active)) return;
+  if (!(st->active && st->ddp_active && in_op(sp, d, b, al_iter, ddp_iter))) return;
   int p = 0;
   while (it >= L.par_knot_off[p + 1]) ++p;
   const int k = it - L.par_knot_off[p];
@@ -1217,7 +1226,8 @@ __global__ __launch_bounds__(MHPC_PAR_BLOCK, MHPC_PAR_MINB) void k_partials(Solv
   }
 }
 
-__global__ __launch_bounds__(256) void k_partials_impact(SolveParams sp, DevBufs d) {
+__global__ __launch_bounds__(256) void k_partials_impact(SolveParams sp, DevBufs d, int al_iter,
+                                                         int ddp_iter) {
   long t0 = 0;
   const int g = block_group_items(sp, sp.gpi, 0, blockIdx.x, 256, &t0);
   if (g < 0) return;
@@ -1228,7 +1238,7 @@ __global__ __launch_bounds__(256) void k_partials_impact(SolveParams sp, DevBufs
   const int it = (int)(t - (long)i0 * L.par_imp);
   const int b = prob_at(sp, d, sp.go[g] + i0);
   const ProbState* st = &d.st[b];
-  if (!(st->active && st->ddp_active)) return;
+  if (!(st->active && st->ddp_active && in_op(sp, d, b, al_iter, ddp_iter))) return;
   int p = 0;
   while (it >= L.par_imp_off[p + 1]) ++p;
   const int dir = it - L.par_imp_off[p];
@@ -1246,14 +1256,18 @@ __global__ __launch_bounds__(256) void k_partials_impact(SolveParams sp, DevBufs
 // ============================================================================================
 // AL / ReB update (MultiPhaseDDP.cpp:273-284, SinglePhase.cpp:334-354)
 // ============================================================================================
-__global__ void k_al_end(SolveParams sp, DevBufs d, int last) {
+// al: the AL iteration this update closes (1 for the lone update of a schedule with no AL
+// iteration, which a problem whose own cap is 0 takes there as well); a problem past its own cap
+// keeps its state.  last: the scope's final op, where every problem's cost is checked.
+__global__ void k_al_end(SolveParams sp, DevBufs d, int al, int last) {
   const GrpBlk gb = block_group(sp, blockIdx.x, 64);
   if (gb.g < 0 || gb.p0 + (int)threadIdx.x >= gb.p1) return;
   const Layout& L = layout_of(d, gb.g);
   const CostParams& cw = params_of(d, gb.g);
   const int b = prob_at(sp, d, gb.p0 + threadIdx.x);
   ProbState* st = &d.st[b];
-  if (st->active) {
+  const OptRec& o = opt_of(d, b);
+  if (st->active && (o.n_al == 0 ? al == 1 : al <= o.n_al)) {
     real up = st->cap_pen;  // _option.update_penalty = captured value, 0 if satisfied
     if (st->viol < real(0.03)) up = 0;
     st->opt_pen = up;
@@ -1262,14 +1276,14 @@ __global__ void k_al_end(SolveParams sp, DevBufs d, int last) {
       if (ntc_of(L.mode[p], wb)) st->lambda[p] += st->sigma[p] * st->h[p];
       st->sigma[p] *= up;
       if (st->reb_active && wb) {
-        st->delta[p] *= sp.update_relax;
+        st->delta[p] *= o.update_relax;
         const real dmin = cw.delta_min[L.mode[p] - 1];
         if (st->delta[p] < dmin) st->delta[p] = dmin;
-        st->eps_tq[p] *= sp.update_ReB;
-        st->eps_grf[p] *= sp.update_ReB;
+        st->eps_tq[p] *= o.update_ReB;
+        st->eps_grf[p] *= o.update_ReB;
       }
     }
-    if (st->viol < sp.AL_thresh) st->active = 0;
+    if (st->viol < o.AL_thresh) st->active = 0;
   }
   if (last && st->status == MHPC_SOLVE_OK && !isfinite(st->J)) st->status = MHPC_SOLVE_NONFINITE;
 }
@@ -1416,13 +1430,37 @@ __global__ __launch_bounds__(256) void k_reset_list(SolveParams sp, DevBufs d, c
 // warm-start rollout below differently, three of its multiply-adds no longer contract, and
 // every fp32 result changes in the last bits (k_init has no MHPC_NO_FMA_F32: its rounding is
 // part of the fp32 results as they stand).
-__global__ __launch_bounds__(64) void k_init_params(SolveParams sp, DevBufs d) {
+// The same holds for the option fields k_init_state writes (the ReB flag; warm: the fields a
+// solve rewrites): k_init writes problem 0's record for all, from SolveParams::ReB_active /
+// update_penalty, and with more than one option set (mhpc_set_option_sets) this kernel then
+// writes each problem's own.  warm: as k_init's.
+// A problem whose record has no AL iteration (n_al = 0) never runs forward_sweep(0): in the
+// reference its SRB phases keep the zero states memory_reset left, since only that first sweep
+// rolls them out.  k_init completed them ahead of that sweep (see there), so with warm the states
+// of its SRB knots in slot 0 go back to zero here (their u and y are zero already); the host
+// makes the problem's first forward_sweep(0) the real rollout should its budget be raised before
+// its next solve (Handle::srb_open).
+__global__ __launch_bounds__(64) void k_init_params(SolveParams sp, DevBufs d, int warm) {
   const GrpBlk gb = block_group(sp, blockIdx.x, 64);
   if (gb.g < 0 || gb.p0 + (int)threadIdx.x >= gb.p1) return;
   const Layout& L = layout_of(d, gb.g);
   const CostParams& cw = params_of(d, gb.g);
-  ProbState* st = &d.st[prob_at(sp, d, gb.p0 + threadIdx.x)];
+  const int b = prob_at(sp, d, gb.p0 + threadIdx.x);
+  ProbState* st = &d.st[b];
   for (int p = 0; p < MAXP; ++p) init_al_reb(st, L, cw, p);
+  const OptRec& o = opt_of(d, b);
+  st->reb_active = o.ReB_active ? 1 : 0;
+  if (!warm) return;
+  st->opt_reb = o.ReB_active ? 1 : 0;
+  st->opt_pen = o.update_penalty;
+  st->cap_reb = st->opt_reb;
+  st->cap_pen = st->opt_pen;
+  if (o.n_al == 0)
+    for (int p = L.n_wb; p < L.P; ++p)
+      for (int k = 0; k < L.N[p]; ++k) {
+        real* r = traj_ptr(sp, d, b, 0, L.ko[p] + k);
+        for (int i = 0; i < 6; ++i) r[i] = real(0.0);
+      }
 }
 
 __global__ __launch_bounds__(64) void k_init(SolveParams sp, DevBufs d, int warm) {
@@ -1555,7 +1593,8 @@ __global__ __launch_bounds__(64) void k_cost(SolveParams sp, DevBufs d, int al_i
   const CostParams& cw = params_of(d, gb.g);
   const int b = prob_at(sp, d, gb.p0);
   ProbState* st = &d.st[b];
-  if (!st->active) return;
+  const bool al_on = al_active_of(sp, d, b);
+  if (!st->active || !in_op(sp, d, b, al_iter, 0)) return;
   const Cmd cm = cmd_of(d, b);
   const int lane = threadIdx.x;
   __shared__ real sc[MHPC_MAX_KNOTS];
@@ -1591,7 +1630,7 @@ __global__ __launch_bounds__(64) void k_cost(SolveParams sp, DevBufs d, int al_i
     for (int k = 0; k < N - 1; ++k) V += sc[ko + k];
     const real* x = traj_ptr(sp, d, b, nom, ko + N - 1);
     const real refT = refpos[ko + N - 1];
-    if (p < L.n_wb) V += wb_terminal_cost(cw, cm, mode, refT, x, sp.AL_active, st, p, &h);
+    if (p < L.n_wb) V += wb_terminal_cost(cw, cm, mode, refT, x, al_on, st, p, &h);
     else V += fb_terminal_cost(cw, cm, mode, refT, x);
     sV[p] = V;
     sH[p] = h;
@@ -1611,7 +1650,7 @@ __global__ __launch_bounds__(64) void k_cost(SolveParams sp, DevBufs d, int al_i
     st->J = J;
     st->viol = sqrt(viol2);
     st->par_slot = nom;  // forward_sweep(0) evaluated the partials (with AL, B1) here
-    st->par_al = sp.AL_active ? 1 : 0;
+    st->par_al = al_on ? 1 : 0;
     st->ls_nt = 0;
     for (int p = 0; p < L.P; ++p) { st->par_sigma[p] = st->sigma[p]; st->par_lambda[p] = st->lambda[p]; }
     st->al_iter = al_iter;
@@ -1872,8 +1911,8 @@ hipError_t launch_reset_list(const SolveParams& sp, const DevBufs& d, int n, con
                      nbk, spmax);
   return hipGetLastError();
 }
-hipError_t launch_init_params(const SolveParams& sp, const DevBufs& d, hipStream_t s) {
-  hipLaunchKernelGGL(k_init_params, dim3(grid_of(sp, 64)), dim3(64), 0, s, sp, d);
+hipError_t launch_init_params(const SolveParams& sp, const DevBufs& d, int warm, hipStream_t s) {
+  hipLaunchKernelGGL(k_init_params, dim3(grid_of(sp, 64)), dim3(64), 0, s, sp, d, warm);
   return hipGetLastError();
 }
 hipError_t launch_init(const SolveParams& sp, const DevBufs& d, hipStream_t s) {
@@ -1928,10 +1967,10 @@ int ro_store_auto(const SolveParams& sp) {
 }
 
 hipError_t launch_rollout(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter,
-                          int max_ddp, int full, hipStream_t s) {
+                          int full, hipStream_t s) {
   if (full) {
     hipLaunchKernelGGL((k_rollout<false, false, false>), dim3(grid_of(sp, 64)), dim3(64), 0, s,
-                       sp, d, al_iter, 0, 0, 1);
+                       sp, d, al_iter, 0, 1);
     return hipGetLastError();
   }
   const RoShape r = ro_shape(sp);
@@ -1939,19 +1978,19 @@ hipError_t launch_rollout(const SolveParams& sp, const DevBufs& d, int al_iter, 
   const int nblk = r.nblk, nblk2 = r.nblk2;
   if (pair)
     hipLaunchKernelGGL((k_rollout<true, true, true>), dim3(nblk2), dim3(128), 0, s, sp, d, al_iter,
-                       ddp_iter, max_ddp, 0);
+                       ddp_iter, 0);
   else if (pipe && st)
     hipLaunchKernelGGL((k_rollout<true, true, false>), dim3(nblk), dim3(128), 0, s, sp, d, al_iter,
-                       ddp_iter, max_ddp, 0);
+                       ddp_iter, 0);
   else if (pipe)
     hipLaunchKernelGGL((k_rollout<true, false, false>), dim3(nblk), dim3(128), 0, s, sp, d,
-                       al_iter, ddp_iter, max_ddp, 0);
+                       al_iter, ddp_iter, 0);
   else if (st)
     hipLaunchKernelGGL((k_rollout<false, true, false>), dim3(nblk), dim3(64), 0, s, sp, d,
-                       al_iter, ddp_iter, max_ddp, 0);
+                       al_iter, ddp_iter, 0);
   else
     hipLaunchKernelGGL((k_rollout<false, false, false>), dim3(nblk), dim3(64), 0, s, sp, d,
-                       al_iter, ddp_iter, max_ddp, 0);
+                       al_iter, ddp_iter, 0);
   // the accepted trials whose records were not stored (RO_STORE_FIRST), rolled out again:
   // lane = problem, ST_PPW problems a block so that their operands go through the LDS stage
   // (a global round trip per knot otherwise: ~2x the latency); a block without one returns
@@ -1959,10 +1998,10 @@ hipError_t launch_rollout(const SolveParams& sp, const DevBufs& d, int al_iter, 
   if (sp.ro_store < sp.n_cand - 1) {
     if (fits)
       hipLaunchKernelGGL((k_rollout<false, true, false>), dim3(grid_of(sp, ST_PPW)), dim3(64),
-                         0, s, sp, d, al_iter, 0, 0, 2);
+                         0, s, sp, d, al_iter, 0, 2);
     else
       hipLaunchKernelGGL((k_rollout<false, false, false>), dim3(grid_of(sp, 64)), dim3(64), 0, s,
-                         sp, d, al_iter, 0, 0, 2);
+                         sp, d, al_iter, 0, 2);
   }
   return hipGetLastError();
 }
@@ -1998,8 +2037,8 @@ hipError_t launch_cost_grad(const SolveParams& sp, const DevBufs& d, int g, int 
 // of the records) the velocity / control group (G = 1, 252 VGPRs, two waves per SIMD) runs on
 // s3 too, beside the configuration group (340 VGPRs, one wave per SIMD), and the impact
 // Jacobians follow it; s joins s3 before returning.
-hipError_t launch_partials(const SolveParams& sp, const DevBufs& d, hipStream_t s, hipStream_t s3,
-                           hipEvent_t fork, hipEvent_t join) {
+hipError_t launch_partials(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter,
+                           hipStream_t s, hipStream_t s3, hipEvent_t fork, hipEvent_t join) {
   const unsigned tk = grid_items(sp, sp.gpk, 0, MHPC_PAR_BLOCK), ti = grid_items(sp, sp.gpi, 0, 256);
   const bool two = s3 && fork && join && kParGroups <= 2 && tk > 0;
   if (two) {
@@ -2010,16 +2049,16 @@ hipError_t launch_partials(const SolveParams& sp, const DevBufs& d, hipStream_t 
   if (tk > 0) {
     constexpr int nt = MHPC_PAR_BLOCK;
     const dim3 grid(tk);
-    if constexpr (kParGroups > 1) hipLaunchKernelGGL(k_partials<1>, grid, dim3(nt), 0, two ? s3 : s, sp, d);
-    hipLaunchKernelGGL(k_partials<0>, grid, dim3(nt), 0, s, sp, d);
+    if constexpr (kParGroups > 1) hipLaunchKernelGGL(k_partials<1>, grid, dim3(nt), 0, two ? s3 : s, sp, d, al_iter, ddp_iter);
+    hipLaunchKernelGGL(k_partials<0>, grid, dim3(nt), 0, s, sp, d, al_iter, ddp_iter);
     if constexpr (kParGroups == 4) {
-      hipLaunchKernelGGL(k_partials<2>, grid, dim3(nt), 0, s, sp, d);
-      hipLaunchKernelGGL(k_partials<3>, grid, dim3(nt), 0, s, sp, d);
+      hipLaunchKernelGGL(k_partials<2>, grid, dim3(nt), 0, s, sp, d, al_iter, ddp_iter);
+      hipLaunchKernelGGL(k_partials<3>, grid, dim3(nt), 0, s, sp, d, al_iter, ddp_iter);
     }
   }
   if (ti > 0)
     hipLaunchKernelGGL(k_partials_impact, dim3(ti), dim3(256), 0, two ? s3 : s,
-                       sp, d);
+                       sp, d, al_iter, ddp_iter);
   if (two) {
     hipError_t e = hipEventRecord(join, s3);
     if (e == hipSuccess) e = hipStreamWaitEvent(s, join, 0);
@@ -2027,8 +2066,8 @@ hipError_t launch_partials(const SolveParams& sp, const DevBufs& d, hipStream_t 
   }
   return hipGetLastError();
 }
-hipError_t launch_al_end(const SolveParams& sp, const DevBufs& d, int last, hipStream_t s) {
-  hipLaunchKernelGGL(k_al_end, dim3(grid_of(sp, 64)), dim3(64), 0, s, sp, d, last);
+hipError_t launch_al_end(const SolveParams& sp, const DevBufs& d, int al, int last, hipStream_t s) {
+  hipLaunchKernelGGL(k_al_end, dim3(grid_of(sp, 64)), dim3(64), 0, s, sp, d, al, last);
   return hipGetLastError();
 }
 hipError_t launch_export(const SolveParams& sp, const DevBufs& d, hipStream_t s) {

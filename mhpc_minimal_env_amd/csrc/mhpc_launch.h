@@ -11,7 +11,7 @@ namespace MHPC_NS {
 
 // ---- mhpc_kernels.hip -----------------------------------------------------------------------
 hipError_t launch_init(const SolveParams& sp, const DevBufs& d, hipStream_t s);
-hipError_t launch_init_params(const SolveParams& sp, const DevBufs& d, hipStream_t s);
+hipError_t launch_init_params(const SolveParams& sp, const DevBufs& d, int warm, hipStream_t s);
 hipError_t launch_reset(const SolveParams& sp, const DevBufs& d, hipStream_t s);
 hipError_t launch_reset_arrays(const SolveParams& sp, const DevBufs& d, hipStream_t s);
 // list-driven device code of mhpc_reset_problems: x0 rows [n][14] to the listed problems, and
@@ -22,10 +22,12 @@ hipError_t launch_reset_list(const SolveParams& sp, const DevBufs& d, int n, con
                              real* store, int nbk, int spmax, hipStream_t s);
 hipError_t launch_cost(const SolveParams& sp, const DevBufs& d, int al_iter, hipStream_t s);
 hipError_t launch_rollout(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter,
-                          int max_ddp, int full, hipStream_t s);
-hipError_t launch_partials(const SolveParams& sp, const DevBufs& d, hipStream_t s, hipStream_t s3,
-                           hipEvent_t fork, hipEvent_t join);
-hipError_t launch_al_end(const SolveParams& sp, const DevBufs& d, int last, hipStream_t s);
+                          int full, hipStream_t s);
+// (al_iter, ddp_iter: the op of the solve schedule a launch belongs to -- every kernel of the
+// schedule leaves out the problems whose own iteration caps exclude that op, in_op, mhpc_device.h)
+hipError_t launch_partials(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter,
+                           hipStream_t s, hipStream_t s3, hipEvent_t fork, hipEvent_t join);
+hipError_t launch_al_end(const SolveParams& sp, const DevBufs& d, int al, int last, hipStream_t s);
 hipError_t launch_export(const SolveParams& sp, const DevBufs& d, hipStream_t s);
 hipError_t launch_export_ref(const SolveParams& sp, const DevBufs& d, int b0, int nb, hipStream_t s);
 hipError_t launch_reduce_counters(const SolveParams& sp, const DevBufs& d,
@@ -94,6 +96,14 @@ hipError_t launch_store_list(const SolveParams& sp, const DevBufs& d, int n, con
 hipError_t launch_status_list(const DevBufs& d, int n, const int* list, int32_t* status,
                               hipStream_t s);
 
+// ---- mhpc_options.hip -----------------------------------------------------------------------
+// list-driven device code of mhpc_set_option_sets / mhpc_copy_problems: ent [n][2] on the device,
+// (problem, option record); each listed problem's oid entry and, with state != 0, the option
+// fields a solve rewrites (ProbState::opt_reb / opt_pen) from that record of the table
+// (oid: the handle's writable index, the array d.oid reads)
+hipError_t launch_set_options(const DevBufs& d, int* oid, int n, const int* ent, int state,
+                              hipStream_t s);
+
 // ---- mhpc_control.hip -----------------------------------------------------------------------
 // Control I/O through device arrays of the caller's element type (dtype MHPC_DEV_F64 / _F32).
 // launch_control: u = u_nom + K (x - x_nom) at control step step[b] of every problem (step on the
@@ -108,14 +118,14 @@ hipError_t launch_x0_in(const SolveParams& sp, const DevBufs& d, const void* x0,
                         hipStream_t s);
 
 // ---- mhpc_bws.hip ---------------------------------------------------------------------------
-hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, real update_reg, int part,
+hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter, int part,
                       hipStream_t s);
 bool bws_split(const SolveParams& sp);
 // the sweep's pivot reciprocal in the sweep's arithmetic type (double in both libraries)
 hipError_t launch_eval_recip(int n, const double* a, double* out, hipStream_t s);
 #ifdef MHPC_FP32
 namespace fsweep {  // the float-arithmetic sweep (mhpc_bws.hip built with MHPC_BWS_F64=0)
-hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, real update_reg, int part,
+hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter, int part,
                       hipStream_t s);
 hipError_t launch_eval_recip(int n, const float* a, float* out, hipStream_t s);
 }

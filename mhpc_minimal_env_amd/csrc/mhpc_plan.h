@@ -5,7 +5,10 @@
 // arrays as they are, the merge of equal parameter sets, and plan_groups, which turns
 // (layout, set) of every problem into a GroupPlan.  The runtime (mhpc_runtime.cpp) validates,
 // plans, and only then commits a plan to the handle and the device (commit_groups); the host check
-// (tests/native/plan_hostcheck.cpp) compiles this header with plain g++.
+// (tests/native/plan_hostcheck.cpp) compiles this header with plain g++.  Option sets are no part of
+// the grouping: their checks, the table of records (plan_options), the iteration caps of a scope
+// (scope_caps) and the launch schedule those give (solve_ops) are here as well
+// (tests/native/option_hostcheck.cpp).
 //
 // A function that can refuse returns MHPC_ERR_INVALID and sets *msg (a literal); it changes
 // nothing it was given unless its comment says otherwise.
@@ -194,6 +197,180 @@ inline void merge_sets(std::vector<CostParams>& sets, std::vector<int>& of) {
   }
   for (int& s : of) s = to[s];
   sets.swap(out);
+}
+
+// ---- option sets ----------------------------------------------------------------------------
+// Integer iteration cap of a (double) max_AL_iter / max_DDP_iter: the last i of the reference's
+// `for (i = 1; i <= max_iter; ++i)` (MultiPhaseDDP.cpp:168, 192), 0 when the loop never runs
+// (0, negative, a fraction below 1); a fraction above rounds down.  check_option bounds v.
+constexpr double kMaxIterBudget = 1 << 20;
+inline int option_cap(double v) {
+  int cap = 0;
+  for (int i = 1; i <= v && i <= (int)kMaxIterBudget; ++i) cap = i;
+  return cap;
+}
+// Trials of the line-search grid 1, alpha, alpha^2, ... > 1e-10 exactly as
+// MultiPhaseDDP::forward_iteration generates it (:130-151), into eps when given; more than max:
+// max + 1 is returned.
+inline int option_grid(double alpha, int max, real* eps) {
+  int nc = 0;
+  for (double e = 1; e > pow(0.1, 10); e *= alpha) {
+    if (nc == max) return max + 1;
+    if (eps) eps[nc] = (real)e;
+    ++nc;
+  }
+  return nc;
+}
+// An option record as mhpc_create and the option setters take it: alpha in (0,1) with a grid of
+// at most MAXC trials, every real field finite, iteration budgets no larger than kMaxIterBudget
+// (a schedule of that length could not be issued anyway).  alpha_of != null (the setters): alpha
+// must be, bit for bit, the handle's -- it fixes the line-search grid and with it the arrays' shape.
+inline int check_option(const mhpc_hsddp_option* o, const double* alpha_of, const char** msg) {
+  if (!o) return plan_refuse(msg, "null option");
+  if (!(o->alpha > 0 && o->alpha < 1)) return plan_refuse(msg, "alpha must be in (0,1)");
+  if (alpha_of && memcmp(&o->alpha, alpha_of, sizeof(double)) != 0)
+    return plan_refuse(msg, "alpha differs from the handle's (it fixes the line-search grid)");
+  if (option_grid(o->alpha, MAXC, nullptr) > MAXC)
+    return plan_refuse(msg, "line search needs more than 32 trials (alpha too large)");
+  const double f[] = {o->gamma,      o->update_penalty, o->update_relax, o->update_regularization,
+                      o->update_ReB, o->max_DDP_iter,   o->max_AL_iter,  o->DDP_thresh,
+                      o->AL_thresh};
+  for (double v : f)
+    if (!std::isfinite(v)) return plan_refuse(msg, "option fields must be finite");
+  if (o->max_DDP_iter > kMaxIterBudget || o->max_AL_iter > kMaxIterBudget)
+    return plan_refuse(msg, "iteration budget too large");
+  return MHPC_OK;
+}
+// A record normalised for comparison and reporting (the reserved field zero); records compare
+// bit for bit, every field.
+inline mhpc_hsddp_option norm_option(const mhpc_hsddp_option& in) {
+  mhpc_hsddp_option o = in;
+  o.reserved = 0;
+  return o;
+}
+inline bool same_option(const mhpc_hsddp_option& a, const mhpc_hsddp_option& b) {
+  const mhpc_hsddp_option x = norm_option(a), y = norm_option(b);
+  static_assert(sizeof(mhpc_hsddp_option) == 10 * sizeof(double) + 4 * sizeof(int32_t), "no padding");
+  return memcmp(&x, &y, sizeof x) == 0;
+}
+// The record as the kernels read it (mhpc_solver.h, OptRec), with its iteration caps.
+inline OptRec option_record(const mhpc_hsddp_option& o) {
+  OptRec r;
+  memset(&r, 0, sizeof r);
+  r.gamma = (real)o.gamma;
+  r.DDP_thresh = (real)o.DDP_thresh;
+  r.AL_thresh = (real)o.AL_thresh;
+  r.update_penalty = (real)o.update_penalty;
+  r.update_relax = (real)o.update_relax;
+  r.update_regularization = (real)o.update_regularization;
+  r.update_ReB = (real)o.update_ReB;
+  r.AL_active = o.AL_active ? 1 : 0;
+  r.ReB_active = o.ReB_active ? 1 : 0;
+  r.n_al = option_cap(o.max_AL_iter);
+  r.max_ddp = option_cap(o.max_DDP_iter);
+  return r;
+}
+// The option table of a handle: at most MAXO slots, each a record and the number of problems that
+// use it (0: the slot is free -- unused records are dropped), and each problem's slot.  Slots are
+// stable: a problem whose record does not change keeps its slot, so an assignment touches the
+// device entries of the changed problems alone.  Equal records share a slot (merged).
+struct OptTable {
+  std::vector<mhpc_hsddp_option> rec;  // [slots] (a free slot keeps its last record)
+  std::vector<int> use;                // [slots]
+  std::vector<int> of;                 // [B] slot of each problem
+  int in_use() const { return (int)std::count_if(use.begin(), use.end(), [](int u) { return u > 0; }); }
+  int find(const mhpc_hsddp_option& o) const {  // the used slot holding o, -1 if none
+    for (size_t s = 0; s < rec.size(); ++s)
+      if (use[s] > 0 && same_option(rec[s], o)) return (int)s;
+    return -1;
+  }
+};
+// Problem b gets record want[b] (checked records): t becomes the new table, changed the problems
+// whose record differs from the one they had, in problem order.  Refused, with t and changed as
+// they were, when the distinct records in use would exceed MAXO.
+inline int plan_options(OptTable& t, const std::vector<const mhpc_hsddp_option*>& want,
+                        std::vector<int>& changed, const char** msg) {
+  OptTable n = t;
+  std::vector<int> ch;
+  for (size_t b = 0; b < want.size(); ++b)
+    if (!same_option(t.rec[t.of[b]], *want[b])) {
+      ch.push_back((int)b);
+      --n.use[n.of[b]];
+    }
+  for (int b : ch) {
+    int s = n.find(*want[b]);
+    for (size_t f = 0; s < 0 && f < n.rec.size(); ++f)
+      if (n.use[f] == 0) s = (int)f;
+    if (s < 0) {
+      if ((int)n.rec.size() == MAXO)
+        return plan_refuse(msg, "more than MHPC_MAX_OPTION_SETS distinct option sets");
+      s = (int)n.rec.size();
+      n.rec.push_back(norm_option(*want[b]));
+      n.use.push_back(0);
+    }
+    if (n.use[s] == 0) n.rec[s] = norm_option(*want[b]);
+    ++n.use[s];
+    n.of[b] = s;
+  }
+  t = std::move(n);
+  changed = std::move(ch);
+  return MHPC_OK;
+}
+
+// ---- the solve schedule -----------------------------------------------------------------------
+// The iteration caps a scope's schedule runs to: the largest n_al and max_ddp among its problems
+// (list == nullptr: every problem, the whole batch).  A problem with smaller caps sits the rest
+// out on the device (in_op, mhpc_device.h).
+// min_*: the smallest caps, al_uniform: the problems' common AL_active (-1: they differ) -- what
+// lets the schedule's kernels skip the per-problem reads (SolveParams::min_n_al ...).
+struct ScopeCaps {
+  int n_al = 0, max_ddp = 0;
+  int min_n_al = 0, min_max_ddp = 0, al_uniform = -1;
+};
+inline ScopeCaps scope_caps(const OptTable& t, const int* list, int n) {
+  std::vector<char> used(t.rec.size(), 0);
+  if (list)
+    for (int i = 0; i < n; ++i) used[t.of[list[i]]] = 1;
+  else
+    for (int s : t.of) used[s] = 1;
+  ScopeCaps c;
+  bool first = true;
+  for (size_t s = 0; s < t.rec.size(); ++s) {
+    if (!used[s]) continue;
+    const int a = option_cap(t.rec[s].max_AL_iter), dd = option_cap(t.rec[s].max_DDP_iter);
+    const int on = t.rec[s].AL_active ? 1 : 0;
+    c.n_al = std::max(c.n_al, a);
+    c.max_ddp = std::max(c.max_ddp, dd);
+    c.min_n_al = first ? a : std::min(c.min_n_al, a);
+    c.min_max_ddp = first ? dd : std::min(c.min_max_ddp, dd);
+    c.al_uniform = first ? on : (c.al_uniform == on ? on : -1);
+    first = false;
+  }
+  return c;
+}
+// MultiPhaseDDP::solve (MultiPhaseDDP.cpp:154-289) as a list of launches for iteration caps
+// (n_al, max_ddp); full: the first forward_sweep(0) is a real rollout.  al / ddp name the
+// iteration an op belongs to (OP_AL: the AL iteration it closes, 1 for the lone update of a
+// schedule without AL iterations), last marks the schedule's final op.
+enum { OP_COST, OP_FULL, OP_PAR, OP_BWS, OP_LS, OP_AL };
+struct SolveOp {
+  int kind, al, ddp, last;
+};
+inline std::vector<SolveOp> solve_ops(ScopeCaps c, bool full) {
+  std::vector<SolveOp> ops;
+  for (int al = 1; al <= c.n_al; ++al) {
+    // forward_sweep(0); a real rollout for the rotated nominal of update_problem
+    ops.push_back({al == 1 && full ? OP_FULL : OP_COST, al, 0, 0});
+    ops.push_back({OP_PAR, al, 0, 0});
+    for (int ddp = 1; ddp <= c.max_ddp; ++ddp) {
+      ops.push_back({OP_BWS, al, ddp, 0});
+      ops.push_back({OP_LS, al, ddp, 0});  // forward_iteration
+      if (ddp < c.max_ddp) ops.push_back({OP_PAR, al, ddp, 0});
+    }
+    ops.push_back({OP_AL, al, 0, al == c.n_al ? 1 : 0});
+  }
+  if (c.n_al == 0) ops.push_back({OP_AL, 1, 0, 1});
+  return ops;
 }
 
 // ---- a layout against the arrays as they are (mhpc_reset_problems, mhpc_copy_problems) --------

@@ -50,7 +50,18 @@ static const char* kKernelNames[NKERN] = {"k_init", "k_cost(forward_sweep0)", "k
 
 struct Handle {
   mhpc_problem_desc desc;  // the descriptor of mhpc_create (precision, vel, height)
-  mhpc_hsddp_option opt;
+  mhpc_hsddp_option opt;   // the option of mhpc_create: its alpha is the handle's line-search grid
+  // option sets (mhpc_set_option_sets): the table of distinct records in use with each problem's
+  // slot by problem number (mhpc_plan.h, OptTable); the device copies dopt [MAXO] (OptRec) and
+  // doid [B].  otab.rec[otab.of[0]] is what mhpc_get_options reports.
+  OptTable otab;
+  // srb_open[b]: mhpc_initialize / mhpc_reset_problems left problem b's SRB nominal zero because its
+  // record has no AL iteration (k_init_params), and no solve has covered it since.  Should its
+  // budget be raised before that solve, its first forward_sweep(0) must be the real rollout
+  // (api_set_option_sets).
+  std::vector<char> srb_open;
+  OptRec* dopt = nullptr;
+  int* doid = nullptr;
   int device = 0;
   SolveParams sp;
   DevBufs d;
@@ -162,13 +173,15 @@ const char* api_kernel_name(int k) {
 static void free_bufs(Handle* h) {
   DevBufs& d = h->d;
   void* ptrs[] = {d.traj, d.refpos, d.K, d.du, d.G, d.par, d.px, d.x0, d.st, d.out, d.carry,
-                  h->dgrp, h->dgidx, h->dlid, h->dcmd};
+                  h->dgrp, h->dgidx, h->dlid, h->dcmd, h->dopt, h->doid};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   memset(&d, 0, sizeof d);
   h->dgrp = nullptr;
   h->dgidx = h->dlid = nullptr;
   h->dcmd = nullptr;
+  h->dopt = nullptr;
+  h->doid = nullptr;
 }
 
 // The packed per-knot arrays for a knot stride of NK (grown, never shrunk: their content is
@@ -231,6 +244,28 @@ static int upload_plan(Handle* h) {
   HIPCHK(hipMemcpyAsync(h->dlid, h->plan.lid.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return upload_params(h);
+}
+
+// The option table to the device (every slot; a free one holds a stale record nobody indexes), and
+// k_init's copy of problem 0's record (SolveParams::update_penalty / ReB_active).
+static int upload_options(Handle* h) {
+  std::vector<OptRec> t(h->otab.rec.size());
+  for (size_t s = 0; s < t.size(); ++s) t[s] = option_record(h->otab.rec[s]);
+  const OptRec r0 = option_record(h->otab.rec[h->otab.of[0]]);
+  h->sp.update_penalty = r0.update_penalty;
+  h->sp.ReB_active = r0.ReB_active;
+  HIPCHK(hipMemcpyAsync(h->dopt, t.data(), t.size() * sizeof(OptRec), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return MHPC_OK;
+}
+// More than one parameter set or option set: k_init wrote problem 0's values for every problem and
+// k_init_params must follow it with each problem's own.
+// The same kernel leaves the SRB nominal of a problem without AL iterations open (zero, as the
+// reference's), so a single record with no AL iteration needs it too.
+static bool no_al_iteration(const mhpc_hsddp_option& o) { return option_cap(o.max_AL_iter) == 0; }
+static bool own_init_values(const Handle* h) {
+  if (h->psets.size() > 1 || h->otab.in_use() > 1) return true;
+  return no_al_iteration(h->otab.rec[h->otab.of[0]]);
 }
 
 // The one way a new grouping reaches a handle: `plan` (plan_groups over the new layouts and sets)
@@ -458,13 +493,98 @@ int api_num_param_sets(Handle* h, int* n) {
   return MHPC_OK;
 }
 
+static int dev_fail(const char* fn, hipError_t e);
+
+// ---- per-problem option sets (mhpc_set_option_sets) ---------------------------------------------
+// In the reference each MHPCLocomotion owns its MultiPhaseDDP::_option, and giving a controller
+// another option is `_option = o`.  Here: validate every record, plan the table on a working copy
+// (plan_options, mhpc_plan.h), and only then upload the table and run the list-driven kernel over
+// the problems whose record changed (their oid entry, and the two fields a solve rewrites).  A
+// problem whose record did not change keeps its slot and its device state; a call that changes no
+// problem touches nothing.  Nothing becomes pending: the next solve or tick reads the new records.
+int api_set_option_sets(Handle* h, int n_sets, const mhpc_hsddp_option* sets, const int32_t* set_of) {
+  if (!h || !sets) return fail(MHPC_ERR_INVALID, "null argument");
+  if (n_sets < 1 || n_sets > MHPC_MAX_OPTION_SETS)
+    return fail(MHPC_ERR_INVALID, "n_sets must be 1..MHPC_MAX_OPTION_SETS");
+  for (int i = 0; i < n_sets; ++i) PLANCHK(check_option, &sets[i], &h->opt.alpha);
+  const int B = h->sp.B;
+  std::vector<const mhpc_hsddp_option*> want(B);
+  for (int b = 0; b < B; ++b) {
+    const int i = set_of ? set_of[b] : b % n_sets;
+    if (i < 0 || i >= n_sets) return fail(MHPC_ERR_INVALID, "set index out of range");
+    want[b] = &sets[i];
+  }
+  OptTable nt = h->otab;
+  std::vector<int> changed;
+  PLANCHK(plan_options, nt, want, changed);
+  if (changed.empty()) return MHPC_OK;
+  std::vector<int> ent(2 * changed.size());
+  for (size_t i = 0; i < changed.size(); ++i) {
+    ent[2 * i] = changed[i];
+    ent[2 * i + 1] = nt.of[changed[i]];
+  }
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  DevTemp<int> ti(h->stream);
+  const int* dent = ti.in(std::move(ent));
+  if (ti.e != hipSuccess) return dev_fail("mhpc_set_option_sets", ti.e);
+  // ---- nothing of the handle or the device has changed up to here ----
+  std::swap(h->otab, nt);
+  int rc = upload_options(h);
+  if (rc) {  // the old table back, host and device (as far as the device still answers)
+    const std::string why = mhpc_g_err;
+    std::swap(h->otab, nt);
+    (void)upload_options(h);
+    mhpc_g_err = why;
+    return rc;
+  }
+  hipError_t e = launch_set_options(h->d, h->doid, (int)changed.size(), dent, 1, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return dev_fail("mhpc_set_option_sets", e);
+  // A problem whose SRB nominal was left open and that now has AL iterations: its next solve's
+  // first forward_sweep(0) is the reference's real rollout, not the cost evaluation of a nominal
+  // k_init completed.  Right after mhpc_initialize (nothing solved, no rollout due) that means a
+  // solve that starts with the rollout for it and with the cost evaluation for everybody else,
+  // which is what `fresh` says; otherwise the next solve starts with the rollout anyway and the
+  // problem only stops being fresh.
+  for (int b : changed) {
+    if (!h->srb_open[b] || no_al_iteration(h->otab.rec[h->otab.of[b]])) continue;
+    h->srb_open[b] = 0;
+    if (!h->need_full && !h->solved && h->initialized) {
+      h->need_full = true;
+      for (int q = 0; q < B; ++q) h->fresh[q] = 1;
+      h->nfresh = B;
+    }
+    if (h->fresh[b]) {
+      h->fresh[b] = 0;
+      --h->nfresh;
+    }
+  }
+  return MHPC_OK;
+}
+int api_set_options(Handle* h, const mhpc_hsddp_option* o) {
+  return api_set_option_sets(h, 1, o, nullptr);
+}
+int api_get_problem_options(Handle* h, int b, mhpc_hsddp_option* o) {
+  if (!h || !o) return fail(MHPC_ERR_INVALID, "null argument");
+  if (b < 0 || b >= h->sp.B) return fail(MHPC_ERR_INVALID, "problem out of range");
+  *o = h->otab.rec[h->otab.of[b]];
+  return MHPC_OK;
+}
+int api_get_options(Handle* h, mhpc_hsddp_option* o) { return api_get_problem_options(h, 0, o); }
+int api_num_option_sets(Handle* h, int* n) {
+  if (!h || !n) return fail(MHPC_ERR_INVALID, "null argument");
+  *n = h->otab.in_use();
+  return MHPC_OK;
+}
+
 int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int batch,
                            int device, Handle** out) {
   if (!out || !opt) return fail(MHPC_ERR_INVALID, "null argument");
   *out = nullptr;
   PLANCHK(check_desc, desc);
   if (batch < 1) return fail(MHPC_ERR_INVALID, "batch must be >= 1");
-  if (!(opt->alpha > 0 && opt->alpha < 1)) return fail(MHPC_ERR_INVALID, "alpha must be in (0,1)");
+  PLANCHK(check_option, opt, nullptr);
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail(MHPC_ERR_INVALID, "no such device");
@@ -482,27 +602,17 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
       sp.ncu < 1)
     sp.ncu = 256;
   // line-search grid exactly as MultiPhaseDDP::forward_iteration generates it (:130-151)
-  int nc = 0;
-  for (double eps = 1; eps > pow(0.1, 10); eps *= opt->alpha) {
-    if (nc == MAXC) {
-      delete h;
-      return fail(MHPC_ERR_INVALID, "line search needs more than 32 trials (alpha too large)");
-    }
-    sp.eps[nc++] = eps;
-  }
+  const int nc = option_grid(opt->alpha, MAXC, sp.eps);  // (check_option: at most MAXC trials)
   sp.n_cand = nc;
   sp.ro_store = ro_store_default();
   sp.nslot = nc + 1;
-  sp.gamma = opt->gamma;
-  sp.DDP_thresh = opt->DDP_thresh;
-  sp.AL_thresh = opt->AL_thresh;
-  sp.update_penalty = opt->update_penalty;
-  sp.update_relax = opt->update_relax;
-  sp.update_regularization = opt->update_regularization;
-  sp.update_ReB = opt->update_ReB;
   sp.eps9 = pow(0.1, 9);
-  sp.AL_active = opt->AL_active ? 1 : 0;
-  sp.ReB_active = opt->ReB_active ? 1 : 0;
+  sp.min_n_al = sp.min_max_ddp = 0;  // (outside a solve's scope: every kernel reads the records)
+  sp.al_uniform = -1;
+  // one option set: the record given here, every problem's (upload_options below fills k_init's copy)
+  h->otab.rec.assign(1, norm_option(*opt));
+  h->otab.use.assign(1, batch);
+  h->otab.of.assign(batch, 0);
   {  // the reference's weights and constraint parameters until mhpc_set_* replaces them
     mhpc_cost_weights w;
     mhpc_constraint_params c;
@@ -516,6 +626,7 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
   }
   h->pl.assign(batch, ProbLayout{h->desc, 0, 0});
   h->fresh.assign(batch, 0);
+  h->srb_open.assign(batch, 0);
   h->cmd_mark.assign(batch, 0);
   h->cmode.assign(batch, desc->mode_seq[0]);
 
@@ -535,6 +646,8 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
   alloc((void**)&h->dgidx, B * sizeof(int));
   alloc((void**)&h->dlid, B * sizeof(int));
   alloc((void**)&h->dsplit, B * sizeof(int));
+  alloc((void**)&h->dopt, MAXO * sizeof(OptRec));
+  alloc((void**)&h->doid, B * sizeof(int));
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->evfork, hipEventDisableTiming);
@@ -547,6 +660,8 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
   // zero x0 on the handle's own (non-blocking) stream: a null-stream memset would not be
   // ordered before mhpc_set_x0's copy on this stream
   if (e == hipSuccess) e = hipMemsetAsync(d.x0, 0, B * 14 * sizeof(real), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(h->dopt, 0, MAXO * sizeof(OptRec), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(h->doid, 0, B * sizeof(int), h->stream);  // slot 0
   // every problem starts with the descriptor's command
   h->cmd.resize(2 * B);
   for (size_t b = 0; b < B; ++b) {
@@ -559,6 +674,11 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
     d.grp = h->dgrp;
     d.gidx = h->dgidx;
     d.lid = h->dlid;
+    d.opt = h->dopt;
+    d.oid = h->doid;
+    rc2 = upload_options(h);
+  }
+  if (!rc2) {
     GroupPlan plan;
     rc2 = plan_groups(h->pl, h->pset_of, plan, nullptr);  // (one layout, one set: never refused)
     if (!rc2) rc2 = commit_groups(h, std::move(plan), false);
@@ -686,8 +806,8 @@ static int initialize_async(Handle* h) {
   HIPCHK(hipEventRecord(h->evjoin, h->stream2));
   LAUNCH(h, K_INIT, launch_init(sp, d, h->stream));
   // (k_init wrote the AL / ReB initial values of problem 0's set for every problem)
-  if (h->psets.size() > 1) {  // its time and bytes (four MAXP-long arrays a problem) count as k_init's
-    LAUNCH(h, K_INIT, launch_init_params(sp, d, h->stream));
+  if (own_init_values(h)) {  // its time and bytes (four MAXP-long arrays a problem) count as k_init's
+    LAUNCH(h, K_INIT, launch_init_params(sp, d, 1, h->stream));
     h->kbytes[K_INIT] += (double)sp.B * 4 * MAXP * kB;
   }
   HIPCHK(hipStreamWaitEvent(h->stream, h->evjoin, 0));
@@ -698,6 +818,7 @@ static int initialize_async(Handle* h) {
   h->need_full = false;
   std::fill(h->fresh.begin(), h->fresh.end(), 0);
   h->nfresh = 0;
+  for (int b = 0; b < sp.B; ++b) h->srb_open[b] = no_al_iteration(h->otab.rec[h->otab.of[b]]);
   return MHPC_OK;
 }
 
@@ -745,10 +866,7 @@ int api_initialize(Handle* h) {
 // arithmetic, tests/test_gpu_variants.py).  Block s+1 starts one launch behind block s:
 // the line search (two thirds of the SIMDs busy at batch 1024, one wave per SIMD) then
 // shares the chip with the other block's sweep / partials instead of leaving SIMDs idle.
-enum { OP_COST, OP_FULL, OP_PAR, OP_BWS, OP_LS, OP_AL };
-struct SolveOp {
-  int kind, al, ddp, max_ddp;
-};
+// (the ops themselves: solve_ops, mhpc_plan.h)
 struct SolveBlock {
   SolveParams sp;
   DevBufs d;
@@ -768,6 +886,7 @@ struct Scope {
   SolveParams sp;
   DevBufs d;
   int n = 0;           // problems of the scope
+  ScopeCaps caps;      // the largest iteration caps among them (scope_caps, mhpc_plan.h)
   bool full = false;   // the first op is the real rollout (a rotated nominal, a new x0)
   // ... with fresh problems in the scope (Handle::fresh): that op splits into the rolled-out
   // problems and the fresh ones (k_cost) over ss->split (mhpc_plan.h, solve_scope)
@@ -800,29 +919,8 @@ static DevBufs block_bufs(const DevBufs& d, const SolveParams& sp, size_t b0) {
   o.out += b0 * NK * KS;
   o.carry += b0;
   o.cmd += b0;
+  o.oid += b0;
   return o;
-}
-
-static std::vector<SolveOp> solve_ops(const Handle* h, bool full) {
-  const mhpc_hsddp_option& o = h->opt;
-  std::vector<SolveOp> ops;
-  int n_al = 0;
-  for (int al = 1; al <= o.max_AL_iter; ++al) n_al = al;
-  int max_ddp = 0;
-  for (int ddp = 1; ddp <= o.max_DDP_iter; ++ddp) max_ddp = ddp;
-  for (int al = 1; al <= n_al; ++al) {
-    // forward_sweep(0); a real rollout for the rotated nominal of update_problem
-    ops.push_back({al == 1 && full ? OP_FULL : OP_COST, al, 0, 0});
-    ops.push_back({OP_PAR, al, 0, 0});
-    for (int ddp = 1; ddp <= max_ddp; ++ddp) {
-      ops.push_back({OP_BWS, al, ddp, max_ddp});
-      ops.push_back({OP_LS, al, ddp, max_ddp});  // forward_iteration
-      if (ddp < max_ddp) ops.push_back({OP_PAR, al, ddp, max_ddp});
-    }
-    ops.push_back({OP_AL, al == n_al ? 1 : 0, 0, 0});
-  }
-  if (n_al == 0) ops.push_back({OP_AL, 1, 0, 0});
-  return ops;
 }
 
 // With bws_split the partials run on the block's second stream beside the SRB half of the
@@ -830,7 +928,6 @@ static std::vector<SolveOp> solve_ops(const Handle* h, bool full) {
 static int issue_op(Handle* h, const SolveBlock& k, const SolveOp& op) {
   const SolveParams& sp = k.sp;
   const DevBufs& d = k.d;
-  const real ureg = h->opt.update_regularization;
   const bool split = bws_split(sp);
 #ifdef MHPC_FP32
   auto launch_bws = h->sweep_bits == 32 ? fsweep::launch_bws : MHPC_NS::launch_bws;
@@ -841,40 +938,40 @@ static int issue_op(Handle* h, const SolveBlock& k, const SolveOp& op) {
         DevBufs ds = d;
         ds.gidx = h->dsplit;
         if (launch_problems(k.spf) > 0)
-          LAUNCH_ON(h, K_FULL, k.s1, launch_rollout(k.spf, ds, op.al, 0, 0, 1, k.s1));
+          LAUNCH_ON(h, K_FULL, k.s1, launch_rollout(k.spf, ds, op.al, 0, 1, k.s1));
         if (launch_problems(k.spc) > 0)
           LAUNCH_ON(h, K_FULL, k.s1, launch_cost(k.spc, ds, op.al, k.s1));
         break;
       }
-      LAUNCH_ON(h, K_FULL, k.s1, launch_rollout(sp, d, op.al, 0, 0, 1, k.s1));
+      LAUNCH_ON(h, K_FULL, k.s1, launch_rollout(sp, d, op.al, 0, 1, k.s1));
       break;
     case OP_COST:
       LAUNCH_ON(h, K_FULL, k.s1, launch_cost(sp, d, op.al, k.s1));
       break;
     case OP_PAR:
       if (!split) {
-        LAUNCH_ON(h, K_PAR, k.s1, launch_partials(sp, d, k.s1, k.s3, k.pfork, k.pjoin));
+        LAUNCH_ON(h, K_PAR, k.s1, launch_partials(sp, d, op.al, op.ddp, k.s1, k.s3, k.pfork, k.pjoin));
         break;
       }
       HIPCHK(hipEventRecord(k.fork, k.s1));
       HIPCHK(hipStreamWaitEvent(k.s2, k.fork, 0));
-      LAUNCH_ON(h, K_PAR, k.s2, launch_partials(sp, d, k.s2, k.s3, k.pfork, k.pjoin));
+      LAUNCH_ON(h, K_PAR, k.s2, launch_partials(sp, d, op.al, op.ddp, k.s2, k.s3, k.pfork, k.pjoin));
       HIPCHK(hipEventRecord(k.join, k.s2));
       break;
     case OP_BWS:
       if (!split) {
-        LAUNCH_ON(h, K_BWS, k.s1, launch_bws(sp, d, ureg, 0, k.s1));
+        LAUNCH_ON(h, K_BWS, k.s1, launch_bws(sp, d, op.al, op.ddp, 0, k.s1));
         break;
       }
-      LAUNCH_ON(h, K_BWS_SRB, k.s1, launch_bws(sp, d, ureg, 1, k.s1));
+      LAUNCH_ON(h, K_BWS_SRB, k.s1, launch_bws(sp, d, op.al, op.ddp, 1, k.s1));
       HIPCHK(hipStreamWaitEvent(k.s1, k.join, 0));
-      LAUNCH_ON(h, K_BWS, k.s1, launch_bws(sp, d, ureg, 2, k.s1));
+      LAUNCH_ON(h, K_BWS, k.s1, launch_bws(sp, d, op.al, op.ddp, 2, k.s1));
       break;
     case OP_LS:
-      LAUNCH_ON(h, K_LS, k.s1, launch_rollout(sp, d, op.al, op.ddp, op.max_ddp, 0, k.s1));
+      LAUNCH_ON(h, K_LS, k.s1, launch_rollout(sp, d, op.al, op.ddp, 0, k.s1));
       break;
     default:
-      LAUNCH_ON(h, K_AL, k.s1, launch_al_end(sp, d, op.al, k.s1));
+      LAUNCH_ON(h, K_AL, k.s1, launch_al_end(sp, d, op.al, op.last, k.s1));
   }
   return MHPC_OK;
 }
@@ -906,7 +1003,12 @@ static int ensure_sub_streams(Handle* h, int n) {
 static int solve_async(Handle* h, Scope& sc) {
   // stored line-search trials for this scope's launch shape (unless set by the caller)
   if (!h->ro_store_req) sc.sp.ro_store = ro_store_auto(sc.sp);
-  const std::vector<SolveOp> ops = solve_ops(h, sc.full);
+  // what the scope's problems have in common, for the kernels' gates (SolveParams::min_n_al ...)
+  sc.sp.min_n_al = sc.caps.min_n_al;
+  sc.sp.min_max_ddp = sc.caps.min_max_ddp;
+  sc.sp.al_uniform = sc.caps.al_uniform;
+  // the schedule runs to the largest iteration caps among the scope's problems
+  const std::vector<SolveOp> ops = solve_ops(sc.caps, sc.full);
   const int nops = (int)ops.size();
   const int nsub = sub_batches(h, sc.n);
   int rc;
@@ -1013,6 +1115,7 @@ static Scope batch_scope(Handle* h, SolveScope& ss) {
   sc.sp = h->sp;
   sc.d = h->d;
   sc.n = h->sp.B;
+  sc.caps = scope_caps(h->otab, nullptr, 0);
   sc.full = h->need_full;
   sc.mixed = h->need_full && h->nfresh > 0;
   if (sc.mixed) {
@@ -1078,6 +1181,7 @@ int api_solve(Handle* h, int32_t* status) {
   h->need_full = false;
   std::fill(h->fresh.begin(), h->fresh.end(), 0);
   h->nfresh = 0;
+  std::fill(h->srb_open.begin(), h->srb_open.end(), 0);  // (every later first sweep is the real rollout)
   if ((rc = account_solve(h, sc))) return rc;
   if (status) {
     std::vector<ProbState> st(h->sp.B);
@@ -1607,7 +1711,7 @@ int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const in
       --h->nfresh;
     }
   HIPCHK(launch_reset(h->sp, h->d, h->stream));  // refs from x0, AL/ReB init, nom_slot = 0
-  if (h->psets.size() > 1) HIPCHK(launch_init_params(h->sp, h->d, h->stream));
+  if (own_init_values(h)) HIPCHK(launch_init_params(h->sp, h->d, 0, h->stream));
   HIPCHK(launch_store(h->sp, h->d, h->store, h->nbk, h->spmax, 0, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->need_full = true;
@@ -1726,11 +1830,12 @@ int api_tick_problems(Handle* h, int n, const int32_t* problems, const double* x
     sc.d = h->d;
     sc.d.gidx = dorder;
     sc.n = n;
+    sc.caps = scope_caps(h->otab, list.data(), n);
     sc.full = true;
     sc.mixed = ss.nnf < n;
     sc.ss = &ss;
     HIPCHK(launch_reset(sc.sp, sc.d, h->stream));  // refs from x0 and the command, AL/ReB init, nom_slot = 0
-    if (h->psets.size() > 1) HIPCHK(launch_init_params(sc.sp, sc.d, h->stream));
+    if (own_init_values(h)) HIPCHK(launch_init_params(sc.sp, sc.d, 0, h->stream));
     HIPCHK(launch_store_list(h->sp, h->d, n, dlist, h->store, h->nbk, h->spmax, 0, h->stream));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     if (int rc = solve_async(h, sc)) return rc;
@@ -1754,6 +1859,7 @@ int api_tick_problems(Handle* h, int n, const int32_t* problems, const double* x
       h->fresh[b] = 0;
       --h->nfresh;
     }
+    h->srb_open[b] = 0;
     if (h->cmd_mark[b]) {
       h->cmd_mark[b] = 0;
       --h->ncmd;
@@ -1837,7 +1943,7 @@ static int reset_launches(Handle* h, const std::vector<int>& order, std::vector<
   if (drows) LAUNCH(h, K_INIT, launch_scatter_x0(h->d, n, dlist, drows, h->stream));
   LAUNCH(h, K_INIT, launch_init(rs, rd, h->stream));
   // (k_init wrote the AL / ReB initial values of problem 0's set)
-  if (h->psets.size() > 1) LAUNCH(h, K_INIT, launch_init_params(rs, rd, h->stream));
+  if (own_init_values(h)) LAUNCH(h, K_INIT, launch_init_params(rs, rd, 1, h->stream));
   HIPCHK(hipStreamWaitEvent(h->stream, h->evjoin, 0));
   HIPCHK(hipStreamSynchronize(h->stream));
   return MHPC_OK;
@@ -1898,11 +2004,12 @@ int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* 
   }
   for (int b : order) {
     h->cmode[b] = h->pl[b].desc.mode_seq[0];
-    h->kbytes[K_INIT] += h->plan.bym[h->plan.lid[b]].init + (h->psets.size() > 1 ? 4 * MAXP * kB : 0.0);
+    h->kbytes[K_INIT] += h->plan.bym[h->plan.lid[b]].init + (own_init_values(h) ? 4 * MAXP * kB : 0.0);
     if (!h->fresh[b]) {
       h->fresh[b] = 1;
       ++h->nfresh;
     }
+    h->srb_open[b] = no_al_iteration(h->otab.rec[h->otab.of[b]]);
   }
   rc = reset_launches(h, order, std::move(rows));
   if (rc) {  // nothing of the handle's may stay queued behind a failed launch
@@ -1914,16 +2021,6 @@ int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* 
 }
 
 // ---- copies of live problems (mhpc_copy_problems) -------------------------------------------
-// The handle-wide options, field by field: the line-search grid, nslot and the thresholds of the
-// solve's state machine are the handle's, so a problem only continues alike under equal ones.
-static bool same_option(const mhpc_hsddp_option& a, const mhpc_hsddp_option& b) {
-  return a.alpha == b.alpha && a.gamma == b.gamma && a.update_penalty == b.update_penalty &&
-         a.update_relax == b.update_relax && a.update_regularization == b.update_regularization &&
-         a.update_ReB == b.update_ReB && a.max_DDP_iter == b.max_DDP_iter &&
-         a.max_AL_iter == b.max_AL_iter && a.DDP_thresh == b.DDP_thresh &&
-         a.AL_thresh == b.AL_thresh && a.AL_active == b.AL_active && a.ReB_active == b.ReB_active &&
-         a.smooth_active == b.smooth_active;
-}
 static CopySide copy_side(const Handle* h) {
   return CopySide{h->d, h->store_valid ? h->store : nullptr, h->sp.NK, h->sp.nslot, h->nbk, h->spmax};
 }
@@ -1953,8 +2050,18 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
     if (is_dst[sp_[i]])
       return fail(MHPC_ERR_INVALID, "a problem is both a source and a destination");
   if (d->device != s->device) return fail(MHPC_ERR_INVALID, "the handles are on different devices");
-  if (!same_option(d->opt, s->opt) || d->sp.nslot != s->sp.nslot)
+  // the line-search grid (alpha, nslot: the arrays' shape) is the handle's; a source problem's
+  // option record travels with it, as an index into dst's table -- the copy never adds a record
+  // to it (that would change dst's launch schedule), so the record must be one of dst's already
+  if (memcmp(&d->opt.alpha, &s->opt.alpha, sizeof(double)) != 0 || d->sp.nslot != s->sp.nslot)
     return fail(MHPC_ERR_INVALID, "the handles' mhpc_hsddp_option differ");
+  std::vector<int> nslot_of(n);  // dst's slot of each source problem's record
+  for (int i = 0; i < n; ++i) {
+    nslot_of[i] = d == s ? s->otab.of[sp_[i]] : d->otab.find(s->otab.rec[s->otab.of[sp_[i]]]);
+    if (nslot_of[i] < 0)
+      return fail(MHPC_ERR_INVALID,
+                  "the handles' mhpc_hsddp_option differ: a source problem's option set is none of the destination's");
+  }
   // the one kernel variant that changes results: the sweep's arithmetic (0 and 64 are both double)
   if ((d->sweep_bits == 32) != (s->sweep_bits == 32))
     return fail(MHPC_ERR_INVALID, "the handles' backward-sweep arithmetic (MHPC_VARIANT_SWEEP_BITS) differs");
@@ -2000,10 +2107,14 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
   // the pair list and, behind it, the (run, chunk) table of one pair: one upload
   const CopySide cs = copy_side(s), cd = copy_side(d);
   const int nblk = copy_block_table(cs, cd, nullptr);
-  std::vector<int> pairs(2 * (size_t)n + nblk);
+  // ... and behind that the (destination problem, option slot) entries of the option hand-over
+  std::vector<int> pairs(2 * (size_t)n + nblk + 2 * (size_t)n);
+  const size_t ent0 = 2 * (size_t)n + nblk;
   for (int i = 0; i < n; ++i) {
     pairs[2 * (size_t)i] = sp_[i];
     pairs[2 * (size_t)i + 1] = dp[i];
+    pairs[ent0 + 2 * (size_t)i] = dp[i];
+    pairs[ent0 + 2 * (size_t)i + 1] = nslot_of[i];
   }
   copy_block_table(cs, cd, pairs.data() + 2 * (size_t)n);
   DevTemp<int> t(d->stream);
@@ -2026,8 +2137,11 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
     d->cmd[2 * (size_t)b + 1] = s->cmd[2 * (size_t)a + 1];
     d->nfresh += (s->fresh[a] ? 1 : 0) - (d->fresh[b] ? 1 : 0);
     d->fresh[b] = s->fresh[a];
+    d->srb_open[b] = s->srb_open[a];
   }
   t.e = launch_copy_problems(cs, cd, n, dpairs, nblk, dpairs + 2 * (size_t)n, d->stream);
+  // the option index of the destinations (their rewritten option fields came with the state)
+  if (t.e == hipSuccess) t.e = launch_set_options(d->d, d->doid, n, dpairs + ent0, 0, d->stream);
   if (t.e == hipSuccess) t.e = hipEventRecord(d->ev1, d->stream);
   if (t.e == hipSuccess) t.e = hipStreamSynchronize(d->stream);
   float el = 0;
@@ -2038,6 +2152,17 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
     (void)hipStreamSynchronize(d->stream);
     return dev_fail("mhpc_copy_problems", t.e);
   }
+  // the host table follows the device index once the launches have succeeded (a record the
+  // destinations were the last to use is dropped; problem 0's may have changed)
+  for (int i = 0; i < n; ++i) {
+    const int b = dp[i];
+    --d->otab.use[d->otab.of[b]];
+    ++d->otab.use[nslot_of[i]];
+    d->otab.of[b] = nslot_of[i];
+  }
+  const OptRec r0 = option_record(d->otab.rec[d->otab.of[0]]);
+  d->sp.update_penalty = r0.update_penalty;
+  d->sp.ReB_active = r0.ReB_active;
   if (ms) *ms = el;
   return MHPC_OK;
 }

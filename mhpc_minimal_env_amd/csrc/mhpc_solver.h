@@ -26,6 +26,10 @@
 //          positions [go[g], go[g+1]) of gidx), lid [B] each problem's group.
 //   cmd    [B][2]              user command (vel, height) of each problem (mhpc_set_commands),
 //          indexed by problem number: it follows a problem through every regrouping.
+//   opt    [MAXO]              option table: the distinct HSDDP_OPTION records in use
+//          (mhpc_set_option_sets), oid [B] each problem's record, by problem number like cmd.
+//          Options are no grouping dimension: a kernel reads its problem's record in the
+//          per-problem control flow (line-search selection, AL update, iteration caps), per lane.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -60,6 +64,7 @@ MHPC_HOST_DEVICE inline size_t par_jac(int NK, int b, int kk) {
 constexpr int MAXP = MHPC_MAX_PHASES;
 constexpr int MAXC = 32;      // max line-search candidates
 constexpr int MAXL = MHPC_MAX_LAYOUTS;  // distinct phase layouts per handle
+constexpr int MAXO = MHPC_MAX_OPTION_SETS;  // distinct option records per handle
 constexpr int ST_RMAX = 128;  // line search: staged position references per problem (knots per phase)
 constexpr int TRACE = MHPC_TRACE_LEN;
 
@@ -118,10 +123,19 @@ struct SolveParams {
   int pmax;                  // most phases of any layout
   int n_cand, nslot;
   real eps[MAXC];          // line-search grid 1, alpha, alpha^2, ... (host libm)
-  real gamma, DDP_thresh, AL_thresh, update_penalty, update_relax, update_regularization,
-      update_ReB;
   real eps9;               // pow(0.1, 9) (SinglePhase.cpp:202), host libm
-  int AL_active, ReB_active;
+  // problem 0's update_penalty and ReB_active: only k_init reads them, for the option state it
+  // writes for every problem; the problems' own values then come from the option table
+  // (k_init_params, which says why k_init keeps reading this block).  Every other kernel reads
+  // the problem's record DevBufs::opt[oid[b]] alone.
+  real update_penalty;
+  int ReB_active;
+  // What the problems of a solve's scope have in common (scope_caps, mhpc_plan.h; set in the
+  // scope's copy of this block): the smallest iteration caps among them -- an op within both takes
+  // every problem, so its kernels skip the per-problem gate and its two dependent loads -- and
+  // their AL_active when they all agree (-1: they differ, read the record).  With one option set
+  // no kernel of the schedule reads the table before the line search's selection.
+  int min_n_al, min_max_ddp, al_uniform;
   // launch shape (host side only): compute units of the handle's device and the kernel
   // variants forced through mhpc_set_kernel_variant (0 = chosen by batch size)
   int ncu, var_bws, var_ro, var_overlap;
@@ -142,6 +156,18 @@ struct SolveParams {
 // handed to ReferenceGen by build_problem, MHPCLocomotion.cpp:98-103): DevBufs::cmd[b].
 struct Cmd {
   real vel, height;
+};
+
+// One option record (MultiPhaseDDP::_option of one controller, MHPC_CompoundTypes.h:196-212) as the
+// kernels read it: the fields of mhpc_hsddp_option but alpha (the handle's line-search grid) and
+// smooth_active (carried on the host only), and the integer iteration caps the launch schedule
+// is sized with (option_cap, mhpc_plan.h): the problem takes part in op (al, ddp) of a schedule
+// only while al <= n_al and ddp <= max_ddp.
+struct OptRec {
+  real gamma, DDP_thresh, AL_thresh, update_penalty, update_relax, update_regularization,
+      update_ReB;
+  int32_t AL_active, ReB_active;
+  int32_t n_al, max_ddp;
 };
 
 // Costs, their sums and the expected cost change are accumulated and compared in fp64 in
@@ -186,7 +212,7 @@ struct ProbState {
   // MultiPhaseDDP::_option as solve() leaves it: ReB_active and update_penalty are rewritten
   // inside the AL loop (MultiPhaseDDP.cpp:178-183, 273-277) and the next solve() starts from
   // the rewritten values (captured at its first AL iteration: cap_*) -- visible across the
-  // solves of a receding-horizon loop.  mhpc_initialize restores the handle's options.
+  // solves of a receding-horizon loop.  mhpc_initialize restores the problem's own option record.
   int32_t opt_reb, cap_reb;
   real opt_pen, cap_pen;
 };
@@ -220,6 +246,8 @@ struct DevBufs {
   const int* gidx;    // [B] problems grouped (by layout, then parameter set)
   const int* lid;     // [B] group of each problem (its record grp[lid[b]])
   const Cmd* cmd;     // [B] user command of each problem
+  const OptRec* opt;  // [MAXO] option table
+  const int* oid;     // [B] option record of each problem (opt[oid[b]])
 };
 
 }  // namespace MHPC_NS

@@ -66,6 +66,14 @@ class HSDDP_OPTION:
         o.smooth_active = int(bool(self.smooth_active))
         return o
 
+    @classmethod
+    def from_c(cls, o: capi.HsddpOption) -> "HSDDP_OPTION":
+        return cls(**{k: getattr(o, k) for k in (
+            "alpha", "gamma", "update_penalty", "update_relax", "update_regularization",
+            "update_ReB", "max_DDP_iter", "max_AL_iter", "DDP_thresh", "AL_thresh")},
+            AL_active=bool(o.AL_active), ReB_active=bool(o.ReB_active),
+            smooth_active=bool(o.smooth_active))
+
 
 @dataclass
 class USRCMD:
@@ -648,6 +656,50 @@ class MHPCLocomotion:
         import ctypes
         n = ctypes.c_int(0)
         capi.check(capi.lib().mhpc_num_param_sets(self._h, ctypes.byref(n)), "mhpc_num_param_sets")
+        return n.value
+
+    # -- per-problem option sets: the batch axis over iteration budgets and thresholds ------
+    def set_options(self, option: HSDDP_OPTION):
+        """mhpc_set_options: every problem gets `option` (the reference's `_option = o` on every
+        controller); alpha must be the handle's.  Allowed at any point of the call order; takes
+        effect at the next solve or tick."""
+        import ctypes
+        o = option.to_c()
+        capi.check(capi.lib().mhpc_set_options(self._h, ctypes.byref(o)), "mhpc_set_options")
+        self.option = option
+
+    def get_options(self) -> HSDDP_OPTION:
+        """Problem 0's option record (mhpc_get_options)."""
+        return self.get_problem_options(0)
+
+    def set_option_sets(self, options, set_of_problem=None):
+        """mhpc_set_option_sets: problem b solves with options[set_of_problem[b]] (b % n_sets
+        when None), a sequence of 1..MHPC_MAX_OPTION_SETS HSDDP_OPTION that share the handle's
+        alpha.  A solve's launch schedule runs to the largest budgets among the problems it
+        covers; a problem with a smaller budget computes what it would in a handle of its own."""
+        n = len(options)
+        sop = None
+        if set_of_problem is not None:
+            sop = np.ascontiguousarray(set_of_problem, dtype=np.int32)
+            if sop.shape != (self.batch,):
+                raise ValueError("set_of_problem must have one entry per problem")
+        arr = (capi.HsddpOption * max(n, 1))(*[o.to_c() for o in options])
+        capi.check(capi.lib().mhpc_set_option_sets(self._h, n, arr, capi.iptr(sop)),
+                   "mhpc_set_option_sets")
+        self.option = self.get_options()
+
+    def get_problem_options(self, b: int) -> HSDDP_OPTION:
+        """Problem b's option record (mhpc_get_problem_options)."""
+        import ctypes
+        o = capi.HsddpOption()
+        capi.check(capi.lib().mhpc_get_problem_options(self._h, int(b), ctypes.byref(o)),
+                   "mhpc_get_problem_options")
+        return HSDDP_OPTION.from_c(o)
+
+    def num_option_sets(self) -> int:
+        import ctypes
+        n = ctypes.c_int(0)
+        capi.check(capi.lib().mhpc_num_option_sets(self._h, ctypes.byref(n)), "mhpc_num_option_sets")
         return n.value
 
     def get_exec(self) -> dict:
