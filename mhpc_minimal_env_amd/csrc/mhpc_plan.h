@@ -8,7 +8,10 @@
 // (tests/native/plan_hostcheck.cpp) compiles this header with plain g++.  Option sets are no part of
 // the grouping: their checks, the table of records (plan_options), the iteration caps of a scope
 // (scope_caps) and the launch schedule those give (solve_ops) are here as well
-// (tests/native/option_hostcheck.cpp).
+// (tests/native/option_hostcheck.cpp).  So is what every call on some problems of a live batch
+// shares (tests/native/ledger_hostcheck.cpp): the checked problem list (ProblemList), the packer of
+// caller rows into device rows (pack_rows), the scope of a list (solve_scope: tick and reset), and
+// the per-problem call-order state with its transitions (Ledger).
 //
 // A function that can refuse returns MHPC_ERR_INVALID and sets *msg (a literal); it changes
 // nothing it was given unless its comment says otherwise.
@@ -396,12 +399,39 @@ inline int fits_arrays(const ProbLayout& q, int NK, bool store_valid, int nbk, i
                                  : "more phases than the phase-buffer store holds");
   return MHPC_OK;
 }
-// Width of the caller's x0 rows: 14 once any problem has a whole-body phase, else 6.
+// Width of the caller's x0 rows: 14 once any problem has a whole-body phase, else 6.  (Of layouts
+// not planned yet; x0_row_of(GroupPlan) below answers for an installed plan from its groups.)
 inline int x0_row_of(const std::vector<ProbLayout>& pl) {
   for (const ProbLayout& q : pl)
     if (q.desc.n_wb > 0) return 14;
   return 6;
 }
+
+// ---- a list of problems (mhpc_tick_problems, mhpc_reset_problems, mhpc_copy_problems) ----------
+// n problems of a batch of B, each in range and none twice; at[b] is problem b's place in the list
+// (-1: not listed).  copy: the wording of mhpc_copy_problems, whose list is the destinations.
+// Entry by entry (begin, then add for each in turn), so a caller with more to check per entry
+// keeps the order of its refusals.
+struct ProblemList {
+  std::vector<int> at;
+  int n = 0;  // entries added
+  bool copy = false;
+  int begin(int count, int B, bool copy_wording, const char** msg) {
+    copy = copy_wording;
+    if (count < 1 || count > B)
+      return plan_refuse(msg, copy ? "n must be 1..batch of the destination" : "n must be 1..batch");
+    at.assign(B, -1);
+    n = 0;
+    return MHPC_OK;
+  }
+  int add(int b, const char** msg) {
+    if (b < 0 || b >= (int)at.size()) return plan_refuse(msg, "problem out of range");
+    if (at[b] >= 0)
+      return plan_refuse(msg, copy ? "destination problem listed twice" : "problem listed twice");
+    at[b] = n++;
+    return MHPC_OK;
+  }
+};
 
 // ---- one problem's gait steps (mhpc_update_problems) ------------------------------------------
 // MHPCLocomotion::update_problem's host part, `steps` times: advance the gait by one mode, recompute
@@ -549,7 +579,8 @@ inline int plan_groups(const std::vector<ProbLayout>& pl, const std::vector<int>
   return MHPC_OK;
 }
 
-// ---- the scope of a solve (mhpc_solve: the batch; mhpc_tick_problems: a list) -----------------
+// ---- the scope of a solve (mhpc_solve: the batch; mhpc_tick_problems, and mhpc_reset_problems for
+// its init kernels: a list) ----------------------------------------------------------------------
 // What the solve schedule runs over: `order`, the scope's problems by group, then problem number
 // (the scope's gidx), and go[], each group's range of positions in it (a group with no problem in
 // the scope is an empty range).  The scope of the whole batch is the plan's own gidx / go[].
@@ -603,5 +634,113 @@ inline void scope_split(const SolveScope& s, const int* go, int* gof, int* goc) 
     goc[g] = s.nnf + go[g] - s.nf[go[g]];
   }
 }
+
+// ---- caller rows -> device rows ---------------------------------------------------------------
+inline int x0_row_of(const GroupPlan& plan) {
+  for (const Layout& L : plan.lays)
+    if (L.n_wb > 0) return 14;
+  return 6;
+}
+// Caller rows src [..][n_s][r] (r = x0_row_of(plan)) as `count` device rows of [n_s][14]: a problem
+// with a whole-body phase has 14 entries, an SRB-only one the first 6 of its row (nothing past
+// them is read); the rest is zero.  Destination row j is problem prob[j]'s (null: first + j) and
+// comes from the caller's row at[that problem] (null: row j).
+template <class E>
+std::vector<E> pack_rows(const GroupPlan& plan, int count, int n_s, const double* src, int first,
+                         const int32_t* prob = nullptr, const int* at = nullptr) {
+  const size_t r = x0_row_of(plan), S = n_s;
+  std::vector<E> out((size_t)count * S * 14, E(0));
+  for (int j = 0; j < count; ++j) {
+    const int b = prob ? prob[j] : first + j;
+    const int nb = plan.lays[plan.lid[b]].n_wb > 0 ? 14 : 6;
+    const double* from = src + (size_t)(at ? at[b] : j) * S * r;
+    for (size_t t = 0; t < S; ++t)
+      std::copy(from + t * r, from + t * r + nb, out.begin() + ((size_t)j * S + t) * 14);
+  }
+  return out;
+}
+
+// ---- per-problem call-order state ---------------------------------------------------------------
+// What the runtime remembers per problem between calls, and the events that change it.
+//  fresh: k_init wrote the problem's nominal since the last solve (mhpc_reset_problems) and no gait
+//    step rotated it: in a solve that starts with the real rollout its first forward_sweep(0) is
+//    still the cost evaluation, as after mhpc_initialize (the fp32 k_init rounds its warm start its
+//    own way, so only k_cost continues it bit for bit).
+//  open: mhpc_initialize / mhpc_reset_problems left the problem's SRB nominal zero because its
+//    option record has no AL iteration (k_init_params), and no solve has covered it since.
+//  mark: the problem's command changed since its references were last generated.
+// The counts follow the flags here and nowhere else.
+class Ledger {
+  std::vector<char> fresh_, open_, mark_;
+  int nfresh_ = 0, nmark_ = 0;
+  static void set(std::vector<char>& f, int& count, int b, bool v) {
+    count += (v ? 1 : 0) - (f[b] ? 1 : 0);
+    f[b] = v;
+  }
+  static void fill(std::vector<char>& f, int& count, bool v) {
+    std::fill(f.begin(), f.end(), v ? 1 : 0);
+    count = v ? (int)f.size() : 0;
+  }
+
+ public:
+  explicit Ledger(int B = 0) : fresh_(B, 0), open_(B, 0), mark_(B, 0) {}
+  int size() const { return (int)fresh_.size(); }
+  bool fresh(int b) const { return fresh_[b]; }
+  bool open(int b) const { return open_[b]; }
+  bool marked(int b) const { return mark_[b]; }
+  int nfresh() const { return nfresh_; }
+  int nmarked() const { return nmark_; }
+  bool cmd_pending() const { return nmark_ > 0; }  // any command mark
+  const std::vector<char>& fresh_flags() const { return fresh_; }  // (solve_scope)
+
+  // mhpc_initialize: nobody fresh; no_al(b): problem b's record has no AL iteration
+  template <class NoAl>
+  void initialized(NoAl no_al) {
+    fill(fresh_, nfresh_, false);
+    for (int b = 0; b < size(); ++b) open_[b] = no_al(b);
+  }
+  // mhpc_solve: every problem solved, every later first sweep the real rollout
+  void solved() {
+    fill(fresh_, nfresh_, false);
+    std::fill(open_.begin(), open_.end(), 0);
+  }
+  // mhpc_tick_problems: the listed problems have their references and their solve
+  void ticked(int n, const int32_t* list) {
+    for (int i = 0; i < n; ++i) {
+      set(fresh_, nfresh_, list[i], false);
+      open_[list[i]] = 0;
+      set(mark_, nmark_, list[i], false);
+    }
+  }
+  // mhpc_update_problems: a gait step rotates the nominal, which is then no longer k_init's
+  void stepped(int b) { set(fresh_, nfresh_, b, false); }
+  // mhpc_reset_problems of problem b
+  void reset(int b, bool no_al) {
+    set(fresh_, nfresh_, b, true);
+    open_[b] = no_al;
+  }
+  // mhpc_copy_problems: problem d becomes src's problem s (src may be this ledger).  No command is
+  // pending in either handle then, so no mark moves.
+  void copied(int d, const Ledger& src, int s) {
+    set(fresh_, nfresh_, d, src.fresh_[s]);
+    open_[d] = src.open_[s];
+  }
+  void command_changed(int b) { set(mark_, nmark_, b, true); }
+  // mhpc_initialize / mhpc_update_problem(s): every problem's references are current
+  void all_current() { fill(mark_, nmark_, false); }
+  // mhpc_set_option_sets gave problem b AL iterations.  If its SRB nominal is open, its next
+  // solve's first forward_sweep(0) is the reference's real rollout, not the cost evaluation of a
+  // nominal k_init completed.  no_rollout_due (right after mhpc_initialize: nothing solved): that
+  // solve starts with the rollout for b and with the cost evaluation for everybody else -- all
+  // fresh, then b not -- and true is returned: the caller's solve must start with the rollout.
+  // Otherwise it starts with the rollout anyway and b only stops being fresh.
+  bool budget_raised(int b, bool no_rollout_due) {
+    if (!open_[b]) return false;
+    open_[b] = 0;
+    if (no_rollout_due) fill(fresh_, nfresh_, true);
+    set(fresh_, nfresh_, b, false);
+    return no_rollout_due;
+  }
+};
 
 }  // namespace MHPC_NS

@@ -29,6 +29,20 @@ int fail(int code, const std::string& msg) {
   mhpc_g_err = msg;
   return code;
 }
+// The epilogue of a failed call: undo() (a rollback, which may fail in turn) with the failure's
+// own message kept; drain: the given streams, in that order, so that nothing of the handle's stays
+// queued behind the failure.
+template <class Undo>
+void keep_error(Undo undo) {
+  const std::string why = mhpc_g_err;
+  undo();
+  mhpc_g_err = why;
+}
+void drain(std::initializer_list<hipStream_t> streams) {
+  keep_error([&] {
+    for (hipStream_t q : streams) (void)hipStreamSynchronize(q);
+  });
+}
 
 #define HIPCHK(expr)                                                                  \
   do {                                                                                \
@@ -55,11 +69,6 @@ struct Handle {
   // slot by problem number (mhpc_plan.h, OptTable); the device copies dopt [MAXO] (OptRec) and
   // doid [B].  otab.rec[otab.of[0]] is what mhpc_get_options reports.
   OptTable otab;
-  // srb_open[b]: mhpc_initialize / mhpc_reset_problems left problem b's SRB nominal zero because its
-  // record has no AL iteration (k_init_params), and no solve has covered it since.  Should its
-  // budget be raised before that solve, its first forward_sweep(0) must be the real rollout
-  // (api_set_option_sets).
-  std::vector<char> srb_open;
   OptRec* dopt = nullptr;
   int* doid = nullptr;
   int device = 0;
@@ -77,16 +86,12 @@ struct Handle {
   // would mix new limits with old initial values -- refused until then
   bool params_changed = false;
   // per-problem user commands [B] (vel, height) as the caller gave them (the device copy is
-  // cast to real), indexed by problem number; changed after the last initialize /
-  // update_problem: the position references still belong to the old speed, so a solve in
-  // between is refused like one after new constraint parameters
+  // cast to real), indexed by problem number.  A problem whose command changed after its references
+  // were last generated is marked in the ledger: the position references still belong to the old
+  // speed, so a solve in between is refused like one after new constraint parameters
   std::vector<double> cmd;
-  bool cmd_changed = false;
-  // ... per problem: cmd_mark[b] = problem b's command changed since its references were last
-  // generated (mhpc_initialize / mhpc_update_problem(s) clear every mark, mhpc_tick_problems the
-  // listed problems'); ncmd counts the marks and cmd_changed is "any problem marked"
-  std::vector<char> cmd_mark;
-  int ncmd = 0;
+  // per-problem call-order state (mhpc_plan.h, Ledger): fresh, open SRB nominal, command mark
+  Ledger led;
   // parameter sets (mhpc_set_param_sets): the distinct sets in use, as the kernels read them
   // (real), and each problem's set by problem number; psets[pset_of[0]] is what the handle-wide
   // getters report.  sets_changed: a mixed call changed some problem's values on an initialised
@@ -122,13 +127,8 @@ struct Handle {
   int nk_floor = 0;  // mhpc_reserve_knots: floor of the knot stride wherever it may change
   bool need_full = false;
   bool store_valid = false;  // store zeroed since the last initialize (memory_reset)
-  // problems whose nominal k_init wrote since the last solve (mhpc_reset_problems) and no gait
-  // step rotated: in a solve that starts with the real rollout (need_full) their first
-  // forward_sweep(0) is still the cost evaluation, as after mhpc_initialize -- the fp32 k_init
-  // rounds its warm start its own way, so only k_cost continues it bit for bit.  dsplit [B]:
-  // the grouped order split for that op, the others first, then the fresh ones.
-  std::vector<char> fresh;
-  int nfresh = 0;
+  // dsplit [B]: the grouped order split for the first op of a solve that starts with the real
+  // rollout (need_full) while the ledger has fresh problems: the others first, then the fresh ones
   int* dsplit = nullptr;
   // sub-batches (MHPC_VARIANT_SUBBATCH): the solve schedule runs once per contiguous block of
   // problems, each block on its own stream pair; created on first use
@@ -246,14 +246,18 @@ static int upload_plan(Handle* h) {
   return upload_params(h);
 }
 
-// The option table to the device (every slot; a free one holds a stale record nobody indexes), and
-// k_init's copy of problem 0's record (SolveParams::update_penalty / ReB_active).
-static int upload_options(Handle* h) {
-  std::vector<OptRec> t(h->otab.rec.size());
-  for (size_t s = 0; s < t.size(); ++s) t[s] = option_record(h->otab.rec[s]);
+// k_init's copy of problem 0's option record (SolveParams::update_penalty / ReB_active)
+static void mirror_option0(Handle* h) {
   const OptRec r0 = option_record(h->otab.rec[h->otab.of[0]]);
   h->sp.update_penalty = r0.update_penalty;
   h->sp.ReB_active = r0.ReB_active;
+}
+// The option table to the device (every slot; a free one holds a stale record nobody indexes), and
+// k_init's copy of problem 0's record.
+static int upload_options(Handle* h) {
+  std::vector<OptRec> t(h->otab.rec.size());
+  for (size_t s = 0; s < t.size(); ++s) t[s] = option_record(h->otab.rec[s]);
+  mirror_option0(h);
   HIPCHK(hipMemcpyAsync(h->dopt, t.data(), t.size() * sizeof(OptRec), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return MHPC_OK;
@@ -298,13 +302,12 @@ static int commit_groups(Handle* h, GroupPlan&& plan, bool keep_stride,
   };
   exchange();
   const int rc = upload_plan(h);
-  if (rc) {
-    const std::string why = mhpc_g_err;
-    exchange();
-    if (h->sp.NK != old_NK && ensure_knot_arrays(h, old_NK) == MHPC_OK) h->sp.NK = old_NK;
-    if (!h->plan.gidx.empty()) (void)upload_plan(h);  // (mhpc_create has no previous plan)
-    mhpc_g_err = why;
-  }
+  if (rc)
+    keep_error([&] {
+      exchange();
+      if (h->sp.NK != old_NK && ensure_knot_arrays(h, old_NK) == MHPC_OK) h->sp.NK = old_NK;
+      if (!h->plan.gidx.empty()) (void)upload_plan(h);  // (mhpc_create has no previous plan)
+    });
   return rc;
 }
 
@@ -532,34 +535,20 @@ int api_set_option_sets(Handle* h, int n_sets, const mhpc_hsddp_option* sets, co
   std::swap(h->otab, nt);
   int rc = upload_options(h);
   if (rc) {  // the old table back, host and device (as far as the device still answers)
-    const std::string why = mhpc_g_err;
-    std::swap(h->otab, nt);
-    (void)upload_options(h);
-    mhpc_g_err = why;
+    keep_error([&] {
+      std::swap(h->otab, nt);
+      (void)upload_options(h);
+    });
     return rc;
   }
   hipError_t e = launch_set_options(h->d, h->doid, (int)changed.size(), dent, 1, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) return dev_fail("mhpc_set_option_sets", e);
-  // A problem whose SRB nominal was left open and that now has AL iterations: its next solve's
-  // first forward_sweep(0) is the reference's real rollout, not the cost evaluation of a nominal
-  // k_init completed.  Right after mhpc_initialize (nothing solved, no rollout due) that means a
-  // solve that starts with the rollout for it and with the cost evaluation for everybody else,
-  // which is what `fresh` says; otherwise the next solve starts with the rollout anyway and the
-  // problem only stops being fresh.
-  for (int b : changed) {
-    if (!h->srb_open[b] || no_al_iteration(h->otab.rec[h->otab.of[b]])) continue;
-    h->srb_open[b] = 0;
-    if (!h->need_full && !h->solved && h->initialized) {
+  // a problem that now has AL iterations while its SRB nominal is open (Ledger::budget_raised)
+  for (int b : changed)
+    if (!no_al_iteration(h->otab.rec[h->otab.of[b]]) &&
+        h->led.budget_raised(b, !h->need_full && !h->solved && h->initialized))
       h->need_full = true;
-      for (int q = 0; q < B; ++q) h->fresh[q] = 1;
-      h->nfresh = B;
-    }
-    if (h->fresh[b]) {
-      h->fresh[b] = 0;
-      --h->nfresh;
-    }
-  }
   return MHPC_OK;
 }
 int api_set_options(Handle* h, const mhpc_hsddp_option* o) {
@@ -625,9 +614,7 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
     h->pset_of.assign(batch, 0);
   }
   h->pl.assign(batch, ProbLayout{h->desc, 0, 0});
-  h->fresh.assign(batch, 0);
-  h->srb_open.assign(batch, 0);
-  h->cmd_mark.assign(batch, 0);
+  h->led = Ledger(batch);
   h->cmode.assign(batch, desc->mode_seq[0]);
 
   DevBufs& d = h->d;
@@ -701,26 +688,7 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
   return MHPC_OK;
 }
 
-static int x0_row(const Handle* h) {
-  for (const Layout& L : h->plan.lays)
-    if (L.n_wb > 0) return 14;
-  return 6;
-}
-
-// Caller rows src [count][n_s][r] (r = x0_row) of problems [first, first + count) as the device
-// rows of 14: a problem with a whole-body phase has 14 entries, an SRB-only one the first 6 of
-// its row; the rest is zero.  unpad_rows is the way back for rows of one width.
-template <class E>
-static std::vector<E> pad_rows(const Handle* h, int first, int count, int n_s, const double* src) {
-  const int r = x0_row(h);
-  std::vector<E> out((size_t)count * n_s * 14, E(0));
-  for (int b = 0; b < count; ++b) {
-    const int nb = h->plan.lays[h->plan.lid[first + b]].n_wb > 0 ? 14 : 6;
-    for (size_t t = (size_t)b * n_s; t < (size_t)(b + 1) * n_s; ++t)
-      std::copy(src + t * r, src + t * r + nb, out.begin() + t * 14);
-  }
-  return out;
-}
+// The way back from device rows of 14 (pack_rows, mhpc_plan.h) for rows of one width.
 static void unpad_rows(const real* src, size_t rows, int r, double* dst) {
   for (size_t t = 0; t < rows; ++t)
     for (int i = 0; i < r; ++i) dst[t * r + i] = src[t * 14 + i];
@@ -729,7 +697,7 @@ static void unpad_rows(const real* src, size_t rows, int r, double* dst) {
 int api_set_x0(Handle* h, const double* x0) {
   if (!h || !x0) return fail(MHPC_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(h->device));
-  const std::vector<real> pad = pad_rows<real>(h, 0, h->sp.B, 1, x0);
+  const std::vector<real> pad = pack_rows<real>(h->plan, h->sp.B, 1, x0, 0);
   HIPCHK(hipMemcpyAsync(h->d.x0, pad.data(), pad.size() * sizeof(real), hipMemcpyHostToDevice,
                         h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -816,9 +784,7 @@ static int initialize_async(Handle* h) {
   // pays nothing for it
   h->store_valid = false;
   h->need_full = false;
-  std::fill(h->fresh.begin(), h->fresh.end(), 0);
-  h->nfresh = 0;
-  for (int b = 0; b < sp.B; ++b) h->srb_open[b] = no_al_iteration(h->otab.rec[h->otab.of[b]]);
+  h->led.initialized([&](int b) { return no_al_iteration(h->otab.rec[h->otab.of[b]]); });
   return MHPC_OK;
 }
 
@@ -828,13 +794,12 @@ static int initialize_async(Handle* h) {
 // handle, those two call mark_current, and the entry points in between refuse with their own
 // message for the flags they look at.
 static void mark_current(Handle* h) {
-  h->x0_changed = h->params_changed = h->sets_changed = h->cmd_changed = false;
-  std::fill(h->cmd_mark.begin(), h->cmd_mark.end(), 0);
-  h->ncmd = 0;
+  h->x0_changed = h->params_changed = h->sets_changed = false;
+  h->led.all_current();
   h->solved = false;
 }
 // commands or constraint parameters pending (sets_changed is only ever raised with params_changed)
-static bool pending(const Handle* h) { return h->cmd_changed || h->params_changed; }
+static bool pending(const Handle* h) { return h->led.cmd_pending() || h->params_changed; }
 static const char* const kCmdPending =
     "commands changed: call mhpc_initialize or mhpc_update_problem first";
 static const char* const kParamsPending =
@@ -872,23 +837,22 @@ struct SolveBlock {
   DevBufs d;
   hipStream_t s1, s2, s3;
   hipEvent_t fork, join, pfork, pjoin;
-  // OP_FULL with fresh problems in the batch (Handle::fresh): the block's problems split into
+  // OP_FULL with fresh problems in the batch (Ledger::fresh): the block's problems split into
   // the rolled-out ones (spf) and the fresh ones (spc, k_cost), both over Handle::dsplit
   bool mixed = false;
   SolveParams spf, spc;
 };
-// What one run of the solve schedule covers (solve_async): the whole batch (mhpc_solve) or a list
-// of problems (mhpc_tick_problems).  sp is a copy of the handle's with the scope's go[] ranges and
-// ident (a list: ident = 0, go[] counted over the list), d the handle's arrays with gidx the
-// scope's order on the device; the launch variants and ro_store follow the scope's problem count
-// through this copy, never through Handle::sp.
+// What one run of the solve schedule (solve_async) or of the batch's init kernels covers: the whole
+// batch (mhpc_solve) or a list of problems (mhpc_tick_problems, mhpc_reset_problems), built by
+// make_scope alone.  sp is a copy of the handle's and d the handle's arrays; the launch variants and
+// ro_store follow the scope's problem count through this copy, never through Handle::sp.
 struct Scope {
   SolveParams sp;
   DevBufs d;
   int n = 0;           // problems of the scope
   ScopeCaps caps;      // the largest iteration caps among them (scope_caps, mhpc_plan.h)
   bool full = false;   // the first op is the real rollout (a rotated nominal, a new x0)
-  // ... with fresh problems in the scope (Handle::fresh): that op splits into the rolled-out
+  // ... with fresh problems in the scope (Ledger::fresh): that op splits into the rolled-out
   // problems and the fresh ones (k_cost) over ss->split (mhpc_plan.h, solve_scope)
   bool mixed = false;
   const SolveScope* ss = nullptr;
@@ -900,6 +864,27 @@ static void split_block(SolveBlock& k, const SolveScope& ss) {
   k.spf = k.spc = k.sp;
   k.spf.ident = k.spc.ident = 0;
   scope_split(ss, k.sp.go, k.spf.go, k.spc.go);
+}
+// dorder: ss->order on the device -- the scope is that list (ident = 0, go[] counted over it, gidx =
+// dorder); null: the whole batch under the handle's own sp and gidx, where ss (may be null) only
+// gives the split of a mixed first op.
+static Scope make_scope(const Handle* h, const SolveScope* ss, const int* dorder, const ScopeCaps& caps,
+                        bool full) {
+  Scope sc;
+  sc.sp = h->sp;
+  sc.d = h->d;
+  sc.n = h->sp.B;
+  if (dorder) {
+    sc.sp.ident = 0;
+    std::copy(ss->go, ss->go + MAXL + 1, sc.sp.go);
+    sc.d.gidx = dorder;
+    sc.n = ss->size();
+  }
+  sc.caps = caps;
+  sc.full = full;
+  sc.mixed = full && ss && ss->nnf < sc.n;
+  sc.ss = ss;
+  return sc;
 }
 
 // Problems [b0, b0 + sp.B) of the handle's arrays as the kernels index them (b * per-problem
@@ -1028,8 +1013,7 @@ static int solve_async(Handle* h, Scope& sc) {
         // an issue failure may leave launches queued on the second / third stream (the
         // partials fork onto stream3 and join back only at their end): drain both, so no later
         // work on the handle runs unordered with them
-        (void)hipStreamSynchronize(h->stream3);
-        (void)hipStreamSynchronize(h->stream2);
+        drain({h->stream3, h->stream2});
         (void)hipStreamWaitEvent(h->stream, h->evjoin, 0);
         return rc;
       }
@@ -1094,10 +1078,7 @@ static int solve_async(Handle* h, Scope& sc) {
       }
     const hipError_t ej = join_all();
     if (rc) {  // (as above: the blocks' partials streams drained on an issue failure)
-      for (int q = 0; q < nsub; ++q) {
-        (void)hipStreamSynchronize(blk[q].s3);
-        (void)hipStreamSynchronize(blk[q].s2);
-      }
+      for (int q = 0; q < nsub; ++q) drain({blk[q].s3, blk[q].s2});
       return rc;
     }
     HIPCHK(ej);
@@ -1111,18 +1092,9 @@ static int solve_async(Handle* h, Scope& sc) {
 // The scope of the whole batch: the handle's own sp / gidx; the first op the real rollout after an
 // update_problem (need_full), split when a reset left fresh problems (ss: the caller's storage).
 static Scope batch_scope(Handle* h, SolveScope& ss) {
-  Scope sc;
-  sc.sp = h->sp;
-  sc.d = h->d;
-  sc.n = h->sp.B;
-  sc.caps = scope_caps(h->otab, nullptr, 0);
-  sc.full = h->need_full;
-  sc.mixed = h->need_full && h->nfresh > 0;
-  if (sc.mixed) {
-    ss = solve_scope(h->plan, h->plan.gidx, h->fresh);
-    sc.ss = &ss;
-  }
-  return sc;
+  const bool split = h->need_full && h->led.nfresh() > 0;
+  if (split) ss = solve_scope(h->plan, h->plan.gidx, h->led.fresh_flags());
+  return make_scope(h, split ? &ss : nullptr, nullptr, scope_caps(h->otab, nullptr, 0), h->need_full);
 }
 
 // After a scope's solve has drained: its counters (per group, summed over the scope's problems)
@@ -1179,9 +1151,7 @@ int api_solve(Handle* h, int32_t* status) {
   HIPCHK(hipStreamSynchronize(h->stream));
   h->solved = true;
   h->need_full = false;
-  std::fill(h->fresh.begin(), h->fresh.end(), 0);
-  h->nfresh = 0;
-  std::fill(h->srb_open.begin(), h->srb_open.end(), 0);  // (every later first sweep is the real rollout)
+  h->led.solved();
   if ((rc = account_solve(h, sc))) return rc;
   if (status) {
     std::vector<ProbState> st(h->sp.B);
@@ -1339,7 +1309,7 @@ int api_rollout_costs(Handle* h, int n_eps, const double* eps, double* J,
   if (!h || !eps || !J) return fail(MHPC_ERR_INVALID, "null argument");
   if (!h->initialized) return fail(MHPC_ERR_STATE, "not initialized");
   if (n_eps < 1 || n_eps > MHPC_MAX_ROLLOUT_EPS) return fail(MHPC_ERR_INVALID, "n_eps out of range");
-  if (h->cmd_changed) return fail(MHPC_ERR_STATE, kCmdPending);
+  if (h->led.cmd_pending()) return fail(MHPC_ERR_STATE, kCmdPending);
   if (h->sets_changed)
     return fail(MHPC_ERR_STATE,
                 "parameter sets changed: call mhpc_initialize or mhpc_update_problem first");
@@ -1359,7 +1329,7 @@ int api_rollout_costs(Handle* h, int n_eps, const double* eps, double* J,
 // a pending x0 does not matter to the rollouts, which never read the handle's x0.
 static int policy_ready(const Handle* h) {
   if (!h->initialized) return fail(MHPC_ERR_STATE, "not initialized");
-  if (pending(h)) return fail(MHPC_ERR_STATE, h->cmd_changed ? kCmdPending : kParamsPending);
+  if (pending(h)) return fail(MHPC_ERR_STATE, h->led.cmd_pending() ? kCmdPending : kParamsPending);
   return MHPC_OK;
 }
 // Caller rows xs [count][n_s][r] of problems [first, first + count) as the device rows of 14
@@ -1368,9 +1338,9 @@ static int policy_ready(const Handle* h) {
 template <class E>
 static int policy_pack(const Handle* h, int first, int count, int n_s, const double* xs,
                        const char* what, std::vector<E>& out) {
-  for (size_t i = 0; i < (size_t)count * n_s * x0_row(h); ++i)
+  for (size_t i = 0; i < (size_t)count * n_s * x0_row_of(h->plan); ++i)
     if (!std::isfinite(xs[i])) return fail(MHPC_ERR_INVALID, std::string(what) + " must be finite");
-  out = pad_rows<E>(h, first, count, n_s, xs);
+  out = pack_rows<E>(h->plan, count, n_s, xs, first);
   return MHPC_OK;
 }
 static int min_phases(const Handle* h) {
@@ -1401,7 +1371,7 @@ int api_rollout_policy(Handle* h, int n_samples, const double* xs, int n_phases,
                                  dxe, nullptr, h->stream);
   });
   if (t.fetch() != hipSuccess) return dev_fail("mhpc_rollout_policy", t.e);
-  if (x_end) unpad_rows(t.staged(dxe), n, x0_row(h), x_end);
+  if (x_end) unpad_rows(t.staged(dxe), n, x0_row_of(h->plan), x_end);
   return MHPC_OK;
 }
 
@@ -1476,7 +1446,7 @@ int api_get_x0(Handle* h, double* x0) {
   HIPCHK(hipSetDevice(h->device));
   std::vector<real> buf((size_t)h->sp.B * 14);
   D2H(buf.data(), h->d.x0, buf.size() * sizeof(real));
-  unpad_rows(buf.data(), h->sp.B, x0_row(h), x0);
+  unpad_rows(buf.data(), h->sp.B, x0_row_of(h->plan), x0);
   return MHPC_OK;
 }
 
@@ -1547,7 +1517,7 @@ int api_control(Handle* h, const int32_t* step, const double* x, double* u, doub
   if (u && !x) return fail(MHPC_ERR_INVALID, "null x");
   int rc = control_ready(h, step);
   if (rc) return rc;
-  const size_t B = h->sp.B, r = x0_row(h);
+  const size_t B = h->sp.B, r = x0_row_of(h->plan);
   for (size_t i = 0; x && i < B * r; ++i)
     if (!std::isfinite(x[i])) return fail(MHPC_ERR_INVALID, "x must be finite");
   HIPCHK(hipSetDevice(h->device));
@@ -1573,7 +1543,7 @@ int api_control_device(Handle* h, const int32_t* step, const void* x, int64_t ld
   int rc = control_ready(h, step);
   if (rc) return rc;
   if ((rc = check_dev_dtype(dtype))) return rc;
-  const int r = x0_row(h);
+  const int r = x0_row_of(h->plan);
   if (u && (ldx < r || ldu < 4)) return fail(MHPC_ERR_INVALID, "ldx < r or ldu < 4");
   HIPCHK(hipSetDevice(h->device));
   const void* ptrs[] = {u ? x : nullptr, u, x_nom, u_nom, K};
@@ -1593,7 +1563,7 @@ int api_set_x0_device(Handle* h, const void* x0, int64_t ld, int dtype, void* st
   if (!h || !x0) return fail(MHPC_ERR_INVALID, "null argument");
   int rc = check_dev_dtype(dtype);
   if (rc) return rc;
-  if (ld < x0_row(h)) return fail(MHPC_ERR_INVALID, "ld < r");
+  if (ld < x0_row_of(h->plan)) return fail(MHPC_ERR_INVALID, "ld < r");
   HIPCHK(hipSetDevice(h->device));
   if ((rc = check_device_ptr(h, x0, "x0"))) return rc;
   if ((rc = wait_for_caller(h, stream))) return rc;
@@ -1705,11 +1675,8 @@ int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const in
   }
   if ((rc = commit_groups(h, std::move(plan), false, &npl))) return rc;
   h->cmode = ncm;
-  for (int b = 0; b < B; ++b)  // a gait step rotates the nominal: no longer k_init's
-    if (h->fresh[b] && (steps ? steps[b] : 1) > 0) {
-      h->fresh[b] = 0;
-      --h->nfresh;
-    }
+  for (int b = 0; b < B; ++b)
+    if ((steps ? steps[b] : 1) > 0) h->led.stepped(b);
   HIPCHK(launch_reset(h->sp, h->d, h->stream));  // refs from x0, AL/ReB init, nom_slot = 0
   if (own_init_values(h)) HIPCHK(launch_init_params(h->sp, h->d, 0, h->stream));
   HIPCHK(launch_store(h->sp, h->d, h->store, h->nbk, h->spmax, 0, h->stream));
@@ -1744,14 +1711,11 @@ int api_tick_problems(Handle* h, int n, const int32_t* problems, const double* x
     return fail(MHPC_ERR_STATE, "mhpc_solve must precede mhpc_tick_problems (the last batch-wide step was no solve)");
   if (h->params_changed) return fail(MHPC_ERR_STATE, kParamsPending);
   const int B = h->sp.B;
-  if (n < 1 || n > B) return fail(MHPC_ERR_INVALID, "n must be 1..batch");
-  std::vector<char> listed(B, 0);
+  ProblemList listed;
+  PLANCHK(listed.begin, n, B, false);
   bool any_step = false;
   for (int i = 0; i < n; ++i) {
-    const int b = problems[i];
-    if (b < 0 || b >= B) return fail(MHPC_ERR_INVALID, "problem out of range");
-    if (listed[b]) return fail(MHPC_ERR_INVALID, "problem listed twice");
-    listed[b] = 1;
+    PLANCHK(listed.add, problems[i]);
     const int ns = steps ? steps[i] : 1;
     if (ns < 0 || ns > 1024) return fail(MHPC_ERR_INVALID, "steps must be 0..1024");
     any_step = any_step || ns > 0;
@@ -1761,7 +1725,7 @@ int api_tick_problems(Handle* h, int n, const int32_t* problems, const double* x
   if (gaits && (rc = check_gaits(n_gaits, gaits))) return rc;
   for (int i = 0; gaits && gait_of && i < n; ++i)
     if (gait_of[i] < 0 || gait_of[i] >= n_gaits) return fail(MHPC_ERR_INVALID, "gait index out of range");
-  const int r = x0_row(h);
+  const int r = x0_row_of(h->plan);
   for (size_t i = 0; x0 && i < (size_t)n * r; ++i)
     if (!std::isfinite(x0[i])) return fail(MHPC_ERR_INVALID, "x0 must be finite");
   // the listed problems' gait steps on working copies; the arrays stay as they are, so each new
@@ -1786,17 +1750,11 @@ int api_tick_problems(Handle* h, int n, const int32_t* problems, const double* x
   // the scope: the list by its groups after the commit; fresh (mhpc_reset_problems) and no step:
   // the first forward_sweep(0) stays the cost evaluation
   std::vector<char> fr(B, 0);
-  for (int i = 0; i < n; ++i) fr[problems[i]] = h->fresh[problems[i]] && (steps ? steps[i] : 1) == 0;
+  for (int i = 0; i < n; ++i) fr[problems[i]] = h->led.fresh(problems[i]) && (steps ? steps[i] : 1) == 0;
   const std::vector<int> list(problems, problems + n);
   const SolveScope ss = solve_scope(np, list, fr);
-  std::vector<real> rows;
-  if (x0) {  // in list order, padded as mhpc_set_x0 pads them
-    rows.assign((size_t)n * 14, real(0));
-    for (int i = 0; i < n; ++i) {
-      const int nb = h->pl[problems[i]].desc.n_wb > 0 ? 14 : 6;
-      std::copy(x0 + (size_t)i * r, x0 + (size_t)i * r + nb, rows.begin() + (size_t)i * 14);
-    }
-  }
+  std::vector<real> rows;  // in list order, padded as mhpc_set_x0 pads them (the plan before the commit)
+  if (x0) rows = pack_rows<real>(h->plan, n, 1, x0, 0, problems);
   // ---- nothing of the handle or the device has changed up to here ----
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1823,17 +1781,7 @@ int api_tick_problems(Handle* h, int n, const int32_t* problems, const double* x
       if (int rc = commit_groups(h, std::move(plan), true, &npl)) return rc;
       for (int i = 0; i < n; ++i) h->cmode[problems[i]] = ncm[problems[i]];
     }
-    Scope sc;
-    sc.sp = h->sp;
-    sc.sp.ident = 0;
-    std::copy(ss.go, ss.go + MAXL + 1, sc.sp.go);
-    sc.d = h->d;
-    sc.d.gidx = dorder;
-    sc.n = n;
-    sc.caps = scope_caps(h->otab, list.data(), n);
-    sc.full = true;
-    sc.mixed = ss.nnf < n;
-    sc.ss = &ss;
+    Scope sc = make_scope(h, &ss, dorder, scope_caps(h->otab, list.data(), n), true);
     HIPCHK(launch_reset(sc.sp, sc.d, h->stream));  // refs from x0 and the command, AL/ReB init, nom_slot = 0
     if (own_init_values(h)) HIPCHK(launch_init_params(sc.sp, sc.d, 0, h->stream));
     HIPCHK(launch_store_list(h->sp, h->d, n, dlist, h->store, h->nbk, h->spmax, 0, h->stream));
@@ -1853,24 +1801,8 @@ int api_tick_problems(Handle* h, int n, const int32_t* problems, const double* x
   rc = run();
   // the listed problems have their references and their solve, whatever came of it: no longer
   // fresh, no command pending
-  for (int i = 0; i < n; ++i) {
-    const int b = problems[i];
-    if (h->fresh[b]) {
-      h->fresh[b] = 0;
-      --h->nfresh;
-    }
-    h->srb_open[b] = 0;
-    if (h->cmd_mark[b]) {
-      h->cmd_mark[b] = 0;
-      --h->ncmd;
-    }
-  }
-  h->cmd_changed = h->ncmd > 0;
-  if (rc) {
-    const std::string why = mhpc_g_err;
-    for (hipStream_t q : {h->stream3, h->stream2, h->stream}) (void)hipStreamSynchronize(q);
-    mhpc_g_err = why;
-  }
+  h->led.ticked(n, problems);
+  if (rc) drain({h->stream3, h->stream2, h->stream});
   return rc;
 }
 
@@ -1914,26 +1846,20 @@ int api_set_layouts(Handle* h, int n_desc, const mhpc_problem_desc* descs, const
   return MHPC_OK;
 }
 
-// The device half of mhpc_reset_problems: `order` is the listed problems by group (then problem
-// number), rows their padded x0 rows in that order (empty: the device rows stay).  The list-driven
-// memory_reset runs on the second stream beside the warm start, as in initialize_async; k_init
-// and k_init_params are the batch's own kernels over a restricted SolveParams (go[] over the
-// list, gidx = the list).  Every launch counts as k_init under profiling.
-static int reset_launches(Handle* h, const std::vector<int>& order, std::vector<real>&& rows) {
-  const int n = (int)order.size();
-  SolveParams rs = h->sp;
-  rs.ident = 0;
-  for (int g = 0; g <= rs.ngrp; ++g) rs.go[g] = 0;
-  for (int b : order) ++rs.go[h->plan.lid[b] + 1];
-  for (int g = 0; g < rs.ngrp; ++g) rs.go[g + 1] += rs.go[g];
+// The device half of mhpc_reset_problems: ss is the scope of the listed problems (its order: by
+// group, then problem number), rows their padded x0 rows in that order (empty: the device rows
+// stay).  The list-driven memory_reset runs on the second stream beside the warm start, as in
+// initialize_async; k_init and k_init_params are the batch's own kernels over the scope's
+// restricted parameters (make_scope).  Every launch counts as k_init under profiling.
+static int reset_launches(Handle* h, const SolveScope& ss, std::vector<real>&& rows) {
+  const int n = ss.size();
   DevTemp<int> ti(h->stream);
   DevTemp<real> tr(h->stream);
-  const int* dlist = ti.in(std::vector<int>(order));
+  const int* dlist = ti.in(std::vector<int>(ss.order));
   const real* drows = rows.empty() ? nullptr : tr.in(std::move(rows));
   if (ti.e != hipSuccess) return dev_fail("mhpc_reset_problems", ti.e);
   if (tr.e != hipSuccess) return dev_fail("mhpc_reset_problems", tr.e);
-  DevBufs rd = h->d;
-  rd.gidx = dlist;
+  const Scope rs = make_scope(h, &ss, dlist, ScopeCaps(), false);
   HIPCHK(hipEventRecord(h->evfork, h->stream));
   HIPCHK(hipStreamWaitEvent(h->stream2, h->evfork, 0));
   LAUNCH_ON(h, K_INIT, h->stream2,
@@ -1941,9 +1867,9 @@ static int reset_launches(Handle* h, const std::vector<int>& order, std::vector<
                               h->spmax, h->stream2));
   HIPCHK(hipEventRecord(h->evjoin, h->stream2));
   if (drows) LAUNCH(h, K_INIT, launch_scatter_x0(h->d, n, dlist, drows, h->stream));
-  LAUNCH(h, K_INIT, launch_init(rs, rd, h->stream));
+  LAUNCH(h, K_INIT, launch_init(rs.sp, rs.d, h->stream));
   // (k_init wrote the AL / ReB initial values of problem 0's set)
-  if (own_init_values(h)) LAUNCH(h, K_INIT, launch_init_params(rs, rd, 1, h->stream));
+  if (own_init_values(h)) LAUNCH(h, K_INIT, launch_init_params(rs.sp, rs.d, 1, h->stream));
   HIPCHK(hipStreamWaitEvent(h->stream, h->evjoin, 0));
   HIPCHK(hipStreamSynchronize(h->stream));
   return MHPC_OK;
@@ -1960,21 +1886,16 @@ int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* 
   if (!h || !problems) return fail(MHPC_ERR_INVALID, "null argument");
   if (!h->initialized) return fail(MHPC_ERR_STATE, "mhpc_initialize must precede mhpc_reset_problems");
   const int B = h->sp.B;
-  if (n < 1 || n > B) return fail(MHPC_ERR_INVALID, "n must be 1..batch");
-  std::vector<int> at(B, -1);  // a listed problem's place in the list
-  for (int i = 0; i < n; ++i) {
-    const int b = problems[i];
-    if (b < 0 || b >= B) return fail(MHPC_ERR_INVALID, "problem out of range");
-    if (at[b] >= 0) return fail(MHPC_ERR_INVALID, "problem listed twice");
-    at[b] = i;
-  }
+  ProblemList listed;  // (listed.at: a listed problem's place in the list)
+  PLANCHK(listed.begin, n, B, false);
+  for (int i = 0; i < n; ++i) PLANCHK(listed.add, problems[i]);
   if (!descs && n_desc != 0) return fail(MHPC_ERR_INVALID, "n_desc without descriptors");
   if (descs && (n_desc < 1 || n_desc > MAXL))
     return fail(MHPC_ERR_INVALID, "n_desc must be 1..MHPC_MAX_LAYOUTS");
   for (int i = 0; i < n_desc; ++i) PLANCHK(check_layout_desc, descs[i], h->desc);
   for (int i = 0; descs && desc_of && i < n; ++i)
     if (desc_of[i] < 0 || desc_of[i] >= n_desc) return fail(MHPC_ERR_INVALID, "layout index out of range");
-  const int r = x0_row(h);
+  const int r = x0_row_of(h->plan);
   std::vector<ProbLayout> npl = h->pl;
   for (int i = 0; i < n; ++i) {
     ProbLayout& q = npl[problems[i]];
@@ -1990,31 +1911,18 @@ int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* 
   PLANCHK(plan_groups, npl, h->pset_of, plan);  // too many groups: nothing changed
   int rc = commit_groups(h, std::move(plan), true, &npl);
   if (rc) return rc;
-  std::vector<int> order(problems, problems + n);
-  std::sort(order.begin(), order.end(), [&](int a, int c) {
-    return h->plan.lid[a] != h->plan.lid[c] ? h->plan.lid[a] < h->plan.lid[c] : a < c;
-  });
+  // the listed problems by group under the new plan, their x0 rows in that order
+  const SolveScope ss = solve_scope(h->plan, std::vector<int>(problems, problems + n), {});
   std::vector<real> rows;
-  if (x0) {
-    rows.assign((size_t)n * 14, real(0));
-    for (int j = 0; j < n; ++j) {
-      const int b = order[j], nb = h->pl[b].desc.n_wb > 0 ? 14 : 6;
-      std::copy(x0 + (size_t)at[b] * r, x0 + (size_t)at[b] * r + nb, rows.begin() + (size_t)j * 14);
-    }
-  }
-  for (int b : order) {
+  if (x0) rows = pack_rows<real>(h->plan, n, 1, x0, 0, ss.order.data(), listed.at.data());
+  for (int b : ss.order) {
     h->cmode[b] = h->pl[b].desc.mode_seq[0];
     h->kbytes[K_INIT] += h->plan.bym[h->plan.lid[b]].init + (own_init_values(h) ? 4 * MAXP * kB : 0.0);
-    if (!h->fresh[b]) {
-      h->fresh[b] = 1;
-      ++h->nfresh;
-    }
-    h->srb_open[b] = no_al_iteration(h->otab.rec[h->otab.of[b]]);
+    h->led.reset(b, no_al_iteration(h->otab.rec[h->otab.of[b]]));
   }
-  rc = reset_launches(h, order, std::move(rows));
+  rc = reset_launches(h, ss, std::move(rows));
   if (rc) {  // nothing of the handle's may stay queued behind a failed launch
-    (void)hipStreamSynchronize(h->stream2);
-    (void)hipStreamSynchronize(h->stream);
+    drain({h->stream2, h->stream});
     return rc;
   }
   return collect_profile(h);
@@ -2038,16 +1946,14 @@ static CopySide copy_side(const Handle* h) {
 int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp_, int n, float* ms) {
   if (!d || !s || !dp || !sp_) return fail(MHPC_ERR_INVALID, "null argument");
   const int Bd = d->sp.B, Bs = s->sp.B;
-  if (n < 1 || n > Bd) return fail(MHPC_ERR_INVALID, "n must be 1..batch of the destination");
-  std::vector<char> is_dst(Bd, 0);
-  for (int i = 0; i < n; ++i) {
-    if (dp[i] < 0 || dp[i] >= Bd || sp_[i] < 0 || sp_[i] >= Bs)
-      return fail(MHPC_ERR_INVALID, "problem out of range");
-    if (is_dst[dp[i]]) return fail(MHPC_ERR_INVALID, "destination problem listed twice");
-    is_dst[dp[i]] = 1;
+  ProblemList dst;
+  PLANCHK(dst.begin, n, Bd, true);
+  for (int i = 0; i < n; ++i) {  // (an entry's ranges, source and destination, before "twice")
+    if (sp_[i] < 0 || sp_[i] >= Bs) return fail(MHPC_ERR_INVALID, "problem out of range");
+    PLANCHK(dst.add, dp[i]);
   }
   for (int i = 0; d == s && i < n; ++i)
-    if (is_dst[sp_[i]])
+    if (dst.at[sp_[i]] >= 0)
       return fail(MHPC_ERR_INVALID, "a problem is both a source and a destination");
   if (d->device != s->device) return fail(MHPC_ERR_INVALID, "the handles are on different devices");
   // the line-search grid (alpha, nslot: the arrays' shape) is the handle's; a source problem's
@@ -2066,8 +1972,8 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
   if ((d->sweep_bits == 32) != (s->sweep_bits == 32))
     return fail(MHPC_ERR_INVALID, "the handles' backward-sweep arithmetic (MHPC_VARIANT_SWEEP_BITS) differs");
   // the destination's arrays stay as they are: every source layout must fit them
-  const int r = x0_row(d);
-  if (x0_row(s) != r) return fail(MHPC_ERR_INVALID, "the handles' x0 row widths differ");
+  const int r = x0_row_of(d->plan);
+  if (x0_row_of(s->plan) != r) return fail(MHPC_ERR_INVALID, "the handles' x0 row widths differ");
   std::vector<ProbLayout> npl = d->pl;
   std::vector<CostParams> nsets = d->psets;
   std::vector<int> nof = d->pset_of;
@@ -2125,7 +2031,7 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
   }
   if (t.e == hipSuccess) t.e = hipEventRecord(d->ev0, d->stream);
   if (t.e != hipSuccess) {  // nothing of the copy is queued yet
-    (void)hipStreamSynchronize(d->stream);
+    drain({d->stream});
     (void)commit_groups(d, std::move(plan), true, &npl, &nsets, &nof);
     return dev_fail("mhpc_copy_problems", t.e);
   }
@@ -2135,9 +2041,7 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
     d->cmode[b] = s->cmode[a];
     d->cmd[2 * (size_t)b] = s->cmd[2 * (size_t)a];
     d->cmd[2 * (size_t)b + 1] = s->cmd[2 * (size_t)a + 1];
-    d->nfresh += (s->fresh[a] ? 1 : 0) - (d->fresh[b] ? 1 : 0);
-    d->fresh[b] = s->fresh[a];
-    d->srb_open[b] = s->srb_open[a];
+    d->led.copied(b, s->led, a);
   }
   t.e = launch_copy_problems(cs, cd, n, dpairs, nblk, dpairs + 2 * (size_t)n, d->stream);
   // the option index of the destinations (their rewritten option fields came with the state)
@@ -2149,7 +2053,7 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
   if (t.e != hipSuccess) {
     // a failed launch: the destination problems are undefined (as after a failed reset); nothing
     // of the handle's may stay queued behind it
-    (void)hipStreamSynchronize(d->stream);
+    drain({d->stream});
     return dev_fail("mhpc_copy_problems", t.e);
   }
   // the host table follows the device index once the launches have succeeded (a record the
@@ -2160,9 +2064,7 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
     ++d->otab.use[nslot_of[i]];
     d->otab.of[b] = nslot_of[i];
   }
-  const OptRec r0 = option_record(d->otab.rec[d->otab.of[0]]);
-  d->sp.update_penalty = r0.update_penalty;
-  d->sp.ReB_active = r0.ReB_active;
+  mirror_option0(d);
   if (ms) *ms = el;
   return MHPC_OK;
 }
@@ -2178,7 +2080,7 @@ int api_get_problem_desc(Handle* h, int b, mhpc_problem_desc* desc) {
 
 // Per-problem user commands (the batch axis over MHPCUserParameters::usrcmd).  New values reach
 // the references at the next mhpc_initialize / mhpc_update_problem(s); until then an
-// initialised handle refuses to solve (cmd_changed).
+// initialised handle refuses to solve (the ledger's command marks).
 int api_set_commands(Handle* h, const double* vel, const double* height) {
   if (!h) return fail(MHPC_ERR_INVALID, "null handle");
   const size_t B = h->sp.B;
@@ -2198,11 +2100,7 @@ int api_set_commands(Handle* h, const double* vel, const double* height) {
   HIPCHK(hipStreamSynchronize(h->stream));
   if (h->initialized) {  // the problems whose value changed: pending until their next references
     for (size_t b = 0; b < B; ++b)
-      if ((nc[2 * b] != h->cmd[2 * b] || nc[2 * b + 1] != h->cmd[2 * b + 1]) && !h->cmd_mark[b]) {
-        h->cmd_mark[b] = 1;
-        ++h->ncmd;
-      }
-    h->cmd_changed = h->ncmd > 0;
+      if (nc[2 * b] != h->cmd[2 * b] || nc[2 * b + 1] != h->cmd[2 * b + 1]) h->led.command_changed((int)b);
   }
   h->cmd = nc;
   return MHPC_OK;
