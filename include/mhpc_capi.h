@@ -38,6 +38,10 @@
  *                        fleet (MHPCLocomotion.cpp:47-53): the listed problems only
  *   mhpc_copy_problems   copy construction / assignment of a controller object (every member of
  *                        MHPCLocomotion and its MultiPhaseDDP): problems copied between slots
+ *   mhpc_snapshot_problems / mhpc_restore_problems   nothing: the reference's controller is an
+ *                        object in one process.  Here the same copy, serialised: live problems to
+ *                        a blob of plain bytes and back into any handle, in any process
+ *                        (mhpc_snapshot_size, _info, _entry, _status read sizes and entries)
  *   mhpc_tick_problems   set_initial_condition + update_problem + solve_mhpc of single controllers
  *                        of the fleet (MHPCLocomotion.cpp:107-158,167-195), each when its own gait
  *                        mode ends: the listed problems only; mhpc_reserve_knots the room that
@@ -354,6 +358,89 @@ int mhpc_reserve_knots(mhpc_handle* h, int knots);
  *  - Device work is proportional to n, not to either batch. */
 int mhpc_copy_problems(mhpc_handle* dst, const int32_t* dst_problems, mhpc_handle* src,
                        const int32_t* src_problems, int n, float* ms);
+/* ---- snapshots of live problems: the batch axis over controller lifetimes across processes ----
+ * mhpc_copy_problems ends at the process boundary: both handles alive, one process, one device.
+ * A snapshot is the serialised form of the same object: the listed problems, as they stand at the
+ * call, as plain bytes in a host buffer of the caller's (pageable or pinned) -- no pointers,
+ * device indices or handle addresses in it --, to be written to a file, sent to another rank or
+ * kept for a replay; mhpc_restore_problems makes problems of any handle that could have been the
+ * destination of that copy (this one later, one in another process, on another device) become
+ * entries of the blob.
+ *  - Contract: a restore is the mhpc_copy_problems the caller could have made at the moment of
+ *    the snapshot, had the source handle still been there.  Everything that travels with the copy
+ *    travels (see above: every slot, K / du / G, partials, impact Jacobians, solver state, x0 row,
+ *    references, layout with rotation and gait point, store rows, command, parameter set, option
+ *    record, the ledger's per-problem marks).  Afterwards every getter reports for the destination
+ *    what it reported for the source at the snapshot, every later mhpc_solve /
+ *    mhpc_update_problem(s) / mhpc_tick_problems / mhpc_advance_x0 / mhpc_control of it equals the
+ *    source's under the same inputs bit for bit in both precisions, every unlisted problem of the
+ *    destination keeps its device state bit for bit, and the destination's arrays are never
+ *    re-strided or reallocated (tests/test_gpu_snapshot.py).  The source keeps its device and host
+ *    state bit for bit.
+ *  - Blob: header | entry table | payload (mhpc_snapshot_map.h).  The payload's knot
+ *    stride is the largest knot count among the listed problems' layouts, not the handle's: a
+ *    robot taken out of a handle with a large mhpc_reserve_knots does not carry the reservation.
+ *    Store rows travel with the source's store shape, or with none.  Two snapshots of the same
+ *    unchanged problems are byte-identical.  MHPC_SNAPSHOT_VERSION names the format; a blob is
+ *    read only by the version, precision and record sizes that wrote it.
+ *  - mhpc_snapshot_size: the exact blob size for these problems.  mhpc_snapshot_problems: bytes
+ *    must be at least that; exactly that many are written.  problems: n distinct numbers,
+ *    1 <= n <= batch.  ms optional: device time of the pack launches (HIP events).
+ *  - mhpc_snapshot_info / _entry / _status work on host memory alone: no handle, no GPU.  entry i's
+ *    descriptor carries its command; option, weights, constraints are its records by value;
+ *    mhpc_snapshot_status gives the mhpc_solve_status of entries [first, first + count) as their
+ *    last solve left it (status [count], read from the solver state in the payload).  Any output pointer of mhpc_snapshot_entry may be NULL.  With them a caller sizes
+ *    and configures a handle for the blob (MHPCLocomotion::from_snapshot does).
+ *  - mhpc_restore_problems: destination problem dst_problems[i] becomes blob entry entries[i]
+ *    (entries == NULL: entry i); an entry may repeat (one to many).  ms optional: device time of
+ *    the unpack launches.
+ *  - Refusals are the copy's, checked before anything changes, MHPC_ERR_INVALID: another
+ *    precision, alpha / slot count, sweep arithmetic or x0 row width; a layout that does not fit
+ *    the destination's knot stride or store; an option record that is none of the destination's;
+ *    more than MHPC_MAX_LAYOUTS groups; a destination listed twice; an entry out of range.
+ *    MHPC_ERR_STATE: the handle not initialised; commands or parameters pending (on the source at
+ *    the snapshot, on the destination at the restore).
+ *  - Call-order point: the blob records the source's (just initialised / updated / solved).  A
+ *    restore that lists every problem of the destination makes the destination adopt it -- resume
+ *    from a checkpoint into a handle that was only created and initialised.  A partial restore
+ *    requires equal points, as the copy does (MHPC_ERR_STATE).
+ *  - Blob validation, MHPC_ERR_INVALID with the cause in mhpc_last_error: a buffer too small or a
+ *    length that does not match the header; a wrong magic; another format version; a build whose
+ *    sizeof(ProbState), sizeof(BwsCarry), element size or record widths differ from the header's;
+ *    a header / entry-table checksum mismatch.
+ *  - Device work and staging memory are proportional to n, never to the batch.  A list whose
+ *    payload exceeds the staging cap runs in rounds of R problems through two staging buffers on
+ *    the handle's two streams: packing round i + 1 overlaps the device-to-host copy of round i,
+ *    and the reverse for a restore.  mhpc_set_kernel_variant(h, MHPC_VARIANT_SNAP_ROUND, R) forces
+ *    R.  After an error inside a round nothing more is queued and the handle's streams are
+ *    drained; a failed restore leaves the destination problems undefined, as a failed copy does. */
+#define MHPC_SNAPSHOT_VERSION 1
+/* (a struct tag, not a typedef: the reader below has the same name, as stat has) */
+struct mhpc_snapshot_info {
+  int32_t version;        /* MHPC_SNAPSHOT_VERSION of the writer */
+  int32_t n_entries;
+  int32_t precision;      /* 64 / 32 */
+  int32_t sweep_bits;     /* 64 / 32: arithmetic of the source's backward sweep */
+  int32_t x0_row;         /* 14 / 6: the source's x0 row width */
+  int32_t n_slots;        /* trajectory slots of the line-search grid (follows alpha) */
+  int32_t knot_stride;    /* of the payload: the longest listed layout */
+  int32_t store_knots;    /* store shape: knots a buffer, */
+  int32_t store_buffers;  /*   buffers a problem (0: no store rows travel) */
+  int32_t need_full;      /* the source's call-order point: next solve starts with a rollout, */
+  int32_t solved;         /*   last batch-wide step was a solve */
+  int32_t reserved;
+  double alpha;
+  int64_t payload_bytes_per_entry;
+  int64_t total_bytes;
+};
+int mhpc_snapshot_size(mhpc_handle* h, int n, const int32_t* problems, int64_t* bytes);
+int mhpc_snapshot_problems(mhpc_handle* h, int n, const int32_t* problems, void* blob,
+                           int64_t bytes, float* ms);
+int mhpc_snapshot_info(const void* blob, int64_t bytes, struct mhpc_snapshot_info* info);
+int mhpc_restore_problems(mhpc_handle* h, int n, const int32_t* dst_problems, const void* blob,
+                          int64_t bytes, const int32_t* entries, float* ms);
+int mhpc_snapshot_status(const void* blob, int64_t bytes, int first, int count, int32_t* status);
+
 /* ---- per-problem user commands: the batch axis over speed / height commands -----------
  * Per-problem user command (the reference's MHPCUserParameters::usrcmd of each controller,
  * MHPCLocomotion.cpp:98-103).  vel, height: host arrays [batch]; either may be NULL = unchanged.
@@ -423,6 +510,11 @@ int mhpc_set_cost_weights(mhpc_handle* h, const mhpc_cost_weights* w);
 int mhpc_get_cost_weights(mhpc_handle* h, mhpc_cost_weights* w);
 int mhpc_set_constraint_params(mhpc_handle* h, const mhpc_constraint_params* c);
 int mhpc_get_constraint_params(mhpc_handle* h, mhpc_constraint_params* c);
+/* Entry `entry` of a snapshot blob (see "snapshots of live problems" above; host memory only):
+ * its descriptor with its command, option record and parameter values; any of them may be NULL. */
+int mhpc_snapshot_entry(const void* blob, int64_t bytes, int entry, mhpc_problem_desc* desc,
+                        mhpc_hsddp_option* option, mhpc_cost_weights* weights,
+                        mhpc_constraint_params* constraints);
 
 /* ---- per-problem parameter sets: the batch axis over weights and constraint parameters --
  * In the reference every MHPCLocomotion owns its WBCost / FBCost / WBConstraint objects
@@ -699,6 +791,10 @@ void mhpc_destroy(mhpc_handle* h);
                                          no faster -- within 1 % of the double sweep -- and 10-70x
                                          larger typical error vs the fp64 oracle, DESIGN.md §3,
                                          §5); 0 = default */
+#define MHPC_VARIANT_SNAP_ROUND 6     /* which: problems a round of mhpc_snapshot_problems /
+                                         mhpc_restore_problems (variant = R >= 1; 0 = as many as
+                                         fit the staging cap); any R gives the same blob and the
+                                         same restore, byte for byte */
 int mhpc_set_kernel_variant(mhpc_handle* h, int which, int variant);
 
 /* ---- batched model evaluation on the device (kernel-level parity hooks) -----------

@@ -21,9 +21,11 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <iterator>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -402,6 +404,118 @@ class MHPCLocomotion {
     refresh_descs();
     return ms;
   }
+  // extension: snapshots -- the copy above, serialised (mhpc_snapshot_problems).  The listed
+  // problems (empty: all) as they stand, as a blob of plain bytes that restore_problems /
+  // from_snapshot turn back into live problems of this or any other fleet, in any process.
+  std::vector<uint8_t> snapshot_problems(const std::vector<int>& problems = {}, float* ms = nullptr) {
+    std::vector<int32_t> pr(problems.begin(), problems.end());
+    if (pr.empty())
+      for (int b = 0; b < batch_; ++b) pr.push_back(b);
+    int64_t bytes = 0;
+    check(mhpc_snapshot_size(h_, (int)pr.size(), pr.data(), &bytes), "mhpc_snapshot_size");
+    std::vector<uint8_t> blob((size_t)bytes);
+    check(mhpc_snapshot_problems(h_, (int)pr.size(), pr.data(), blob.data(), bytes, ms),
+          "mhpc_snapshot_problems");
+    return blob;
+  }
+  // problem dst_problems[i] becomes entry entries[i] of the blob (empty: entry i); an entry may
+  // repeat.  A restore that lists every problem also adopts the blob's point of the call order.
+  // Returns the device time of the unpack launches in ms.
+  float restore_problems(const std::vector<int>& dst_problems, const std::vector<uint8_t>& blob,
+                         const std::vector<int>& entries = {}) {
+    if (!entries.empty() && entries.size() != dst_problems.size())
+      throw std::runtime_error("restore_problems: one blob entry per destination problem");
+    const std::vector<int32_t> dp(dst_problems.begin(), dst_problems.end());
+    const std::vector<int32_t> en(entries.begin(), entries.end());
+    float ms = 0;
+    check(mhpc_restore_problems(h_, (int)dp.size(), dp.data(), blob.data(), (int64_t)blob.size(),
+                                en.empty() ? nullptr : en.data(), &ms),
+          "mhpc_restore_problems");
+    const std::vector<double> rows = get_x0();  // what update_problem(s) hands back
+    status_.resize(batch_, 0);
+    for (size_t i = 0; i < dp.size(); ++i) {
+      std::copy(rows.begin() + (size_t)dp[i] * xw_, rows.begin() + (size_t)(dp[i] + 1) * xw_,
+                x0_.begin() + (size_t)dp[i] * xw_);
+      check(mhpc_snapshot_status(blob.data(), (int64_t)blob.size(), en.empty() ? (int)i : en[i], 1,
+                                 &status_[dp[i]]),
+            "mhpc_snapshot_status");
+    }
+    refresh_descs();
+    _option = get_options();
+    return ms;
+  }
+  static struct mhpc_snapshot_info snapshot_info(const std::vector<uint8_t>& blob) {
+    struct mhpc_snapshot_info info;
+    check(::mhpc_snapshot_info(blob.data(), (int64_t)blob.size(), &info), "mhpc_snapshot_info");
+    return info;
+  }
+  struct SnapshotEntry {
+    mhpc_problem_desc desc;  // with the entry's command
+    mhpc_hsddp_option option;
+    mhpc_cost_weights weights;
+    mhpc_constraint_params constraints;
+  };
+  static SnapshotEntry snapshot_entry(const std::vector<uint8_t>& blob, int i) {
+    SnapshotEntry e;
+    check(mhpc_snapshot_entry(blob.data(), (int64_t)blob.size(), i, &e.desc, &e.option, &e.weights,
+                              &e.constraints),
+          "mhpc_snapshot_entry");
+    return e;
+  }
+  // A fleet that can hold the blob and holds it: the entries' descriptors (set_layouts), their
+  // longest layout as reserve_knots, the blob's alpha, precision and sweep arithmetic, the distinct
+  // option records (set_option_sets); initialised, every entry restored into problems 0..n-1.
+  // batch 0: the entry count, so the fleet resumes at the blob's point of the call order.  gait:
+  // what update_problem() steps with (a blob holds gait points, not gaits).
+  static std::unique_ptr<MHPCLocomotion> from_snapshot(const std::vector<uint8_t>& blob, Gait* gait,
+                                                       int device = 0, int batch = 0) {
+    const struct mhpc_snapshot_info info = snapshot_info(blob);
+    const int n = info.n_entries, B = batch > 0 ? batch : n;
+    if (B < n) throw std::runtime_error("from_snapshot: batch smaller than the blob's entry count");
+    std::vector<mhpc_problem_desc> descs;
+    std::vector<mhpc_hsddp_option> opts;
+    std::vector<int32_t> lop(B, 0), oop(B, 0);
+    for (int i = 0; i < n; ++i) {
+      SnapshotEntry e = snapshot_entry(blob, i);
+      if (i > 0) {  // one handle-wide command in the descriptors: the entries' own travel with them
+        e.desc.vel_cmd = descs[0].vel_cmd;
+        e.desc.height_cmd = descs[0].height_cmd;
+      }
+      size_t k = 0;
+      while (k < descs.size() && std::memcmp(&descs[k], &e.desc, sizeof e.desc) != 0) ++k;
+      if (k == descs.size()) descs.push_back(e.desc);
+      lop[i] = (int32_t)k;
+      for (k = 0; k < opts.size() && std::memcmp(&opts[k], &e.option, sizeof e.option) != 0;) ++k;
+      if (k == opts.size()) opts.push_back(e.option);
+      oop[i] = (int32_t)k;
+    }
+    std::unique_ptr<MHPCLocomotion> f(new MHPCLocomotion(descs[0], opts[0], gait, B, device));
+    if (info.sweep_bits == 32)
+      check(mhpc_set_kernel_variant(f->h_, MHPC_VARIANT_SWEEP_BITS, 32), "mhpc_set_kernel_variant");
+    if (descs.size() > 1) f->set_layouts(descs, lop);
+    f->reserve_knots(info.knot_stride);
+    if (opts.size() > 1) {
+      check(mhpc_set_option_sets(f->h_, (int)opts.size(), opts.data(), oop.data()), "mhpc_set_option_sets");
+      f->_option = f->get_options();
+    }
+    f->initialization();
+    std::vector<int> all(n);
+    for (int i = 0; i < n; ++i) all[i] = i;
+    f->restore_problems(all, blob);
+    return f;
+  }
+  // thin file helpers over the two
+  void save_problems(const std::string& path, const std::vector<int>& problems = {}) {
+    const std::vector<uint8_t> blob = snapshot_problems(problems);
+    std::ofstream f(path, std::ios::binary);
+    f.write((const char*)blob.data(), (std::streamsize)blob.size());
+    if (!f) throw std::runtime_error("save_problems: cannot write " + path);
+  }
+  static std::vector<uint8_t> load_snapshot(const std::string& path) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("load_snapshot: cannot read " + path);
+    return std::vector<uint8_t>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  }
   // problems whose last solve did not end MHPC_SOLVE_OK or left a non-finite cost
   std::vector<int> lost_problems() {
     std::vector<double> J(batch_);
@@ -763,6 +877,19 @@ class MHPCLocomotion {
   HSDDP_OPTION<TH> _option;
 
  private:
+  // from_snapshot: a fleet of a given descriptor and option record
+  MHPCLocomotion(const mhpc_problem_desc& desc, const mhpc_hsddp_option& opt, Gait* gait, int batch,
+                 int device)
+      : batch_(batch), desc_(desc), opt_(opt) {
+    check(mhpc_create(&desc_, &opt_, batch_, device, &h_), "mhpc_create");
+    _option = option_from_c(opt_);
+    _n_phases = desc_.n_wb + desc_.n_fb;
+    gait_ = gait->to_c();
+    xw_ = desc_.n_wb > 0 ? 14 : 6;
+    pmax_ = _n_phases;
+    refresh_phases(false);
+    default_x0();
+  }
   // every problem's layout (kept only when they differ), the x0 row width, the widest
   // phase count (the row width of mhpc_get_scalars' per-phase arrays)
   void refresh_descs() {

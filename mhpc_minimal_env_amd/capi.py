@@ -39,6 +39,8 @@ MHPC_VARIANT_SUBBATCH = 3
 MHPC_MAX_SUBBATCH = 4
 MHPC_VARIANT_RO_STORE = 4  # line-search trials storing their records (0 = default)
 MHPC_VARIANT_SWEEP_BITS = 5  # backward-sweep arithmetic: 64 double (default) / 32 float (fp32)
+MHPC_VARIANT_SNAP_ROUND = 6  # problems a round of snapshot / restore (0 = by the staging cap)
+MHPC_SNAPSHOT_VERSION = 1
 # element type of a caller's device array (mhpc_control_device, mhpc_set_x0_device)
 MHPC_DEV_F64 = 0
 MHPC_DEV_F32 = 1
@@ -178,6 +180,21 @@ class Counters(ctypes.Structure):
     ]
 
 
+class SnapshotInfo(ctypes.Structure):
+    """struct mhpc_snapshot_info: what a snapshot blob's header says."""
+    _fields_ = [
+        ("version", ctypes.c_int32), ("n_entries", ctypes.c_int32), ("precision", ctypes.c_int32),
+        ("sweep_bits", ctypes.c_int32), ("x0_row", ctypes.c_int32), ("n_slots", ctypes.c_int32),
+        ("knot_stride", ctypes.c_int32), ("store_knots", ctypes.c_int32),
+        ("store_buffers", ctypes.c_int32), ("need_full", ctypes.c_int32), ("solved", ctypes.c_int32),
+        ("reserved", ctypes.c_int32), ("alpha", ctypes.c_double),
+        ("payload_bytes_per_entry", ctypes.c_int64), ("total_bytes", ctypes.c_int64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 _DP = ctypes.POINTER(ctypes.c_double)
 _IP = ctypes.POINTER(ctypes.c_int32)
 
@@ -216,6 +233,20 @@ SIGNATURES = [
     ("mhpc_reserve_knots", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("mhpc_copy_problems", ctypes.c_int, [ctypes.c_void_p, _IP, ctypes.c_void_p, _IP, ctypes.c_int,
                                           ctypes.POINTER(ctypes.c_float)]),
+    ("mhpc_snapshot_size", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _IP,
+                                          ctypes.POINTER(ctypes.c_int64)]),
+    ("mhpc_snapshot_problems", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _IP, ctypes.c_void_p,
+                                              ctypes.c_int64, ctypes.POINTER(ctypes.c_float)]),
+    ("mhpc_snapshot_info", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64,
+                                          ctypes.POINTER(SnapshotInfo)]),
+    ("mhpc_snapshot_entry", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+                                           ctypes.POINTER(ProblemDesc), ctypes.POINTER(HsddpOption),
+                                           ctypes.POINTER(CostWeights),
+                                           ctypes.POINTER(ConstraintParams)]),
+    ("mhpc_snapshot_status", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+                                            ctypes.c_int, _IP]),
+    ("mhpc_restore_problems", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _IP, ctypes.c_void_p,
+                                             ctypes.c_int64, _IP, ctypes.POINTER(ctypes.c_float)]),
     ("mhpc_set_commands", ctypes.c_int, [ctypes.c_void_p, _DP, _DP]),
     ("mhpc_get_commands", ctypes.c_int, [ctypes.c_void_p, _DP, _DP]),
     ("mhpc_get_reference_problems", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,

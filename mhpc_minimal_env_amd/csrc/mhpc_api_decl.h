@@ -40,6 +40,14 @@ int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* 
                        const mhpc_problem_desc* descs, const int32_t* desc_of);
 int api_copy_problems(Handle* dst, const int32_t* dst_problems, Handle* src,
                       const int32_t* src_problems, int n, float* ms);
+int api_snapshot_size(Handle* h, int n, const int32_t* problems, int64_t* bytes);
+int api_snapshot_problems(Handle* h, int n, const int32_t* problems, void* blob, int64_t bytes,
+                          float* ms);
+int api_restore_problems(Handle* dst, int n, const int32_t* dst_problems, const void* blob,
+                         int64_t bytes, const int32_t* entries, float* ms);
+int api_snapshot_entry(const void* blob, int64_t bytes, int entry, mhpc_problem_desc* desc,
+                       mhpc_hsddp_option* option, mhpc_cost_weights* w, mhpc_constraint_params* c);
+int api_snapshot_status(const void* blob, int64_t bytes, int first, int count, int32_t* status);
 int api_get_problem_desc(Handle* h, int b, mhpc_problem_desc* desc);
 int api_set_commands(Handle* h, const double* vel, const double* height);
 int api_get_commands(Handle* h, double* vel, double* height);

@@ -2,11 +2,13 @@
 // call forwards to the fp64 (namespace mhpc) or fp32 (namespace mhpc32) instantiation of
 // mhpc_runtime.cpp according to the descriptor's precision at mhpc_create.
 #include <math.h>
+#include <string.h>
 
 #include <exception>
 #include <string>
 
 #include "../../include/mhpc_capi.h"
+#include "mhpc_snapshot_map.h"
 
 thread_local std::string mhpc_g_err;
 
@@ -206,6 +208,85 @@ extern "C" int mhpc_copy_problems(mhpc_handle* dst, const int32_t* dst_problems,
                                          (mhpc::Handle*)src->impl, src_problems, n, ms);
   } catch (...) {
     return fail_exception("mhpc_copy_problems");
+  }
+}
+extern "C" int mhpc_snapshot_size(mhpc_handle* h, int n, const int32_t* problems, int64_t* bytes) {
+  FWD(snapshot_size, n, problems, bytes);
+}
+extern "C" int mhpc_snapshot_problems(mhpc_handle* h, int n, const int32_t* problems, void* blob,
+                                      int64_t bytes, float* ms) {
+  FWD(snapshot_problems, n, problems, blob, bytes, ms);
+}
+extern "C" int mhpc_restore_problems(mhpc_handle* h, int n, const int32_t* dst_problems,
+                                     const void* blob, int64_t bytes, const int32_t* entries,
+                                     float* ms) {
+  FWD(restore_problems, n, dst_problems, blob, bytes, entries, ms);
+}
+// The blob readers need no handle: the header says which instantiation wrote the entries.
+static int snapshot_header(const void* blob, int64_t bytes, mhpc_snap::Header* hd) {
+  const char* why = bytes < 0 ? "negative length" : mhpc_snap::validate(blob, (size_t)bytes, hd);
+  if (why) {
+    mhpc_g_err = why;
+    return MHPC_ERR_INVALID;
+  }
+  if (hd->precision != 64 && hd->precision != 32) {
+    mhpc_g_err = "snapshot header out of range (precision)";
+    return MHPC_ERR_INVALID;
+  }
+  return MHPC_OK;
+}
+extern "C" int mhpc_snapshot_info(const void* blob, int64_t bytes,
+                                  struct mhpc_snapshot_info* info) {
+  if (!info) {
+    mhpc_g_err = "null argument";
+    return MHPC_ERR_INVALID;
+  }
+  mhpc_snap::Header hd;
+  if (int rc = snapshot_header(blob, bytes, &hd)) return rc;
+  if (const char* why = mhpc_snap::consistent(hd)) {
+    mhpc_g_err = why;
+    return MHPC_ERR_INVALID;
+  }
+  struct mhpc_snapshot_info o = {};
+  o.version = (int32_t)hd.version;
+  o.n_entries = (int32_t)hd.n_entries;
+  o.precision = (int32_t)hd.precision;
+  o.sweep_bits = hd.sweep32 ? 32 : 64;
+  o.x0_row = (int32_t)hd.x0_row;
+  o.n_slots = (int32_t)hd.nslot;
+  o.knot_stride = (int32_t)hd.NK;
+  o.store_knots = (int32_t)hd.nbk;
+  o.store_buffers = (int32_t)hd.spmax;
+  o.need_full = (int32_t)hd.need_full;
+  o.solved = (int32_t)hd.solved;
+  memcpy(&o.alpha, &hd.alpha_bits, sizeof(double));
+  o.payload_bytes_per_entry = (int64_t)hd.payload_entry_bytes;
+  o.total_bytes = (int64_t)hd.total_bytes;
+  *info = o;
+  return MHPC_OK;
+}
+extern "C" int mhpc_snapshot_entry(const void* blob, int64_t bytes, int entry,
+                                   mhpc_problem_desc* desc, mhpc_hsddp_option* option,
+                                   mhpc_cost_weights* weights, mhpc_constraint_params* constraints) {
+  mhpc_snap::Header hd;
+  if (int rc = snapshot_header(blob, bytes, &hd)) return rc;
+  try {
+    return hd.precision == 32
+               ? mhpc32::api_snapshot_entry(blob, bytes, entry, desc, option, weights, constraints)
+               : mhpc::api_snapshot_entry(blob, bytes, entry, desc, option, weights, constraints);
+  } catch (...) {
+    return fail_exception("mhpc_snapshot_entry");
+  }
+}
+extern "C" int mhpc_snapshot_status(const void* blob, int64_t bytes, int first, int count,
+                                    int32_t* status) {
+  mhpc_snap::Header hd;
+  if (int rc = snapshot_header(blob, bytes, &hd)) return rc;
+  try {
+    return hd.precision == 32 ? mhpc32::api_snapshot_status(blob, bytes, first, count, status)
+                              : mhpc::api_snapshot_status(blob, bytes, first, count, status);
+  } catch (...) {
+    return fail_exception("mhpc_snapshot_status");
   }
 }
 extern "C" int mhpc_get_problem_desc(mhpc_handle* h, int problem, mhpc_problem_desc* desc) {

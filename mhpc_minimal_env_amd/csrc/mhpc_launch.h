@@ -86,6 +86,18 @@ int copy_block_table(const CopySide& src, const CopySide& dst, int* out);
 hipError_t launch_copy_problems(const CopySide& src, const CopySide& dst, int n, const int* pairs,
                                 int nblk, const int* blocks, hipStream_t s);
 
+// ---- mhpc_snapshot.hip ----------------------------------------------------------------------
+// The staging side of one round of mhpc_snapshot_problems / mhpc_restore_problems: R problems of
+// knot stride NK, nslot slots and a store of spmax buffers of nbk knots (spmax = 0: none) laid out
+// in one device buffer of snap_stage_bytes (mhpc_snapshot_map.h) -- a CopySide, so pack and unpack
+// are launch_copy_problems into and out of it.  snap_move queues the copies of `count` consecutive
+// entries between a blob's payload (n entries) from `entry` on and the staging records from `slot`
+// on, one per array.
+CopySide snap_side(void* staging, int R, int NK, int nslot, int nbk, int spmax);
+size_t snap_stage_bytes(int R, int NK, int nslot, int nbk, int spmax);
+hipError_t snap_move(void* staging, int R, int NK, int nslot, int nbk, int spmax, char* payload,
+                     int n, int entry, int slot, int count, bool to_host, hipStream_t s);
+
 // ---- mhpc_tick.hip --------------------------------------------------------------------------
 // list-driven device code of mhpc_tick_problems: the phase-buffer save (save = 1: the nominal slot
 // of each listed problem to its store rows) / load (store rows to slot 0, K, du, G; a phase's last

@@ -721,9 +721,11 @@ class Ledger {
   }
   // mhpc_copy_problems: problem d becomes src's problem s (src may be this ledger).  No command is
   // pending in either handle then, so no mark moves.
-  void copied(int d, const Ledger& src, int s) {
-    set(fresh_, nfresh_, d, src.fresh_[s]);
-    open_[d] = src.open_[s];
+  void copied(int d, const Ledger& src, int s) { copied(d, src.fresh_[s] != 0, src.open_[s] != 0); }
+  // ... or the marks a snapshot entry carries (mhpc_restore_problems)
+  void copied(int d, bool fresh, bool open) {
+    set(fresh_, nfresh_, d, fresh);
+    open_[d] = open;
   }
   void command_changed(int b) { set(mark_, nmark_, b, true); }
   // mhpc_initialize / mhpc_update_problem(s): every problem's references are current

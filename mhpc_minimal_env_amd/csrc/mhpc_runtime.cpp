@@ -16,6 +16,7 @@
 #include "mhpc_devtemp.h"
 #include "mhpc_launch.h"
 #include "mhpc_plan.h"
+#include "mhpc_snapshot_map.h"
 
 extern thread_local std::string mhpc_g_err;  // mhpc_capi.cpp (mhpc_last_error)
 
@@ -135,6 +136,7 @@ struct Handle {
   int nsub_req = 0;
   int ro_store_req = 0;  // MHPC_VARIANT_RO_STORE (0: by the batch's line-search shape)
   int sweep_bits = 0;    // MHPC_VARIANT_SWEEP_BITS (0 = 64: the sweep computes in double)
+  int snap_round_req = 0;  // MHPC_VARIANT_SNAP_ROUND (0: as many problems as fit the staging cap)
   struct SubStreams {
     hipStream_t s1 = nullptr, s2 = nullptr, s3 = nullptr;  // s3: the partials' second group
     hipEvent_t fork = nullptr, join = nullptr, gate = nullptr, done = nullptr, pfork = nullptr,
@@ -1928,70 +1930,110 @@ int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* 
   return collect_profile(h);
 }
 
-// ---- copies of live problems (mhpc_copy_problems) -------------------------------------------
+// ---- copies of live problems (mhpc_copy_problems, mhpc_restore_problems) ------------------------
 static CopySide copy_side(const Handle* h) {
   return CopySide{h->d, h->store_valid ? h->store : nullptr, h->sp.NK, h->sp.nslot, h->nbk, h->spmax};
 }
+
+// The host state of one source problem that travels with a copy -- and, byte for byte, the entry
+// record of a snapshot blob (fixed-width members, no padding, no pointers).
+struct SrcProblem {
+  ProbLayout pl;  // layout with its buffer rotation
+  int32_t cmode, fresh, open, reserved;  // gait point; the ledger's marks
+  double cmd[2];
+  mhpc_hsddp_option opt;
+  CostParams cw;
+};
+static_assert(sizeof(SrcProblem) == sizeof(ProbLayout) + 4 * sizeof(int32_t) + 2 * sizeof(double) +
+                                        sizeof(mhpc_hsddp_option) + sizeof(CostParams) &&
+                  sizeof(ProbLayout) == sizeof(mhpc_problem_desc) + 2 * sizeof(int),
+              "a snapshot entry has no padding");
+static SrcProblem src_problem(const Handle* s, int a) {
+  SrcProblem q;
+  memset(&q, 0, sizeof q);
+  q.pl = s->pl[a];
+  q.cmode = s->cmode[a];
+  q.fresh = s->led.fresh(a);
+  q.open = s->led.open(a);
+  q.cmd[0] = s->cmd[2 * (size_t)a];
+  q.cmd[1] = s->cmd[2 * (size_t)a + 1];
+  q.opt = s->otab.rec[s->otab.of[a]];
+  q.cw = s->psets[s->pset_of[a]];
+  return q;
+}
+
+// What a copy compares and takes, whether its source is a live handle or a snapshot blob.
+struct CopySource {
+  const char* call;   // the entry point, for messages
+  bool blob;          // a snapshot: a copy that covers the whole destination adopts its call-order point
+  double alpha;
+  int nslot, x0_row;
+  bool sweep32, initialized, pending, need_full, solved, has_store;
+  std::vector<SrcProblem> p;  // the listed source problems, in list order
+};
+static CopySource source_of(const Handle* s, const char* call) {
+  return CopySource{call, false, s->opt.alpha, s->sp.nslot, x0_row_of(s->plan), s->sweep_bits == 32,
+                    s->initialized, pending(s), s->need_full, s->solved, s->store_valid, {}};
+}
+// The device part of a copy, which differs between the two: one launch out of the source handle's
+// arrays, or rounds through the staging buffers of a blob.
+struct CopyMover {
+  virtual ~CopyMover() {}
+  // everything that can fail while the destination can still go back: allocations, uploads, the
+  // order against the source's stream (dst's arrays and store are final here)
+  virtual hipError_t prepare(Handle* d, const int32_t* dp, int n) = 0;
+  // the copy of every pair, queued and waited for; ms: device time of its launches
+  virtual hipError_t run(Handle* d, float* ms) = 0;
+};
 
 // In the reference a controller is an object and a copy of it is a copy of the object: the
 // destination problems become the source problems as they stand -- nominal and trial slots,
 // K / du / G, partials, impact Jacobians, solver state, x0 row, references, command, parameter set,
 // layout with its buffer rotation, gait point, phase-buffer rows -- inside one handle or between
-// two of one device.  Like mhpc_reset_problems it never re-strides or reallocates the
-// destination's packed arrays and leaves every other problem's records where they are; everything
-// that can refuse the call is checked before anything changes (a device error, unlike a refusal, can
-// leave the destination problems undefined, as for a reset).  The device part is one list-driven
-// launch (mhpc_copy.hip) on the destination's stream, after an event on the source's; both
-// streams are idle when the call returns.
-int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp_, int n, float* ms) {
-  if (!d || !s || !dp || !sp_) return fail(MHPC_ERR_INVALID, "null argument");
-  const int Bd = d->sp.B, Bs = s->sp.B;
-  ProblemList dst;
-  PLANCHK(dst.begin, n, Bd, true);
-  for (int i = 0; i < n; ++i) {  // (an entry's ranges, source and destination, before "twice")
-    if (sp_[i] < 0 || sp_[i] >= Bs) return fail(MHPC_ERR_INVALID, "problem out of range");
-    PLANCHK(dst.add, dp[i]);
-  }
-  for (int i = 0; d == s && i < n; ++i)
-    if (dst.at[sp_[i]] >= 0)
-      return fail(MHPC_ERR_INVALID, "a problem is both a source and a destination");
-  if (d->device != s->device) return fail(MHPC_ERR_INVALID, "the handles are on different devices");
+// two of one device, or out of a snapshot blob.  Like mhpc_reset_problems it never re-strides or
+// reallocates the destination's packed arrays and leaves every other problem's records where they
+// are; everything that can refuse the call is checked before anything changes (a device error,
+// unlike a refusal, can leave the destination problems undefined, as for a reset).  dp: n checked
+// destination problems, none twice.  All the handle's streams are idle when the call returns.
+static int copy_into(Handle* d, const int32_t* dp, int n, const CopySource& src, CopyMover& mv, float* ms) {
   // the line-search grid (alpha, nslot: the arrays' shape) is the handle's; a source problem's
   // option record travels with it, as an index into dst's table -- the copy never adds a record
   // to it (that would change dst's launch schedule), so the record must be one of dst's already
-  if (memcmp(&d->opt.alpha, &s->opt.alpha, sizeof(double)) != 0 || d->sp.nslot != s->sp.nslot)
+  // (inside one handle that is the source's own slot: equal records share one)
+  if (memcmp(&d->opt.alpha, &src.alpha, sizeof(double)) != 0 || d->sp.nslot != src.nslot)
     return fail(MHPC_ERR_INVALID, "the handles' mhpc_hsddp_option differ");
   std::vector<int> nslot_of(n);  // dst's slot of each source problem's record
   for (int i = 0; i < n; ++i) {
-    nslot_of[i] = d == s ? s->otab.of[sp_[i]] : d->otab.find(s->otab.rec[s->otab.of[sp_[i]]]);
+    nslot_of[i] = d->otab.find(src.p[i].opt);
     if (nslot_of[i] < 0)
       return fail(MHPC_ERR_INVALID,
                   "the handles' mhpc_hsddp_option differ: a source problem's option set is none of the destination's");
   }
   // the one kernel variant that changes results: the sweep's arithmetic (0 and 64 are both double)
-  if ((d->sweep_bits == 32) != (s->sweep_bits == 32))
+  if ((d->sweep_bits == 32) != src.sweep32)
     return fail(MHPC_ERR_INVALID, "the handles' backward-sweep arithmetic (MHPC_VARIANT_SWEEP_BITS) differs");
   // the destination's arrays stay as they are: every source layout must fit them
   const int r = x0_row_of(d->plan);
-  if (x0_row_of(s->plan) != r) return fail(MHPC_ERR_INVALID, "the handles' x0 row widths differ");
+  if (src.x0_row != r) return fail(MHPC_ERR_INVALID, "the handles' x0 row widths differ");
   std::vector<ProbLayout> npl = d->pl;
   std::vector<CostParams> nsets = d->psets;
   std::vector<int> nof = d->pset_of;
   for (int i = 0; i < n; ++i) {
-    const ProbLayout& q = s->pl[sp_[i]];
+    const ProbLayout& q = src.p[i].pl;
     PLANCHK(fits_arrays, q, d->sp.NK, d->store_valid, d->nbk, d->spmax, true);
     npl[dp[i]] = q;
     nof[dp[i]] = (int)nsets.size();  // the source's set, merged below with the ones it equals
-    nsets.push_back(s->psets[s->pset_of[sp_[i]]]);
+    nsets.push_back(src.p[i].cw);
   }
   if (x0_row_of(npl) != r) return fail(MHPC_ERR_INVALID, "the x0 row width would change");
-  if (!d->initialized || !s->initialized)
-    return fail(MHPC_ERR_STATE, "mhpc_initialize must precede mhpc_copy_problems");
-  for (const Handle* h : {d, s})
-    if (pending(h))
-      return fail(MHPC_ERR_STATE,
-                  "commands or parameters pending: call mhpc_initialize or mhpc_update_problem first");
-  if (d->need_full != s->need_full || d->solved != s->solved)
+  if (!d->initialized || !src.initialized)
+    return fail(MHPC_ERR_STATE, std::string("mhpc_initialize must precede ") + src.call);
+  if (pending(d) || src.pending)
+    return fail(MHPC_ERR_STATE,
+                "commands or parameters pending: call mhpc_initialize or mhpc_update_problem first");
+  // a snapshot that replaces every problem of the destination brings its point of the call order
+  const bool adopt = src.blob && n == d->sp.B;
+  if (!adopt && (d->need_full != src.need_full || d->solved != src.solved))
     return fail(MHPC_ERR_STATE, "the handles are at different points of the call order");
   merge_sets(nsets, nof);
   HIPCHK(hipSetDevice(d->device));
@@ -2006,55 +2048,42 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
   if (rc) return rc;
   // a source with phase buffers gives the destination its own, as its first update would (an
   // empty store of the new layouts' shape, which the old layouts fit as well)
-  if (s->store_valid && (rc = ensure_store(d))) {
+  if (src.has_store && (rc = ensure_store(d))) {
     (void)commit_groups(d, std::move(plan), true, &npl, &nsets, &nof);
     return rc;
   }
-  // the pair list and, behind it, the (run, chunk) table of one pair: one upload
-  const CopySide cs = copy_side(s), cd = copy_side(d);
-  const int nblk = copy_block_table(cs, cd, nullptr);
-  // ... and behind that the (destination problem, option slot) entries of the option hand-over
-  std::vector<int> pairs(2 * (size_t)n + nblk + 2 * (size_t)n);
-  const size_t ent0 = 2 * (size_t)n + nblk;
+  // the (destination problem, option slot) entries of the option hand-over
+  std::vector<int> ent(2 * (size_t)n);
   for (int i = 0; i < n; ++i) {
-    pairs[2 * (size_t)i] = sp_[i];
-    pairs[2 * (size_t)i + 1] = dp[i];
-    pairs[ent0 + 2 * (size_t)i] = dp[i];
-    pairs[ent0 + 2 * (size_t)i + 1] = nslot_of[i];
+    ent[2 * (size_t)i] = dp[i];
+    ent[2 * (size_t)i + 1] = nslot_of[i];
   }
-  copy_block_table(cs, cd, pairs.data() + 2 * (size_t)n);
   DevTemp<int> t(d->stream);
-  const int* dpairs = t.in(std::move(pairs));
-  if (t.e == hipSuccess && s != d) {
-    t.e = hipEventRecord(s->evfork, s->stream);
-    if (t.e == hipSuccess) t.e = hipStreamWaitEvent(d->stream, s->evfork, 0);
-  }
-  if (t.e == hipSuccess) t.e = hipEventRecord(d->ev0, d->stream);
+  const int* dent = t.in(std::move(ent));
+  if (t.e == hipSuccess) t.e = mv.prepare(d, dp, n);
   if (t.e != hipSuccess) {  // nothing of the copy is queued yet
-    drain({d->stream});
+    drain({d->stream2, d->stream});
     (void)commit_groups(d, std::move(plan), true, &npl, &nsets, &nof);
-    return dev_fail("mhpc_copy_problems", t.e);
+    return dev_fail(src.call, t.e);
   }
-  // (d == s reads its own entries: a source is no destination, so they are the old ones)
   for (int i = 0; i < n; ++i) {
-    const int a = sp_[i], b = dp[i];
-    d->cmode[b] = s->cmode[a];
-    d->cmd[2 * (size_t)b] = s->cmd[2 * (size_t)a];
-    d->cmd[2 * (size_t)b + 1] = s->cmd[2 * (size_t)a + 1];
-    d->led.copied(b, s->led, a);
+    const SrcProblem& q = src.p[i];
+    const int b = dp[i];
+    d->cmode[b] = q.cmode;
+    d->cmd[2 * (size_t)b] = q.cmd[0];
+    d->cmd[2 * (size_t)b + 1] = q.cmd[1];
+    d->led.copied(b, q.fresh != 0, q.open != 0);
   }
-  t.e = launch_copy_problems(cs, cd, n, dpairs, nblk, dpairs + 2 * (size_t)n, d->stream);
-  // the option index of the destinations (their rewritten option fields came with the state)
-  if (t.e == hipSuccess) t.e = launch_set_options(d->d, d->doid, n, dpairs + ent0, 0, d->stream);
-  if (t.e == hipSuccess) t.e = hipEventRecord(d->ev1, d->stream);
-  if (t.e == hipSuccess) t.e = hipStreamSynchronize(d->stream);
   float el = 0;
-  if (t.e == hipSuccess) t.e = hipEventElapsedTime(&el, d->ev0, d->ev1);
+  t.e = mv.run(d, &el);
+  // the option index of the destinations (their rewritten option fields came with the state)
+  if (t.e == hipSuccess) t.e = launch_set_options(d->d, d->doid, n, dent, 0, d->stream);
+  if (t.e == hipSuccess) t.e = hipStreamSynchronize(d->stream);
   if (t.e != hipSuccess) {
     // a failed launch: the destination problems are undefined (as after a failed reset); nothing
     // of the handle's may stay queued behind it
-    drain({d->stream});
-    return dev_fail("mhpc_copy_problems", t.e);
+    drain({d->stream2, d->stream});
+    return dev_fail(src.call, t.e);
   }
   // the host table follows the device index once the launches have succeeded (a record the
   // destinations were the last to use is dropped; problem 0's may have changed)
@@ -2065,7 +2094,399 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
     d->otab.of[b] = nslot_of[i];
   }
   mirror_option0(d);
+  if (adopt) {
+    d->need_full = src.need_full;
+    d->solved = src.solved;
+  }
   if (ms) *ms = el;
+  return MHPC_OK;
+}
+
+// One list-driven launch (mhpc_copy.hip) on the destination's stream, after an event on the
+// source's.
+struct HandleMover : CopyMover {
+  Handle* s;
+  const int32_t* sp;
+  DevTemp<int> t;
+  const int* dpairs = nullptr;
+  int n = 0, nblk = 0;
+  CopySide cs, cd;
+  HandleMover(Handle* src, const int32_t* src_problems, hipStream_t q) : s(src), sp(src_problems), t(q) {}
+  hipError_t prepare(Handle* d, const int32_t* dp, int n_) override {
+    n = n_;
+    cs = copy_side(s);
+    cd = copy_side(d);
+    // the pair list and, behind it, the (run, chunk) table of one pair: one upload
+    nblk = copy_block_table(cs, cd, nullptr);
+    std::vector<int> pairs(2 * (size_t)n + nblk);
+    for (int i = 0; i < n; ++i) {
+      pairs[2 * (size_t)i] = sp[i];
+      pairs[2 * (size_t)i + 1] = dp[i];
+    }
+    copy_block_table(cs, cd, pairs.data() + 2 * (size_t)n);
+    dpairs = t.in(std::move(pairs));
+    if (t.e == hipSuccess && s != d) {
+      t.e = hipEventRecord(s->evfork, s->stream);
+      if (t.e == hipSuccess) t.e = hipStreamWaitEvent(d->stream, s->evfork, 0);
+    }
+    return t.e;
+  }
+  hipError_t run(Handle* d, float* ms) override {
+    hipError_t e = hipEventRecord(d->ev0, d->stream);
+    if (e == hipSuccess) e = launch_copy_problems(cs, cd, n, dpairs, nblk, dpairs + 2 * (size_t)n, d->stream);
+    if (e == hipSuccess) e = hipEventRecord(d->ev1, d->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    if (e == hipSuccess) e = hipEventElapsedTime(ms, d->ev0, d->ev1);
+    return e;
+  }
+};
+
+int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp_, int n, float* ms) {
+  if (!d || !s || !dp || !sp_) return fail(MHPC_ERR_INVALID, "null argument");
+  const int Bd = d->sp.B, Bs = s->sp.B;
+  ProblemList dst;
+  PLANCHK(dst.begin, n, Bd, true);
+  for (int i = 0; i < n; ++i) {  // (an entry's ranges, source and destination, before "twice")
+    if (sp_[i] < 0 || sp_[i] >= Bs) return fail(MHPC_ERR_INVALID, "problem out of range");
+    PLANCHK(dst.add, dp[i]);
+  }
+  for (int i = 0; d == s && i < n; ++i)
+    if (dst.at[sp_[i]] >= 0)
+      return fail(MHPC_ERR_INVALID, "a problem is both a source and a destination");
+  if (d->device != s->device) return fail(MHPC_ERR_INVALID, "the handles are on different devices");
+  // (d == s: a source is no destination, so its entries are read before any of them changes)
+  CopySource src = source_of(s, "mhpc_copy_problems");
+  src.p.reserve(n);
+  for (int i = 0; i < n; ++i) src.p.push_back(src_problem(s, sp_[i]));
+  HandleMover mv(s, sp_, d->stream);
+  return copy_into(d, dp, n, src, mv, ms);
+}
+
+// ---- snapshots of live problems (mhpc_snapshot_problems, mhpc_restore_problems) -----------------
+// The serialised form of the copy above: header, entry table (SrcProblem records), payload
+// (mhpc_snapshot_map.h).  A snapshot packs the listed problems through staging sides whose knot
+// stride is the longest listed layout; a restore is copy_into with the blob as its source.
+static constexpr size_t kSnapStageCap = (size_t)256 << 20;  // bytes of one staging buffer
+
+static mhpc_copy::Sizes snap_sizes() {
+  return mhpc_copy::Sizes{(int)sizeof(real), (int)sizeof(ProbState), (int)sizeof(BwsCarry)};
+}
+// The header of a snapshot of the listed (checked) problems of h.
+static mhpc_snap::Header snap_header(const Handle* h, int n, const int32_t* problems) {
+  mhpc_snap::Header o;
+  memset(&o, 0, sizeof o);
+  int NK = 1;
+  for (int i = 0; i < n; ++i) {
+    const mhpc_problem_desc& q = h->pl[problems[i]].desc;
+    int nk = 0;
+    for (int p = 0; p < q.n_wb + q.n_fb; ++p) nk += q.N[p];
+    NK = std::max(NK, nk);
+  }
+  o.magic = mhpc_snap::MAGIC;
+  o.version = mhpc_snap::FORMAT_VERSION;
+  o.header_bytes = sizeof o;
+  o.n_entries = n;
+  o.entry_bytes = sizeof(SrcProblem);
+  o.precision = sizeof(real) == 4 ? 32 : 64;
+  o.elem_bytes = sizeof(real);
+  o.sizeof_state = sizeof(ProbState);
+  o.sizeof_carry = sizeof(BwsCarry);
+  o.KS = KS;
+  o.PS = PS;
+  o.PS_JAC = PS_JAC;
+  o.SREC = kStoreRec;
+  o.MAXP = MAXP;
+  o.nslot = h->sp.nslot;
+  memcpy(&o.alpha_bits, &h->opt.alpha, sizeof(double));
+  o.sweep32 = h->sweep_bits == 32;
+  o.x0_row = x0_row_of(h->plan);
+  o.NK = std::min(NK, h->sp.NK);
+  o.nbk = h->store_valid ? h->nbk : 0;
+  o.spmax = h->store_valid ? h->spmax : 0;
+  o.need_full = h->need_full;
+  o.solved = h->solved;
+  o.payload_entry_bytes = mhpc_snap::entry_payload_bytes(mhpc_snap::dims_of(o), snap_sizes());
+  o.total_bytes = sizeof o + (size_t)n * (o.entry_bytes + o.payload_entry_bytes);
+  return o;
+}
+static int snap_list(const Handle* h, int n, const int32_t* problems) {
+  if (!h || !problems) return fail(MHPC_ERR_INVALID, "null argument");
+  ProblemList l;
+  PLANCHK(l.begin, n, h->sp.B, false);
+  for (int i = 0; i < n; ++i) PLANCHK(l.add, problems[i]);
+  return MHPC_OK;
+}
+// A blob this build can read: the format's own checks, then this instantiation's sizes.
+static int snap_open(const void* blob, int64_t bytes, mhpc_snap::Header* hd) {
+  if (!blob || bytes < 0) return fail(MHPC_ERR_INVALID, "null snapshot blob");
+  if (const char* why = mhpc_snap::validate(blob, (size_t)bytes, hd)) return fail(MHPC_ERR_INVALID, why);
+  if (hd->precision != (sizeof(real) == 4 ? 32u : 64u) || hd->elem_bytes != sizeof(real))
+    return fail(MHPC_ERR_INVALID, "the snapshot's precision differs from the handle's");
+  if (hd->sizeof_state != sizeof(ProbState) || hd->sizeof_carry != sizeof(BwsCarry))
+    return fail(MHPC_ERR_INVALID, "snapshot of another build: sizeof(ProbState) / sizeof(BwsCarry) differ");
+  if (hd->KS != (unsigned)KS || hd->PS != (unsigned)PS || hd->PS_JAC != (unsigned)PS_JAC ||
+      hd->SREC != (unsigned)kStoreRec || hd->MAXP != (unsigned)MAXP || hd->entry_bytes != sizeof(SrcProblem))
+    return fail(MHPC_ERR_INVALID, "snapshot of another build: record widths (KS, PS, PS_JAC, SREC, MAXP) differ");
+  if (const char* why = mhpc_snap::consistent(*hd)) return fail(MHPC_ERR_INVALID, why);
+  return MHPC_OK;
+}
+
+int api_snapshot_size(Handle* h, int n, const int32_t* problems, int64_t* bytes) {
+  if (!bytes) return fail(MHPC_ERR_INVALID, "null argument");
+  if (int rc = snap_list(h, n, problems)) return rc;
+  *bytes = (int64_t)snap_header(h, n, problems).total_bytes;
+  return MHPC_OK;
+}
+
+// The two staging buffers of a snapshot or restore and the events that time its launches; the
+// rounds alternate between the handle's two streams, each with a buffer of its own, so a round's
+// launch runs beside the other round's copies and a buffer is reused in stream order.
+struct SnapStage {
+  void* buf[2] = {nullptr, nullptr};
+  std::vector<hipEvent_t> ev;  // [rounds][2]
+  ~SnapStage() {
+    for (void* p : buf)
+      if (p) (void)hipFree(p);
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+  hipError_t alloc(size_t bytes, int rounds) {
+    for (int k = 0; k < (rounds > 1 ? 2 : 1); ++k)
+      if (hipError_t e = hipMalloc(&buf[k], bytes)) return e;
+    ev.reserve(2 * (size_t)rounds);
+    for (int i = 0; i < 2 * rounds; ++i) {
+      hipEvent_t x;
+      if (hipError_t e = hipEventCreate(&x)) return e;
+      ev.push_back(x);
+    }
+    return hipSuccess;
+  }
+  hipError_t elapsed(int rounds, float* ms) const {
+    float sum = 0;
+    for (int r = 0; r < rounds; ++r) {
+      float el = 0;
+      if (hipError_t e = hipEventElapsedTime(&el, ev[2 * (size_t)r], ev[2 * (size_t)r + 1])) return e;
+      sum += el;
+    }
+    *ms = sum;
+    return hipSuccess;
+  }
+};
+static int snap_round(const Handle* h, size_t entry_bytes, int n) {
+  return h->snap_round_req > 0 ? std::min(h->snap_round_req, n)
+                               : mhpc_snap::default_round(entry_bytes, kSnapStageCap, n);
+}
+
+int api_snapshot_problems(Handle* h, int n, const int32_t* problems, void* blob, int64_t bytes, float* ms) {
+  if (!blob) return fail(MHPC_ERR_INVALID, "null argument");
+  if (int rc = snap_list(h, n, problems)) return rc;
+  if (!h->initialized) return fail(MHPC_ERR_STATE, "mhpc_initialize must precede mhpc_snapshot_problems");
+  if (pending(h))
+    return fail(MHPC_ERR_STATE,
+                "commands or parameters pending: call mhpc_initialize or mhpc_update_problem first");
+  mhpc_snap::Header hd = snap_header(h, n, problems);
+  if (bytes < (int64_t)hd.total_bytes)
+    return fail(MHPC_ERR_INVALID, "snapshot buffer too small (mhpc_snapshot_size)");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const int NK = hd.NK, nslot = hd.nslot, nbk = hd.nbk, spmax = hd.spmax;
+  const int R = snap_round(h, hd.payload_entry_bytes, n), rounds = mhpc_snap::n_rounds(n, R);
+  const CopySide cs = copy_side(h), cstage = snap_side(nullptr, R, NK, nslot, nbk, spmax);
+  // the pair list (source problem, staging record) and behind it the (run, chunk) table of a pair
+  const int nblk = copy_block_table(cs, cstage, nullptr);
+  std::vector<int> pairs(2 * (size_t)n + nblk);
+  for (int i = 0; i < n; ++i) {
+    pairs[2 * (size_t)i] = problems[i];
+    pairs[2 * (size_t)i + 1] = i % R;
+  }
+  copy_block_table(cs, cstage, pairs.data() + 2 * (size_t)n);
+  DevTemp<int> t(h->stream);
+  const int* dpairs = t.in(std::move(pairs));
+  SnapStage st;
+  if (t.e == hipSuccess) t.e = st.alloc(snap_stage_bytes(R, NK, nslot, nbk, spmax), rounds);
+  if (t.e == hipSuccess) t.e = hipStreamSynchronize(h->stream);  // the lists are up before stream2 reads them
+  char* payload = (char*)blob + sizeof hd + (size_t)n * sizeof(SrcProblem);
+  for (int r = 0; t.e == hipSuccess && r < rounds; ++r) {
+    int e0, cnt;
+    mhpc_snap::round_of(n, R, r, &e0, &cnt);
+    const hipStream_t q = r & 1 ? h->stream2 : h->stream;
+    void* buf = st.buf[r & 1];
+    t.e = hipEventRecord(st.ev[2 * (size_t)r], q);
+    if (t.e == hipSuccess)
+      t.e = launch_copy_problems(cs, snap_side(buf, R, NK, nslot, nbk, spmax), cnt, dpairs + 2 * (size_t)e0,
+                                 nblk, dpairs + 2 * (size_t)n, q);
+    if (t.e == hipSuccess) t.e = hipEventRecord(st.ev[2 * (size_t)r + 1], q);
+    if (t.e == hipSuccess) t.e = snap_move(buf, R, NK, nslot, nbk, spmax, payload, n, e0, 0, cnt, true, q);
+  }
+  // after an error nothing more was queued; either way both streams are idle from here
+  for (hipStream_t q : {h->stream2, h->stream}) {
+    const hipError_t e = hipStreamSynchronize(q);
+    if (t.e == hipSuccess) t.e = e;
+  }
+  float el = 0;
+  if (t.e == hipSuccess) t.e = st.elapsed(rounds, &el);
+  if (t.e != hipSuccess) return dev_fail("mhpc_snapshot_problems", t.e);
+  // header and entry table last: a blob with a valid header has its whole payload
+  char* ent = (char*)blob + sizeof hd;
+  for (int i = 0; i < n; ++i) {
+    const SrcProblem q = src_problem(h, problems[i]);
+    memcpy(ent + (size_t)i * sizeof q, &q, sizeof q);
+  }
+  hd.checksum = mhpc_snap::checksum_of(hd, ent);
+  memcpy(blob, &hd, sizeof hd);
+  if (ms) *ms = el;
+  return MHPC_OK;
+}
+
+// Rounds of distinct blob entries through the staging buffers: upload, then unpack with the
+// destination's strides (k_copy_problems out of the staging side).
+struct BlobMover : CopyMover {
+  mhpc_snap::Header hd;
+  char* payload;
+  const int32_t* entries;  // [n] entry of each destination (null: entry i)
+  int R_req;
+  DevTemp<int> t;
+  SnapStage st;
+  const int* dlists = nullptr;
+  int R = 0, rounds = 0, nblk = 0, n = 0;
+  std::vector<int> uniq;             // the distinct entries, ascending
+  std::vector<int> first, count;     // [rounds] each round's pairs in the uploaded list
+  CopySide cd;
+  BlobMover(const mhpc_snap::Header& h, const void* blob, const int32_t* ent, int round_req, hipStream_t q)
+      : hd(h), payload((char*)blob + sizeof(mhpc_snap::Header) + (size_t)h.n_entries * h.entry_bytes),
+        entries(ent), R_req(round_req), t(q) {}
+  CopySide stage(void* buf) const {
+    return snap_side(buf, R, (int)hd.NK, (int)hd.nslot, (int)hd.nbk, (int)hd.spmax);
+  }
+  hipError_t prepare(Handle* d, const int32_t* dp, int n_) override {
+    n = n_;
+    auto entry = [&](int i) { return entries ? entries[i] : i; };
+    for (int i = 0; i < n; ++i) uniq.push_back(entry(i));
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    const int nu = (int)uniq.size();
+    R = R_req > 0 ? std::min(R_req, nu) : mhpc_snap::default_round(hd.payload_entry_bytes, kSnapStageCap, nu);
+    rounds = mhpc_snap::n_rounds(nu, R);
+    cd = copy_side(d);
+    const CopySide cstage = stage(nullptr);
+    nblk = copy_block_table(cstage, cd, nullptr);
+    // the pairs (staging record, destination problem) round by round, then the block table
+    std::vector<int> lists;
+    lists.reserve(2 * (size_t)n + nblk);
+    first.assign(rounds, 0);
+    count.assign(rounds, 0);
+    for (int r = 0; r < rounds; ++r) {
+      first[r] = (int)lists.size() / 2;
+      for (int i = 0; i < n; ++i) {
+        const int u = (int)(std::lower_bound(uniq.begin(), uniq.end(), entry(i)) - uniq.begin());
+        if (u / R != r) continue;
+        lists.push_back(u % R);
+        lists.push_back(dp[i]);
+      }
+      count[r] = (int)lists.size() / 2 - first[r];
+    }
+    lists.resize(2 * (size_t)n + nblk);
+    copy_block_table(cstage, cd, lists.data() + 2 * (size_t)n);
+    dlists = t.in(std::move(lists));
+    if (t.e == hipSuccess)
+      t.e = st.alloc(snap_stage_bytes(R, (int)hd.NK, (int)hd.nslot, (int)hd.nbk, (int)hd.spmax), rounds);
+    if (t.e == hipSuccess) t.e = hipStreamSynchronize(d->stream);  // the lists are up before stream2 reads them
+    return t.e;
+  }
+  hipError_t run(Handle* d, float* ms) override {
+    hipError_t e = hipSuccess;
+    for (int r = 0; e == hipSuccess && r < rounds; ++r) {
+      int u0, cnt;
+      mhpc_snap::round_of((int)uniq.size(), R, r, &u0, &cnt);
+      const hipStream_t q = r & 1 ? d->stream2 : d->stream;
+      void* buf = st.buf[r & 1];
+      // consecutive entries of the round travel in one copy per array
+      for (int a = 0; e == hipSuccess && a < cnt;) {
+        int b = a + 1;
+        while (b < cnt && uniq[u0 + b] == uniq[u0 + b - 1] + 1) ++b;
+        e = snap_move(buf, R, (int)hd.NK, (int)hd.nslot, (int)hd.nbk, (int)hd.spmax, payload, (int)hd.n_entries,
+                      uniq[u0 + a], a, b - a, false, q);
+        a = b;
+      }
+      if (e == hipSuccess) e = hipEventRecord(st.ev[2 * (size_t)r], q);
+      if (e == hipSuccess)
+        e = launch_copy_problems(stage(buf), cd, count[r], dlists + 2 * (size_t)first[r], nblk,
+                                 dlists + 2 * (size_t)n, q);
+      if (e == hipSuccess) e = hipEventRecord(st.ev[2 * (size_t)r + 1], q);
+    }
+    // after an error nothing more was queued; either way both streams are idle from here
+    for (hipStream_t q : {d->stream2, d->stream}) {
+      const hipError_t s = hipStreamSynchronize(q);
+      if (e == hipSuccess) e = s;
+    }
+    if (e == hipSuccess) e = st.elapsed(rounds, ms);
+    return e;
+  }
+};
+
+int api_restore_problems(Handle* d, int n, const int32_t* dp, const void* blob, int64_t bytes,
+                         const int32_t* entries, float* ms) {
+  if (!d || !dp) return fail(MHPC_ERR_INVALID, "null argument");
+  mhpc_snap::Header hd;
+  if (int rc = snap_open(blob, bytes, &hd)) return rc;
+  ProblemList dst;
+  PLANCHK(dst.begin, n, d->sp.B, true);
+  for (int i = 0; i < n; ++i) {
+    const int e = entries ? entries[i] : i;
+    if (e < 0 || e >= (int)hd.n_entries) return fail(MHPC_ERR_INVALID, "snapshot entry out of range");
+    PLANCHK(dst.add, dp[i]);
+  }
+  double alpha;
+  memcpy(&alpha, &hd.alpha_bits, sizeof alpha);
+  CopySource src{"mhpc_restore_problems", true, alpha, (int)hd.nslot, (int)hd.x0_row, hd.sweep32 != 0,
+                 true, false, hd.need_full != 0, hd.solved != 0, hd.spmax > 0, {}};
+  src.p.resize(n);
+  const char* ent = (const char*)blob + sizeof hd;
+  for (int i = 0; i < n; ++i)
+    memcpy(&src.p[i], ent + (size_t)(entries ? entries[i] : i) * sizeof(SrcProblem), sizeof(SrcProblem));
+  // (the entries passed the checksum, but a descriptor is still checked like a caller's)
+  for (int i = 0; i < n; ++i) {
+    PLANCHK(check_desc, &src.p[i].pl.desc);
+    const mhpc_problem_desc& q = src.p[i].pl.desc;
+    int nk = 0;
+    for (int p = 0; p < q.n_wb + q.n_fb; ++p) nk += q.N[p];
+    if (nk > (int)hd.NK) return fail(MHPC_ERR_INVALID, "snapshot entry longer than the blob's knot stride");
+  }
+  BlobMover mv(hd, blob, entries, d->snap_round_req, d->stream);
+  return copy_into(d, dp, n, src, mv, ms);
+}
+
+// Entry `entry` of a blob, on the host alone.
+int api_snapshot_entry(const void* blob, int64_t bytes, int entry, mhpc_problem_desc* desc,
+                       mhpc_hsddp_option* option, mhpc_cost_weights* w, mhpc_constraint_params* c) {
+  mhpc_snap::Header hd;
+  if (int rc = snap_open(blob, bytes, &hd)) return rc;
+  if (entry < 0 || entry >= (int)hd.n_entries) return fail(MHPC_ERR_INVALID, "snapshot entry out of range");
+  SrcProblem q;
+  memcpy(&q, (const char*)blob + sizeof hd + (size_t)entry * sizeof q, sizeof q);
+  if (desc) {
+    *desc = q.pl.desc;
+    desc->vel_cmd = q.cmd[0];
+    desc->height_cmd = q.cmd[1];
+  }
+  if (option) *option = q.opt;
+  if (w) get_weights(q.cw, *w);
+  if (c) get_constraints(q.cw, *c);
+  return MHPC_OK;
+}
+// ProbState::status of entries [first, first + count), from the payload.
+int api_snapshot_status(const void* blob, int64_t bytes, int first, int count, int32_t* status) {
+  if (!status) return fail(MHPC_ERR_INVALID, "null argument");
+  mhpc_snap::Header hd;
+  if (int rc = snap_open(blob, bytes, &hd)) return rc;
+  if (first < 0 || count < 1 || first > (int)hd.n_entries - count)
+    return fail(MHPC_ERR_INVALID, "snapshot entry out of range");
+  const char* st = (const char*)blob + sizeof hd + (size_t)hd.n_entries * sizeof(SrcProblem) +
+                   mhpc_snap::payload_off(mhpc_snap::dims_of(hd), snap_sizes(), mhpc_copy::A_ST, hd.n_entries);
+  for (int i = 0; i < count; ++i) {
+    ProbState s;
+    memcpy(&s, st + (size_t)(first + i) * sizeof s, sizeof s);
+    status[i] = s.status;
+  }
   return MHPC_OK;
 }
 
@@ -2208,6 +2629,11 @@ int api_set_kernel_variant(Handle* h, int which, int variant) {
     if (variant != 0 && variant != 64 && !(variant == 32 && sizeof(real) == 4))
       return fail(MHPC_ERR_INVALID, "sweep arithmetic must be 0 / 64 (double), or 32 (float) in an fp32 handle");
     h->sweep_bits = variant;
+    return MHPC_OK;
+  }
+  if (which == MHPC_VARIANT_SNAP_ROUND) {
+    if (variant < 0) return fail(MHPC_ERR_INVALID, "the snapshot round must be >= 1 problem, or 0");
+    h->snap_round_req = variant;
     return MHPC_OK;
   }
   if (which == MHPC_VARIANT_SUBBATCH) {

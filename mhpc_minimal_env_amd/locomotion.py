@@ -213,6 +213,58 @@ def random_x0(batch: int, seed: int = X0_SEED, offset: int = 0) -> np.ndarray:
     return out
 
 
+def _blob_array(blob) -> np.ndarray:
+    """A snapshot blob (bytes-like or numpy uint8) as a contiguous 1-d uint8 array."""
+    if isinstance(blob, np.ndarray):
+        a = np.ascontiguousarray(blob).reshape(-1)
+        if a.dtype != np.uint8:
+            raise ValueError("a snapshot blob is uint8")
+        return a
+    return np.frombuffer(blob, dtype=np.uint8)
+
+
+def snapshot_status(blob, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+    """mhpc_snapshot_status: the solve status of entries [first, first + count) (None: to the last)
+    as their last solve left it.  No handle, no GPU."""
+    a = _blob_array(blob)
+    if count is None:
+        count = snapshot_info(a)["n_entries"] - first
+    st = np.zeros(count, dtype=np.int32)
+    capi.check(capi.lib().mhpc_snapshot_status(a.ctypes.data, int(a.size), int(first), int(count),
+                                               capi.iptr(st)), "mhpc_snapshot_status")
+    return st
+
+
+def snapshot_info(blob) -> dict:
+    """mhpc_snapshot_info: what the blob's header says (format version, entry count, precision,
+    alpha, sweep arithmetic, x0 row width, knot stride, store shape, payload bytes per entry, the
+    source's point of the call order).  Host memory only: no handle, no GPU."""
+    import ctypes
+    a = _blob_array(blob)
+    info = capi.SnapshotInfo()
+    capi.check(capi.lib().mhpc_snapshot_info(a.ctypes.data, int(a.size), ctypes.byref(info)),
+               "mhpc_snapshot_info")
+    return info.as_dict()
+
+
+def snapshot_entry(blob, i: int) -> dict:
+    """mhpc_snapshot_entry: entry i's descriptor (with its command), option record, cost weights
+    and constraint parameters, and the status its last solve left.  No handle, no GPU."""
+    import ctypes
+    a = _blob_array(blob)
+    d, o, w, c = capi.ProblemDesc(), capi.HsddpOption(), capi.CostWeights(), capi.ConstraintParams()
+    capi.check(capi.lib().mhpc_snapshot_entry(a.ctypes.data, int(a.size), int(i), ctypes.byref(d),
+                                              ctypes.byref(o), ctypes.byref(w), ctypes.byref(c)),
+               "mhpc_snapshot_entry")
+    return {"desc": d, "option": HSDDP_OPTION.from_c(o), "weights": w, "constraints": c,
+            "status": int(snapshot_status(a, i, 1)[0])}
+
+
+def load_snapshot(path) -> np.ndarray:
+    """A snapshot file (save_problems) as a numpy uint8 array."""
+    return np.fromfile(path, dtype=np.uint8)
+
+
 # ----------------------------------------------------------------------------------------
 class SinglePhaseView:
     """One phase of the batch after a solve, with the public members of the reference's
@@ -470,6 +522,126 @@ class MHPCLocomotion:
         self.status[dp] = src.status[sp]
         self._refresh_descs()
         return float(ms.value)
+
+    # -- snapshots of live problems: checkpoints, migration between ranks, replays ---------------
+    def _problem_list(self, problems) -> np.ndarray:
+        if problems is None:
+            return np.arange(self.batch, dtype=np.int32)
+        return np.ascontiguousarray(problems, dtype=np.int32).reshape(-1)
+
+    def snapshot_size(self, problems=None) -> int:
+        """mhpc_snapshot_size: the exact blob size of a snapshot of the listed problems."""
+        import ctypes
+        pr = self._problem_list(problems)
+        n = ctypes.c_int64(0)
+        capi.check(capi.lib().mhpc_snapshot_size(self._h, int(pr.size), capi.iptr(pr),
+                                                 ctypes.byref(n)), "mhpc_snapshot_size")
+        return int(n.value)
+
+    def snapshot_problems(self, problems=None, out=None) -> np.ndarray:
+        """mhpc_snapshot_problems: the listed problems (None: all) as they stand, serialised into a
+        blob of plain bytes -- everything copy_problems carries, to be restored into this or any
+        other handle, in this process or another (restore_problems, from_snapshot).  Returns a
+        numpy uint8 array; out: a caller's contiguous uint8 buffer of at least snapshot_size()
+        bytes (for example a pinned torch tensor's numpy view), whose leading part is returned.
+        self.last_snapshot_ms is the device time of the pack launches."""
+        import ctypes
+        pr = self._problem_list(problems)
+        size = self.snapshot_size(pr)
+        if out is None:
+            out = np.empty(size, dtype=np.uint8)
+        if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.ndim == 1
+                and out.flags.c_contiguous and out.flags.writeable):
+            raise ValueError("out must be a writeable contiguous 1-d numpy uint8 array")
+        ms = ctypes.c_float(0.0)
+        capi.check(capi.lib().mhpc_snapshot_problems(self._h, int(pr.size), capi.iptr(pr),
+                                                     out.ctypes.data, int(out.size), ctypes.byref(ms)),
+                   "mhpc_snapshot_problems")
+        self.last_snapshot_ms = float(ms.value)
+        return out[:size]
+
+    def restore_problems(self, dst_problems, blob, entries=None) -> float:
+        """mhpc_restore_problems: problem dst_problems[i] of this handle becomes entry entries[i]
+        (None: entry i) of the snapshot `blob` -- the copy_problems that could have been made at the
+        moment of the snapshot.  An entry may repeat.  A restore that lists every problem of the
+        handle also adopts the blob's point of the call order (resume from a checkpoint).  Returns
+        the device time of the unpack launches in ms."""
+        import ctypes
+        dp = np.ascontiguousarray(dst_problems, dtype=np.int32).reshape(-1)
+        en = None
+        if entries is not None:
+            en = np.ascontiguousarray(entries, dtype=np.int32).reshape(-1)
+            if en.shape != dp.shape:
+                raise ValueError("one blob entry per destination problem")
+        a = _blob_array(blob)
+        ms = ctypes.c_float(0.0)
+        capi.check(capi.lib().mhpc_restore_problems(self._h, int(dp.size), capi.iptr(dp),
+                                                    a.ctypes.data, int(a.size), capi.iptr(en),
+                                                    ctypes.byref(ms)), "mhpc_restore_problems")
+        # the host mirrors follow, as after copy_problems
+        if not self._x0_on_device:
+            self._x0 = self._x0.copy()
+            self._x0[dp] = self.get_x0()[dp]
+        self.status[dp] = snapshot_status(a)[np.arange(dp.size) if en is None else en]
+        self._refresh_descs()
+        self.option = self.get_options()
+        return float(ms.value)
+
+    def save_problems(self, path, problems=None) -> int:
+        """snapshot_problems written to a file; returns its size in bytes."""
+        blob = self.snapshot_problems(problems)
+        with open(path, "wb") as f:
+            f.write(blob.tobytes())
+        return int(blob.size)
+
+    @classmethod
+    def from_snapshot(cls, blob, device: int = 0, batch: Optional[int] = None,
+                      gait: Optional[Gait] = None) -> "MHPCLocomotion":
+        """A handle that can hold `blob` and holds it: created with the entries' descriptors
+        (set_layouts), their longest layout as reserve_knots, the blob's alpha, precision and sweep
+        arithmetic and the distinct option records (set_option_sets); then initialised and every
+        entry restored into problems 0..n-1.  batch None: the entry count, so the restore covers
+        the handle and it resumes at the blob's point of the call order; a larger batch leaves the
+        other problems as initialization() made them.  gait: what update_problem() steps with (a
+        blob holds gait points, not gaits)."""
+        a = _blob_array(blob)
+        info = snapshot_info(a)
+        n = info["n_entries"]
+        ents = [snapshot_entry(a, i) for i in range(n)]
+        B = n if batch is None else int(batch)
+        if B < n:
+            raise ValueError("batch smaller than the blob's entry count")
+        descs, lop, key_of = [], [], {}
+        for e in ents:  # one handle-wide command in the descriptors: the entries' own travel with them
+            d = capi.ProblemDesc.from_buffer_copy(bytes(e["desc"]))
+            d.vel_cmd, d.height_cmd = ents[0]["desc"].vel_cmd, ents[0]["desc"].height_cmd
+            k = bytes(d)
+            if k not in key_of:
+                key_of[k] = len(descs)
+                descs.append(d)
+            lop.append(key_of[k])
+        lop += [0] * (B - n)
+        opts, oop = [], []
+        for e in ents:
+            if e["option"] not in opts:
+                opts.append(e["option"])
+            oop.append(opts.index(e["option"]))
+        oop += [0] * (B - n)
+        loco = cls(desc=descs[0], gait=gait, option=opts[0], batch=B, device=device)
+        try:
+            if info["sweep_bits"] == 32:
+                loco.set_kernel_variant(sweep_bits=32)
+            if len(descs) > 1:
+                loco.set_layouts(descs, lop)
+            loco.reserve_knots(info["knot_stride"])
+            if len(opts) > 1:
+                loco.set_option_sets(opts, oop)
+            loco.initialization()
+            loco.restore_problems(np.arange(n, dtype=np.int32), a)
+        except Exception:
+            loco.close()
+            raise
+        return loco
 
     def lost_problems(self) -> np.ndarray:
         """Problems whose last solve did not end MHPC_SOLVE_OK or left a non-finite cost."""
@@ -929,14 +1101,20 @@ class MHPCLocomotion:
         capi.check(capi.lib().mhpc_reset_kernel_stats(self._h), "mhpc_reset_kernel_stats")
 
     def set_kernel_variant(self, bws: str = "auto", rollout: str = "auto", overlap: str = "auto",
-                           sub_batches: int = 0, ro_store: int = 0, sweep_bits: int = 0):
+                           sub_batches: int = 0, ro_store: int = 0, sweep_bits: int = 0,
+                           snap_round: Optional[int] = None):
         """Pin the backward-sweep / line-search launch variant, the partials / sweep
         overlap, the number of concurrently scheduled sub-batches and the number of
         line-search trials that store their knot records (mhpc_set_kernel_variant); names in
         capi.BWS_VARIANTS / capi.RO_VARIANTS / capi.OVERLAP_VARIANTS, "auto" / 0 = chosen by
         batch size and phase layout (ro_store 0: the default).  sweep_bits: arithmetic of the
-        backward sweep, 0 / 64 double (default), 32 float (fp32 handles only)."""
+        backward sweep, 0 / 64 double (default), 32 float (fp32 handles only).  snap_round:
+        problems a round of snapshot_problems / restore_problems (0: by the staging cap; None:
+        unchanged)."""
         L = capi.lib()
+        if snap_round is not None:
+            capi.check(L.mhpc_set_kernel_variant(self._h, capi.MHPC_VARIANT_SNAP_ROUND,
+                                                 int(snap_round)), "mhpc_set_kernel_variant")
         if sweep_bits or getattr(self, "_sweep_bits_pinned", False):
             capi.check(L.mhpc_set_kernel_variant(self._h, capi.MHPC_VARIANT_SWEEP_BITS,
                                                  int(sweep_bits)), "mhpc_set_kernel_variant")

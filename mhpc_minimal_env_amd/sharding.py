@@ -62,3 +62,40 @@ def gather_summaries(local: np.ndarray, device=None) -> np.ndarray:
              for o, s in zip(outs, sizes)]
     allp = np.concatenate(parts)
     return allp[np.argsort(allp["index"], kind="stable")]
+
+
+def _gather_bytes(raw: np.ndarray, device=None):
+    """The byte strings of every rank, by rank: sizes first, then one padded byte all-gather."""
+    import torch
+    import torch.distributed as dist
+    world = dist.get_world_size()
+    n = torch.tensor([raw.size], dtype=torch.int64, device=device)
+    sizes = [torch.zeros_like(n) for _ in range(world)]
+    dist.all_gather(sizes, n)
+    cap = max(1, int(max(int(s.item()) for s in sizes)))
+    buf = torch.zeros(cap, dtype=torch.uint8, device=device)
+    buf[:raw.size] = torch.from_numpy(raw.copy()).to(buf.device)
+    outs = [torch.zeros(cap, dtype=torch.uint8, device=device) for _ in range(world)]
+    dist.all_gather(outs, buf)
+    return [o[:int(s.item())].cpu().numpy().tobytes() for o, s in zip(outs, sizes)]
+
+
+def exchange_bytes(outgoing, device=None):
+    """Every rank hands every rank a byte string: outgoing[r] goes to rank r (possibly empty;
+    outgoing[own rank] comes back as it is).  Returns the strings received, by sender.  What
+    carries snapshot blobs (MHPCLocomotion.snapshot_problems) between ranks when robots move:
+    the same size-first byte all-gather as gather_summaries, each rank's message being its
+    per-receiver lengths followed by the strings, of which a receiver keeps its own."""
+    import torch.distributed as dist
+    world, rank = dist.get_world_size(), dist.get_rank()
+    if len(outgoing) != world:
+        raise ValueError("outgoing needs one byte string per rank")
+    parts = [bytes(p) for p in outgoing]
+    head = np.array([len(p) for p in parts], dtype=np.int64).tobytes()
+    msgs = _gather_bytes(np.frombuffer(head + b"".join(parts), dtype=np.uint8), device)
+    got = []
+    for m in msgs:
+        lens = np.frombuffer(m[:8 * world], dtype=np.int64)
+        start = 8 * world + int(lens[:rank].sum())
+        got.append(m[start:start + int(lens[rank])])
+    return got
