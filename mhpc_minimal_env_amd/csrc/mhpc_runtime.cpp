@@ -13,6 +13,7 @@
 
 #include "../../include/mhpc_capi.h"
 #include "mhpc_control_map.h"
+#include "mhpc_devres.h"
 #include "mhpc_devtemp.h"
 #include "mhpc_launch.h"
 #include "mhpc_plan.h"
@@ -64,23 +65,44 @@ static const char* kKernelNames[NKERN] = {"k_init", "k_cost(forward_sweep0)", "k
                                           "k_partials", "k_bws", "k_al_end", "k_bws_srb"};
 
 struct Handle {
+  // What the handle owns on the device (mhpc_devres.h), mirrored by tests/native/devres_hostcheck.cpp.
+  // ~Handle releases from the last member to the first, and that order is kept: device memory
+  // first (mhpc_destroy has drained every stream), in the order the arrays were always freed; then
+  // the events, each before the streams it was recorded on; the main stream last.
+  StreamSet main;  // s1: the handle's stream; the partials run on s2 / s3 beside the SRB sweep
+  Event evstart;   // sub-batches (MHPC_VARIANT_SUBBATCH): each block on a set of its own (first use)
+  std::vector<StreamSet> subs;
+  Event ev0, ev1;
+  std::vector<Event> evpool;  // profiling: one event pair per launch of a solve (evkind)
+  // at first use: the event that orders the handle's stream behind a caller's (control I/O), and
+  // those around a whole mhpc_tick_problems (ev0 / ev1 bracket its solve schedule)
+  Event evctl, evt0, evt1;
+  // the control steps [B] (first call with steps), the split order [B] of a mixed first op, the
+  // buffer store [B][spmax][nbk] (first update), the reduced counters per group [MAXL][NCNT]
+  DevArray<int> dstep, dsplit;
+  DevArray<real> store;
+  DevArray<unsigned long long> dcnt;
+  struct Arrays {  // behind the views of d (set_views)
+    DevArray<int> oid;
+    DevArray<OptRec> opt;  // [MAXO]
+    DevArray<Cmd> cmd;
+    DevArray<int> lid, gidx;
+    DevArray<Group> grp;  // [MAXL]
+    DevArray<BwsCarry> carry;
+    DevArray<real> out;
+    DevArray<ProbState> st;
+    DevArray<real> x0, px, par, G, du, K, refpos, traj;
+  } own;
+
   mhpc_problem_desc desc;  // the descriptor of mhpc_create (precision, vel, height)
   mhpc_hsddp_option opt;   // the option of mhpc_create: its alpha is the handle's line-search grid
   // option sets (mhpc_set_option_sets): the table of distinct records in use with each problem's
-  // slot by problem number (mhpc_plan.h, OptTable); the device copies dopt [MAXO] (OptRec) and
-  // doid [B].  otab.rec[otab.of[0]] is what mhpc_get_options reports.
+  // slot by problem number (mhpc_plan.h, OptTable); the device copies own.opt and own.oid.
+  // otab.rec[otab.of[0]] is what mhpc_get_options reports.
   OptTable otab;
-  OptRec* dopt = nullptr;
-  int* doid = nullptr;
   int device = 0;
   SolveParams sp;
-  DevBufs d;
-  hipStream_t stream = nullptr;
-  // second stream: the partials run there beside the SRB half of the backward sweep
-  // (fork / join events order it against the main stream)
-  hipStream_t stream2 = nullptr, stream3 = nullptr;  // stream3: the partials' second group
-  hipEvent_t evfork = nullptr, evjoin = nullptr, evpfork = nullptr, evpjoin = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevBufs d;  // the arrays as the kernels receive them: views of `own`
   bool x0_set = false, initialized = false, solved = false, x0_changed = false;
   // constraint parameters replaced after the last initialize / update_problem: their AL / ReB
   // initial values reach the problems' state only there, so a solve in between
@@ -101,57 +123,33 @@ struct Handle {
   std::vector<int> pset_of;
   bool sets_changed = false;
   float solve_ms = 0;
-  unsigned long long* dcnt = nullptr;  // reduced counters per group [MAXL][NCNT]
-  unsigned long long cnt[NCNT] = {};   // their sum over the groups
+  unsigned long long cnt[NCNT] = {};  // the reduced counters' sum over the groups
   unsigned long long gcnt[MAXL][NCNT] = {};
-  // profiling: one event pair per launch of a solve, accumulated per kernel id
+  // profiling: the event pairs of evpool, accumulated per kernel id
   bool profile = false;
-  std::vector<hipEvent_t> evpool;
   std::vector<int> evkind;
   double kms[NKERN] = {}, kbytes[NKERN] = {}, kflops[NKERN] = {};
   int64_t klaunch[NKERN] = {};
   // per-problem layouts, and the plan installed from them and the parameter sets (plan_groups,
   // mhpc_plan.h; commit_groups): each group's layout, descriptor, byte model and set, each
-  // problem's group, the problems grouped.  The device copies: dgrp, dlid, dgidx.
+  // problem's group, the problems grouped.  The device copies: own.grp, own.lid, own.gidx.
   std::vector<ProbLayout> pl;
   GroupPlan plan;
-  Group* dgrp = nullptr;  // device group table [MAXL]
-  int *dgidx = nullptr, *dlid = nullptr;
-  Cmd* dcmd = nullptr;
   // receding horizon (MHPCLocomotion::update_problem): each problem's current mode, the
-  // buffer store [B][spmax][nbk] (allocated at the first update), knot capacity of the
-  // packed arrays, and whether the next solve's first forward_sweep(0) must be a real
-  // rollout (rotated nominal, new x0)
+  // shape of the buffer store, knot capacity of the packed arrays, and whether the next solve's
+  // first forward_sweep(0) must be a real rollout (rotated nominal, new x0)
   std::vector<int> cmode;
-  real* store = nullptr;
   int nbk = 0, nk_cap = 0, spmax = 0;
   int nk_floor = 0;  // mhpc_reserve_knots: floor of the knot stride wherever it may change
   bool need_full = false;
   bool store_valid = false;  // store zeroed since the last initialize (memory_reset)
-  // dsplit [B]: the grouped order split for the first op of a solve that starts with the real
-  // rollout (need_full) while the ledger has fresh problems: the others first, then the fresh ones
-  int* dsplit = nullptr;
-  // sub-batches (MHPC_VARIANT_SUBBATCH): the solve schedule runs once per contiguous block of
-  // problems, each block on its own stream pair; created on first use
-  int nsub_req = 0;
+  // (dsplit: the grouped order of a solve that starts with the real rollout (need_full) while the
+  // ledger has fresh problems, split for its first op: the others first, then the fresh ones)
+  int nsub_req = 0;  // MHPC_VARIANT_SUBBATCH: the schedule runs once per contiguous block of problems
   int ro_store_req = 0;  // MHPC_VARIANT_RO_STORE (0: by the batch's line-search shape)
   int sweep_bits = 0;    // MHPC_VARIANT_SWEEP_BITS (0 = 64: the sweep computes in double)
   int snap_round_req = 0;  // MHPC_VARIANT_SNAP_ROUND (0: as many problems as fit the staging cap)
-  struct SubStreams {
-    hipStream_t s1 = nullptr, s2 = nullptr, s3 = nullptr;  // s3: the partials' second group
-    hipEvent_t fork = nullptr, join = nullptr, gate = nullptr, done = nullptr, pfork = nullptr,
-               pjoin = nullptr;
-  };
-  std::vector<SubStreams> subs;
-  hipEvent_t evstart = nullptr;
-  // control I/O (mhpc_control*, mhpc_set_x0_device): the problems' control steps on the device
-  // [B] with the host copy the upload reads, and the event that orders the handle's stream behind
-  // the caller's; all created at the first call that needs them
-  int* dstep = nullptr;
-  std::vector<int> hstep;
-  hipEvent_t evctl = nullptr;
-  // mhpc_tick_problems: the events around the whole tick (ev0 / ev1 bracket its solve schedule)
-  hipEvent_t evt0 = nullptr, evt1 = nullptr;
+  std::vector<int> hstep;  // the host copy of dstep that its upload reads
 };
 
 // backward sweep: per WB knot partials record + x,u,y + refpos read, K,du,G written;
@@ -172,18 +170,21 @@ const char* api_kernel_name(int k) {
 }
 
 
-static void free_bufs(Handle* h) {
-  DevBufs& d = h->d;
-  void* ptrs[] = {d.traj, d.refpos, d.K, d.du, d.G, d.par, d.px, d.x0, d.st, d.out, d.carry,
-                  h->dgrp, h->dgidx, h->dlid, h->dcmd, h->dopt, h->doid};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  memset(&d, 0, sizeof d);
-  h->dgrp = nullptr;
-  h->dgidx = h->dlid = nullptr;
-  h->dcmd = nullptr;
-  h->dopt = nullptr;
-  h->doid = nullptr;
+// The one place where d gets its pointers: called wherever an array of `own` is (re)allocated.
+static void set_views(Handle* h) {
+  const Handle::Arrays& a = h->own;
+  h->d = DevBufs{a.traj.get(), a.refpos.get(), a.K.get(),    a.du.get(),   a.G.get(),   a.par.get(),
+                 a.px.get(),   a.x0.get(),     a.st.get(),   a.out.get(),  a.carry.get(), a.grp.get(),
+                 a.gidx.get(), a.lid.get(),    a.cmd.get(),  a.opt.get(),  a.oid.get()};
+}
+// Every stream of the handle drained, the main set and each sub-batch's; the first error.
+static hipError_t sync_streams(const Handle* h) {
+  hipError_t e = h->main.sync();
+  for (const StreamSet& s : h->subs) {
+    const hipError_t e1 = s.sync();
+    if (e == hipSuccess) e = e1;
+  }
+  return e;
 }
 
 // The packed per-knot arrays for a knot stride of NK (grown, never shrunk: their content is
@@ -193,38 +194,24 @@ static void free_bufs(Handle* h) {
 // stride used for other columns.  New arrays are allocated before the old ones are freed, so
 // a failed allocation leaves the handle's arrays and stride as they were.
 static int ensure_knot_arrays(Handle* h, int NK) {
-  DevBufs& d = h->d;
+  const DevBufs& d = h->d;
   const size_t B = h->sp.B, nk = NK;
   const bool grow = NK > h->nk_cap;
   if (!grow && NK == h->sp.NK) return MHPC_OK;
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream2));
-  HIPCHK(hipStreamSynchronize(h->stream3));
-  for (const Handle::SubStreams& s : h->subs) {
-    if (s.s1) HIPCHK(hipStreamSynchronize(s.s1));
-    if (s.s2) HIPCHK(hipStreamSynchronize(s.s2));
-    if (s.s3) HIPCHK(hipStreamSynchronize(s.s3));
-  }
+  HIPCHK(sync_streams(h));
   if (grow) {
-    real** arr[] = {&d.traj, &d.refpos, &d.K, &d.du, &d.G, &d.par, &d.out};
-    const size_t per[] = {(size_t)h->sp.nslot * KS, 1, 56, 4, 14, PS, KS};
-    real* fresh[7] = {};
-    for (int i = 0; i < 7; ++i) {
-      const hipError_t e = hipMalloc((void**)&fresh[i], B * nk * per[i] * sizeof(real));
-      if (e != hipSuccess) {
-        for (int j = 0; j < i; ++j) (void)hipFree(fresh[j]);
-        return fail(MHPC_ERR_DEVICE, std::string("knot array allocation failed: ") + hipGetErrorString(e));
-      }
-    }
-    for (int i = 0; i < 7; ++i) {
-      if (*arr[i]) (void)hipFree(*arr[i]);
-      *arr[i] = fresh[i];
-    }
+    Handle::Arrays& a = h->own;
+    DevArray<real>* const arr[] = {&a.traj, &a.refpos, &a.K, &a.du, &a.G, &a.par, &a.out};
+    const size_t n = B * nk;
+    const size_t count[] = {n * h->sp.nslot * KS, n, n * 56, n * 4, n * 14, n * PS, n * KS};
+    if (const hipError_t e = grow_and_swap(arr, count))
+      return fail(MHPC_ERR_DEVICE, std::string("knot array allocation failed: ") + hipGetErrorString(e));
+    set_views(h);
     h->nk_cap = NK;
-    HIPCHK(hipMemsetAsync(d.traj, 0, B * h->sp.nslot * nk * KS * sizeof(real), h->stream));
+    HIPCHK(hipMemsetAsync(d.traj, 0, B * h->sp.nslot * nk * KS * sizeof(real), h->main.s1));
   }
-  HIPCHK(hipMemsetAsync(d.par, 0, B * nk * PS * sizeof(real), h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemsetAsync(d.par, 0, B * nk * PS * sizeof(real), h->main.s1));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   return MHPC_OK;
 }
 
@@ -233,18 +220,18 @@ static int upload_params(Handle* h) {
   std::vector<Group> t(h->plan.gset.size());
   for (size_t g = 0; g < t.size(); ++g) t[g] = Group{h->plan.lays[g], h->psets[h->plan.gset[g]]};
   h->sp.cw = h->psets[h->pset_of[0]];  // k_init's copy (problem 0's set)
-  HIPCHK(hipMemcpyAsync(h->dgrp, t.data(), t.size() * sizeof(Group), hipMemcpyHostToDevice,
-                        h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpyAsync(h->own.grp.get(), t.data(), t.size() * sizeof(Group), hipMemcpyHostToDevice,
+                        h->main.s1));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   return MHPC_OK;
 }
 
 // The installed plan's grouped order, each problem's group and the group table to the device.
 static int upload_plan(Handle* h) {
   const size_t B = h->sp.B;
-  HIPCHK(hipMemcpyAsync(h->dgidx, h->plan.gidx.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->dlid, h->plan.lid.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpyAsync(h->own.gidx.get(), h->plan.gidx.data(), B * sizeof(int), hipMemcpyHostToDevice, h->main.s1));
+  HIPCHK(hipMemcpyAsync(h->own.lid.get(), h->plan.lid.data(), B * sizeof(int), hipMemcpyHostToDevice, h->main.s1));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   return upload_params(h);
 }
 
@@ -260,8 +247,8 @@ static int upload_options(Handle* h) {
   std::vector<OptRec> t(h->otab.rec.size());
   for (size_t s = 0; s < t.size(); ++s) t[s] = option_record(h->otab.rec[s]);
   mirror_option0(h);
-  HIPCHK(hipMemcpyAsync(h->dopt, t.data(), t.size() * sizeof(OptRec), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpyAsync(h->own.opt.get(), t.data(), t.size() * sizeof(OptRec), hipMemcpyHostToDevice, h->main.s1));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   return MHPC_OK;
 }
 // More than one parameter set or option set: k_init wrote problem 0's values for every problem and
@@ -477,7 +464,7 @@ int api_set_param_sets(Handle* h, int n_sets, const mhpc_cost_weights* w,
     changed = !same_params(ns[nof[b]], h->psets[h->pset_of[b]]);
   if (!changed) return MHPC_OK;  // nothing changes: nothing pending
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   GroupPlan plan;
   PLANCHK(plan_groups, h->pl, nof, plan);  // too many (layout, set) pairs: the old sets stay
   // (the knot stride stays as in apply_sets: the records of an initialised handle are live)
@@ -529,8 +516,8 @@ int api_set_option_sets(Handle* h, int n_sets, const mhpc_hsddp_option* sets, co
     ent[2 * i + 1] = nt.of[changed[i]];
   }
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  DevTemp<int> ti(h->stream);
+  HIPCHK(hipStreamSynchronize(h->main.s1));
+  DevTemp<int> ti(h->main.s1);
   const int* dent = ti.in(std::move(ent));
   if (ti.e != hipSuccess) return dev_fail("mhpc_set_option_sets", ti.e);
   // ---- nothing of the handle or the device has changed up to here ----
@@ -543,8 +530,8 @@ int api_set_option_sets(Handle* h, int n_sets, const mhpc_hsddp_option* sets, co
     });
     return rc;
   }
-  hipError_t e = launch_set_options(h->d, h->doid, (int)changed.size(), dent, 1, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  hipError_t e = launch_set_options(h->d, h->own.oid.get(), (int)changed.size(), dent, 1, h->main.s1);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->main.s1);
   if (e != hipSuccess) return dev_fail("mhpc_set_option_sets", e);
   // a problem that now has AL iterations while its SRB nominal is open (Ledger::budget_raised)
   for (int b : changed)
@@ -622,65 +609,54 @@ int api_create(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int 
   DevBufs& d = h->d;
   memset(&d, 0, sizeof d);
   const size_t B = batch;
+  Handle::Arrays& a = h->own;
   hipError_t e = hipSuccess;
-  auto alloc = [&](void** p, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc(p, bytes);
+  auto alloc = [&](auto& arr, size_t n) {
+    if (e == hipSuccess) e = arr.alloc(n);
   };
-  alloc((void**)&d.px, B * MAXP * 196 * sizeof(real));
-  alloc((void**)&d.x0, B * 14 * sizeof(real));
-  alloc((void**)&d.st, B * sizeof(ProbState));
-  alloc((void**)&d.carry, B * sizeof(BwsCarry));
-  alloc((void**)&h->dcnt, MAXL * NCNT * sizeof(unsigned long long));
-  alloc((void**)&h->dgrp, MAXL * sizeof(Group));
-  alloc((void**)&h->dgidx, B * sizeof(int));
-  alloc((void**)&h->dlid, B * sizeof(int));
-  alloc((void**)&h->dsplit, B * sizeof(int));
-  alloc((void**)&h->dopt, MAXO * sizeof(OptRec));
-  alloc((void**)&h->doid, B * sizeof(int));
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->evfork, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->evjoin, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream3, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->evpfork, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->evpjoin, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreate(&h->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&h->ev1);
+  alloc(a.px, B * MAXP * 196);
+  alloc(a.x0, B * 14);
+  alloc(a.st, B);
+  alloc(a.carry, B);
+  alloc(h->dcnt, MAXL * NCNT);
+  alloc(a.grp, MAXL);
+  alloc(a.gidx, B);
+  alloc(a.lid, B);
+  alloc(h->dsplit, B);
+  alloc(a.opt, MAXO);
+  alloc(a.oid, B);
+  set_views(h);
+  if (e == hipSuccess) e = h->main.create(false);
+  if (e == hipSuccess) e = h->ev0.create(EV_TIMING);
+  if (e == hipSuccess) e = h->ev1.create(EV_TIMING);
   // zero x0 on the handle's own (non-blocking) stream: a null-stream memset would not be
   // ordered before mhpc_set_x0's copy on this stream
-  if (e == hipSuccess) e = hipMemsetAsync(d.x0, 0, B * 14 * sizeof(real), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(h->dopt, 0, MAXO * sizeof(OptRec), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(h->doid, 0, B * sizeof(int), h->stream);  // slot 0
+  if (e == hipSuccess) e = hipMemsetAsync(d.x0, 0, B * 14 * sizeof(real), h->main.s1);
+  if (e == hipSuccess) e = hipMemsetAsync(a.opt.get(), 0, MAXO * sizeof(OptRec), h->main.s1);
+  if (e == hipSuccess) e = hipMemsetAsync(a.oid.get(), 0, B * sizeof(int), h->main.s1);  // slot 0
   // every problem starts with the descriptor's command
   h->cmd.resize(2 * B);
   for (size_t b = 0; b < B; ++b) {
     h->cmd[2 * b] = desc->vel_cmd;
     h->cmd[2 * b + 1] = desc->height_cmd;
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->main.s1);
   int rc2 = e == hipSuccess ? MHPC_OK : fail(MHPC_ERR_DEVICE, std::string("allocation failed: ") + hipGetErrorString(e));
+  if (!rc2) rc2 = upload_options(h);
   if (!rc2) {  // one group; allocates the packed arrays
-    d.grp = h->dgrp;
-    d.gidx = h->dgidx;
-    d.lid = h->dlid;
-    d.opt = h->dopt;
-    d.oid = h->doid;
-    rc2 = upload_options(h);
-  }
-  if (!rc2) {
     GroupPlan plan;
     rc2 = plan_groups(h->pl, h->pset_of, plan, nullptr);  // (one layout, one set: never refused)
     if (!rc2) rc2 = commit_groups(h, std::move(plan), false);
   }
   if (!rc2) {  // the command array (after the packed arrays: their placement stays as it was)
     const std::vector<Cmd> hcmd(B, Cmd{(real)desc->vel_cmd, (real)desc->height_cmd});
-    e = hipMalloc((void**)&h->dcmd, B * sizeof(Cmd));
+    e = a.cmd.alloc(B);
+    set_views(h);
     if (e == hipSuccess)
-      e = hipMemcpyAsync(h->dcmd, hcmd.data(), B * sizeof(Cmd), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+      e = hipMemcpyAsync(a.cmd.get(), hcmd.data(), B * sizeof(Cmd), hipMemcpyHostToDevice, h->main.s1);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->main.s1);
     if (e != hipSuccess)
       rc2 = fail(MHPC_ERR_DEVICE, std::string("allocation failed: ") + hipGetErrorString(e));
-    h->d.cmd = h->dcmd;
   }
   if (rc2) {
     api_destroy(h);
@@ -701,8 +677,8 @@ int api_set_x0(Handle* h, const double* x0) {
   HIPCHK(hipSetDevice(h->device));
   const std::vector<real> pad = pack_rows<real>(h->plan, h->sp.B, 1, x0, 0);
   HIPCHK(hipMemcpyAsync(h->d.x0, pad.data(), pad.size() * sizeof(real), hipMemcpyHostToDevice,
-                        h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+                        h->main.s1));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   h->x0_set = true;
   h->x0_changed = true;  // references follow x0 only through initialize / update_problem
   return MHPC_OK;
@@ -710,10 +686,10 @@ int api_set_x0(Handle* h, const double* x0) {
 
 static int mark(Handle* h, int kind, hipStream_t s) {
   if (!h->profile) return MHPC_OK;
-  hipEvent_t e;
-  HIPCHK(hipEventCreate(&e));
+  Event e;  // (appended only once recorded: a failure leaves the pool as it was)
+  HIPCHK(e.create(EV_TIMING));
   HIPCHK(hipEventRecord(e, s));
-  h->evpool.push_back(e);
+  h->evpool.push_back(std::move(e));
   h->evkind.push_back(kind);
   return MHPC_OK;
 }
@@ -726,7 +702,7 @@ static int mark(Handle* h, int kind, hipStream_t s) {
     rc_ = mark(h, -1, s);              \
     if (rc_) return rc_;               \
   } while (0)
-#define LAUNCH(h, kind, expr) LAUNCH_ON(h, kind, h->stream, expr)
+#define LAUNCH(h, kind, expr) LAUNCH_ON(h, kind, h->main.s1, expr)
 
 static int collect_profile(Handle* h) {
   for (size_t i = 0; i + 1 < h->evpool.size(); i += 2) {
@@ -735,7 +711,6 @@ static int collect_profile(Handle* h) {
     h->kms[h->evkind[i]] += ms;
     h->klaunch[h->evkind[i]] += 1;
   }
-  for (hipEvent_t e : h->evpool) (void)hipEventDestroy(e);
   h->evpool.clear();
   h->evkind.clear();
   return MHPC_OK;
@@ -743,8 +718,8 @@ static int collect_profile(Handle* h) {
 
 // Device -> host copy ordered on the handle's stream.
 static int d2h(Handle* h, void* dst, const void* src, size_t bytes) {
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->main.s1));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   return MHPC_OK;
 }
 #define D2H(dst, src, bytes)                \
@@ -770,17 +745,17 @@ static int initialize_async(Handle* h) {
   DevBufs& d = h->d;
   // memory_reset (K / du / G, trajectory tails) on the second stream beside k_init, which
   // touches none of it; the first solve op waits for both
-  HIPCHK(hipEventRecord(h->evfork, h->stream));
-  HIPCHK(hipStreamWaitEvent(h->stream2, h->evfork, 0));
-  HIPCHK(launch_reset_arrays(sp, d, h->stream2));
-  HIPCHK(hipEventRecord(h->evjoin, h->stream2));
-  LAUNCH(h, K_INIT, launch_init(sp, d, h->stream));
+  HIPCHK(hipEventRecord(h->main.fork, h->main.s1));
+  HIPCHK(hipStreamWaitEvent(h->main.s2, h->main.fork, 0));
+  HIPCHK(launch_reset_arrays(sp, d, h->main.s2));
+  HIPCHK(hipEventRecord(h->main.join, h->main.s2));
+  LAUNCH(h, K_INIT, launch_init(sp, d, h->main.s1));
   // (k_init wrote the AL / ReB initial values of problem 0's set for every problem)
   if (own_init_values(h)) {  // its time and bytes (four MAXP-long arrays a problem) count as k_init's
-    LAUNCH(h, K_INIT, launch_init_params(sp, d, 1, h->stream));
+    LAUNCH(h, K_INIT, launch_init_params(sp, d, 1, h->main.s1));
     h->kbytes[K_INIT] += (double)sp.B * 4 * MAXP * kB;
   }
-  HIPCHK(hipStreamWaitEvent(h->stream, h->evjoin, 0));
+  HIPCHK(hipStreamWaitEvent(h->main.s1, h->main.join, 0));
   for (int g = 0; g < sp.ngrp; ++g) h->kbytes[K_INIT] += h->plan.bym[g].init * (sp.go[g + 1] - sp.go[g]);
   // the buffer store is zeroed lazily (first update_problem), so a plain initialize + solve
   // pays nothing for it
@@ -813,7 +788,7 @@ int api_initialize(Handle* h) {
   HIPCHK(hipSetDevice(h->device));
   int rc = initialize_async(h);
   if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   rc = collect_profile(h);
   if (rc) return rc;
   h->initialized = true;
@@ -837,8 +812,7 @@ int api_initialize(Handle* h) {
 struct SolveBlock {
   SolveParams sp;
   DevBufs d;
-  hipStream_t s1, s2, s3;
-  hipEvent_t fork, join, pfork, pjoin;
+  const StreamSet* q = nullptr;  // what it runs on: the handle's main set, or a sub-batch's
   // OP_FULL with fresh problems in the batch (Ledger::fresh): the block's problems split into
   // the rolled-out ones (spf) and the fresh ones (spc, k_cost), both over Handle::dsplit
   bool mixed = false;
@@ -915,6 +889,7 @@ static DevBufs block_bufs(const DevBufs& d, const SolveParams& sp, size_t b0) {
 static int issue_op(Handle* h, const SolveBlock& k, const SolveOp& op) {
   const SolveParams& sp = k.sp;
   const DevBufs& d = k.d;
+  const StreamSet& q = *k.q;
   const bool split = bws_split(sp);
 #ifdef MHPC_FP32
   auto launch_bws = h->sweep_bits == 32 ? fsweep::launch_bws : MHPC_NS::launch_bws;
@@ -923,42 +898,42 @@ static int issue_op(Handle* h, const SolveBlock& k, const SolveOp& op) {
     case OP_FULL:
       if (k.mixed) {
         DevBufs ds = d;
-        ds.gidx = h->dsplit;
+        ds.gidx = h->dsplit.get();
         if (launch_problems(k.spf) > 0)
-          LAUNCH_ON(h, K_FULL, k.s1, launch_rollout(k.spf, ds, op.al, 0, 1, k.s1));
+          LAUNCH_ON(h, K_FULL, q.s1, launch_rollout(k.spf, ds, op.al, 0, 1, q.s1));
         if (launch_problems(k.spc) > 0)
-          LAUNCH_ON(h, K_FULL, k.s1, launch_cost(k.spc, ds, op.al, k.s1));
+          LAUNCH_ON(h, K_FULL, q.s1, launch_cost(k.spc, ds, op.al, q.s1));
         break;
       }
-      LAUNCH_ON(h, K_FULL, k.s1, launch_rollout(sp, d, op.al, 0, 1, k.s1));
+      LAUNCH_ON(h, K_FULL, q.s1, launch_rollout(sp, d, op.al, 0, 1, q.s1));
       break;
     case OP_COST:
-      LAUNCH_ON(h, K_FULL, k.s1, launch_cost(sp, d, op.al, k.s1));
+      LAUNCH_ON(h, K_FULL, q.s1, launch_cost(sp, d, op.al, q.s1));
       break;
     case OP_PAR:
       if (!split) {
-        LAUNCH_ON(h, K_PAR, k.s1, launch_partials(sp, d, op.al, op.ddp, k.s1, k.s3, k.pfork, k.pjoin));
+        LAUNCH_ON(h, K_PAR, q.s1, launch_partials(sp, d, op.al, op.ddp, q.s1, q.s3, q.pfork, q.pjoin));
         break;
       }
-      HIPCHK(hipEventRecord(k.fork, k.s1));
-      HIPCHK(hipStreamWaitEvent(k.s2, k.fork, 0));
-      LAUNCH_ON(h, K_PAR, k.s2, launch_partials(sp, d, op.al, op.ddp, k.s2, k.s3, k.pfork, k.pjoin));
-      HIPCHK(hipEventRecord(k.join, k.s2));
+      HIPCHK(hipEventRecord(q.fork, q.s1));
+      HIPCHK(hipStreamWaitEvent(q.s2, q.fork, 0));
+      LAUNCH_ON(h, K_PAR, q.s2, launch_partials(sp, d, op.al, op.ddp, q.s2, q.s3, q.pfork, q.pjoin));
+      HIPCHK(hipEventRecord(q.join, q.s2));
       break;
     case OP_BWS:
       if (!split) {
-        LAUNCH_ON(h, K_BWS, k.s1, launch_bws(sp, d, op.al, op.ddp, 0, k.s1));
+        LAUNCH_ON(h, K_BWS, q.s1, launch_bws(sp, d, op.al, op.ddp, 0, q.s1));
         break;
       }
-      LAUNCH_ON(h, K_BWS_SRB, k.s1, launch_bws(sp, d, op.al, op.ddp, 1, k.s1));
-      HIPCHK(hipStreamWaitEvent(k.s1, k.join, 0));
-      LAUNCH_ON(h, K_BWS, k.s1, launch_bws(sp, d, op.al, op.ddp, 2, k.s1));
+      LAUNCH_ON(h, K_BWS_SRB, q.s1, launch_bws(sp, d, op.al, op.ddp, 1, q.s1));
+      HIPCHK(hipStreamWaitEvent(q.s1, q.join, 0));
+      LAUNCH_ON(h, K_BWS, q.s1, launch_bws(sp, d, op.al, op.ddp, 2, q.s1));
       break;
     case OP_LS:
-      LAUNCH_ON(h, K_LS, k.s1, launch_rollout(sp, d, op.al, op.ddp, 0, k.s1));
+      LAUNCH_ON(h, K_LS, q.s1, launch_rollout(sp, d, op.al, op.ddp, 0, q.s1));
       break;
     default:
-      LAUNCH_ON(h, K_AL, k.s1, launch_al_end(sp, d, op.al, op.last, k.s1));
+      LAUNCH_ON(h, K_AL, q.s1, launch_al_end(sp, d, op.al, op.last, q.s1));
   }
   return MHPC_OK;
 }
@@ -970,20 +945,8 @@ static int sub_batches(const Handle* h, int problems) {
 }
 
 static int ensure_sub_streams(Handle* h, int n) {
-  if (!h->evstart) HIPCHK(hipEventCreateWithFlags(&h->evstart, hipEventDisableTiming));
-  while ((int)h->subs.size() < n) {
-    h->subs.emplace_back();
-    Handle::SubStreams& s = h->subs.back();
-    HIPCHK(hipStreamCreateWithFlags(&s.s1, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&s.s2, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&s.s3, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&s.pfork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&s.pjoin, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&s.fork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&s.join, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&s.gate, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-  }
+  HIPCHK(h->evstart.ensure());
+  HIPCHK(grow_stream_sets(h->subs, n));
   return MHPC_OK;
 }
 
@@ -1002,35 +965,33 @@ static int solve_async(Handle* h, Scope& sc) {
   // fresh problems in a solve that starts with the real rollout: the split order to the device
   const bool mixed = sc.mixed;
   if (mixed) {
-    HIPCHK(hipMemcpyAsync(h->dsplit, sc.ss->split.data(), (size_t)sc.n * sizeof(int),
-                          hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(h->dsplit.get(), sc.ss->split.data(), (size_t)sc.n * sizeof(int),
+                          hipMemcpyHostToDevice, h->main.s1));
+    HIPCHK(hipStreamSynchronize(h->main.s1));
   }
   if (nsub <= 1) {
-    SolveBlock k{sc.sp,       sc.d,      h->stream,  h->stream2, h->stream3,
-                 h->evfork,   h->evjoin, h->evpfork, h->evpjoin};
+    SolveBlock k{sc.sp, sc.d, &h->main};
     if (mixed) split_block(k, *sc.ss);
     for (const SolveOp& op : ops)
       if ((rc = issue_op(h, k, op))) {
         // an issue failure may leave launches queued on the second / third stream (the
-        // partials fork onto stream3 and join back only at their end): drain both, so no later
+        // partials fork onto s3 and join back only at their end): drain both, so no later
         // work on the handle runs unordered with them
-        drain({h->stream3, h->stream2});
-        (void)hipStreamWaitEvent(h->stream, h->evjoin, 0);
+        drain({h->main.s3, h->main.s2});
+        (void)hipStreamWaitEvent(h->main.s1, h->main.join, 0);
         return rc;
       }
     // a schedule whose last partials have no sweep after them (max_DDP_iter = 0) still
     // joins the second stream back before the solve counts as done
-    HIPCHK(hipStreamWaitEvent(h->stream, h->evjoin, 0));
+    HIPCHK(hipStreamWaitEvent(h->main.s1, h->main.join, 0));
   } else {
     if ((rc = ensure_sub_streams(h, nsub))) return rc;
-    HIPCHK(hipEventRecord(h->evstart, h->stream));
+    HIPCHK(hipEventRecord(h->evstart, h->main.s1));
     std::vector<SolveBlock> blk(nsub);
     // even partition of the scope's positions: every block non-empty (sub_batches() <= n), sizes
     // differ by <= 1
     const int B = sc.n;
     for (int s = 0; s < nsub; ++s) {
-      const Handle::SubStreams& ss = h->subs[s];
       SolveBlock& k = blk[s];
       const int b0 = (int)((int64_t)s * B / nsub), b1 = (int)((int64_t)(s + 1) * B / nsub);
       // the block's problems: the scope's positions [b0, b1) (each group's range clipped to them);
@@ -1038,29 +999,23 @@ static int solve_async(Handle* h, Scope& sc) {
       k.sp = sc.sp;
       scope_clip(sc.sp.go, sc.sp.ngrp, b0, b1, k.sp.go);
       k.d = sc.d;
-      k.s1 = ss.s1;
-      k.s2 = ss.s2;
-      k.fork = ss.fork;
-      k.join = ss.join;
-      k.s3 = ss.s3;
-      k.pfork = ss.pfork;
-      k.pjoin = ss.pjoin;
+      k.q = &h->subs[s];
       if (mixed) split_block(k, *sc.ss);
-      HIPCHK(hipStreamWaitEvent(k.s1, h->evstart, 0));
+      HIPCHK(hipStreamWaitEvent(k.q->s1, h->evstart, 0));
     }
     // block s runs `lag` launches behind block s - 1 (its first launch waits on the gate
     // event recorded after launch lag - 1 of the block before; issued in that order)
     int lag = 1;
     if (const char* e = getenv("MHPC_SUB_LAG")) lag = atoi(e);  // tuning only
     lag = std::max(0, std::min(lag, nops - 1));
-    // every block's streams are joined back to h->stream even when an issue fails partway,
+    // every block's streams are joined back to h->main.s1 even when an issue fails partway,
     // so later work on the handle never races with a block's queued launches
     auto join_all = [&]() -> hipError_t {
       hipError_t e = hipSuccess;
       for (int s = 0; s < nsub; ++s) {
-        hipError_t e1 = hipStreamWaitEvent(blk[s].s1, blk[s].join, 0);
-        if (e1 == hipSuccess) e1 = hipEventRecord(h->subs[s].done, blk[s].s1);
-        if (e1 == hipSuccess) e1 = hipStreamWaitEvent(h->stream, h->subs[s].done, 0);
+        hipError_t e1 = hipStreamWaitEvent(h->subs[s].s1, h->subs[s].join, 0);
+        if (e1 == hipSuccess) e1 = hipEventRecord(h->subs[s].done, h->subs[s].s1);
+        if (e1 == hipSuccess) e1 = hipStreamWaitEvent(h->main.s1, h->subs[s].done, 0);
         if (e == hipSuccess) e = e1;
       }
       return e;
@@ -1071,23 +1026,23 @@ static int solve_async(Handle* h, Scope& sc) {
         const int i = t - s * lag;
         if (i < 0 || i >= nops) continue;
         if (s > 0 && i == 0 && lag > 0 &&
-            hipStreamWaitEvent(blk[s].s1, h->subs[s - 1].gate, 0) != hipSuccess)
+            hipStreamWaitEvent(h->subs[s].s1, h->subs[s - 1].gate, 0) != hipSuccess)
           rc = fail(MHPC_ERR_DEVICE, "sub-batch gate wait failed");
         if (!rc) rc = issue_op(h, blk[s], ops[i]);
         if (!rc && s + 1 < nsub && lag > 0 && i == lag - 1 &&
-            hipEventRecord(h->subs[s].gate, blk[s].s1) != hipSuccess)
+            hipEventRecord(h->subs[s].gate, h->subs[s].s1) != hipSuccess)
           rc = fail(MHPC_ERR_DEVICE, "sub-batch gate record failed");
       }
     const hipError_t ej = join_all();
     if (rc) {  // (as above: the blocks' partials streams drained on an issue failure)
-      for (int q = 0; q < nsub; ++q) drain({blk[q].s3, blk[q].s2});
+      for (int q = 0; q < nsub; ++q) drain({h->subs[q].s3, h->subs[q].s2});
       return rc;
     }
     HIPCHK(ej);
   }
   // totals of the per-problem counters per group (tiny reduction, NCNT words each)
-  HIPCHK(hipMemsetAsync(h->dcnt, 0, (size_t)sc.sp.ngrp * NCNT * sizeof(unsigned long long), h->stream));
-  HIPCHK(launch_reduce_counters(sc.sp, sc.d, h->dcnt, h->stream));
+  HIPCHK(hipMemsetAsync(h->dcnt.get(), 0, (size_t)sc.sp.ngrp * NCNT * sizeof(unsigned long long), h->main.s1));
+  HIPCHK(launch_reduce_counters(sc.sp, sc.d, h->dcnt.get(), h->main.s1));
   return MHPC_OK;
 }
 
@@ -1141,16 +1096,16 @@ int api_solve(Handle* h, int32_t* status) {
     return fail(MHPC_ERR_STATE, "x0 changed: call mhpc_initialize or mhpc_update_problem first");
   if (pending(h)) return fail(MHPC_ERR_STATE, h->params_changed ? kParamsPending : kCmdPending);
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipEventRecord(h->ev0, h->stream));
+  HIPCHK(hipEventRecord(h->ev0, h->main.s1));
   SolveScope ss;
   Scope sc = batch_scope(h, ss);
   int rc = solve_async(h, sc);
   h->sp.ro_store = sc.sp.ro_store;  // (the batch's own choice stays visible in the handle's sp)
   if (rc) return rc;
-  HIPCHK(hipEventRecord(h->ev1, h->stream));
-  HIPCHK(hipMemcpyAsync(h->gcnt, h->dcnt, (size_t)h->sp.ngrp * NCNT * sizeof(unsigned long long),
-                        hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipEventRecord(h->ev1, h->main.s1));
+  HIPCHK(hipMemcpyAsync(h->gcnt, h->dcnt.get(), (size_t)h->sp.ngrp * NCNT * sizeof(unsigned long long),
+                        hipMemcpyDeviceToHost, h->main.s1));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   h->solved = true;
   h->need_full = false;
   h->led.solved();
@@ -1170,8 +1125,8 @@ static int copy_rows(Handle* h, const real* src, int per, int ko, int N, size_t 
   const size_t NK = h->sp.NK, w = (size_t)N * per * sizeof(real);
   buf.resize(B * N * per);
   HIPCHK(hipMemcpy2DAsync(buf.data(), w, src + (b0 * NK + (size_t)ko) * per,
-                          NK * per * sizeof(real), w, B, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+                          NK * per * sizeof(real), w, B, hipMemcpyDeviceToHost, h->main.s1));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   return MHPC_OK;
 }
 
@@ -1188,7 +1143,7 @@ static int get_phase_run(Handle* h, int phase, int n, int N, int ko, size_t b0, 
     // export the whole batch per call)
     SolveParams sub = sp;
     sub.B = (int)B;
-    HIPCHK(launch_export(sub, block_bufs(h->d, sp, b0), h->stream));
+    HIPCHK(launch_export(sub, block_bufs(h->d, sp, b0), h->main.s1));
     if ((rc = copy_rows(h, h->d.out, KS, ko, N, b0, B, buf))) return rc;
     for (size_t b = 0; b < B; ++b)
       for (int k = 0; k < N; ++k) {
@@ -1297,9 +1252,9 @@ static int dev_fail(const char* fn, hipError_t e) {
 // and the launch's time to *ms (ms may be null); all of it folded into t.e.
 template <class Launch>
 static void timed_launch(Handle* h, DevTemp<real>& t, float* ms, Launch launch) {
-  if (t.e == hipSuccess) t.e = hipEventRecord(h->ev0, h->stream);
+  if (t.e == hipSuccess) t.e = hipEventRecord(h->ev0, h->main.s1);
   if (t.e == hipSuccess) t.e = launch();
-  if (t.e == hipSuccess) t.e = hipEventRecord(h->ev1, h->stream);
+  if (t.e == hipSuccess) t.e = hipEventRecord(h->ev1, h->main.s1);
   t.stage();
   float el = 0;
   if (t.e == hipSuccess) t.e = hipEventElapsedTime(&el, h->ev0, h->ev1);
@@ -1317,10 +1272,10 @@ int api_rollout_costs(Handle* h, int n_eps, const double* eps, double* J,
                 "parameter sets changed: call mhpc_initialize or mhpc_update_problem first");
   HIPCHK(hipSetDevice(h->device));
   const size_t n = (size_t)h->sp.B * n_eps;
-  DevTemp<real> t(h->stream);
+  DevTemp<real> t(h->main.s1);
   real *deps = t.in(eps, n_eps), *dJ = t.out(J, n), *dv = t.out(viol, n);
   timed_launch(h, t, ms,
-               [&] { return launch_eps_rollout(h->sp, h->d, n_eps, deps, dJ, dv, h->stream); });
+               [&] { return launch_eps_rollout(h->sp, h->d, n_eps, deps, dJ, dv, h->main.s1); });
   if (t.fetch() != hipSuccess) return dev_fail("mhpc_rollout_costs", t.e);
   return MHPC_OK;
 }
@@ -1365,12 +1320,12 @@ int api_rollout_policy(Handle* h, int n_samples, const double* xs, int n_phases,
   std::vector<real> hxs;
   if ((rc = policy_pack(h, 0, B, n_samples, xs, "start states", hxs))) return rc;
   HIPCHK(hipSetDevice(h->device));
-  DevTemp<real> t(h->stream);
+  DevTemp<real> t(h->main.s1);
   real *dxs = t.in(std::move(hxs)), *dJ = t.out(J, n), *dv = t.out(viol, n);
   real* dxe = x_end ? t.out(nullptr, n * 14) : nullptr;
   timed_launch(h, t, ms, [&] {
     return launch_policy_rollout(h->sp, h->d, n_samples, 0, B, dxs, nullptr, n_phases, 0, dJ, dv,
-                                 dxe, nullptr, h->stream);
+                                 dxe, nullptr, h->main.s1);
   });
   if (t.fetch() != hipSuccess) return dev_fail("mhpc_rollout_policy", t.e);
   if (x_end) unpad_rows(t.staged(dxe), n, x0_row_of(h->plan), x_end);
@@ -1390,11 +1345,11 @@ int api_rollout_policy_phase(Handle* h, int phase, int first, int count, int n_s
   std::vector<real> hxs;
   if ((rc = policy_pack(h, first, count, n_samples, xs, "start states", hxs))) return rc;
   HIPCHK(hipSetDevice(h->device));
-  DevTemp<real> t(h->stream);
+  DevTemp<real> t(h->main.s1);
   real *dxs = t.in(std::move(hxs)), *drec = t.out(nullptr, n * N * PREC_W);
   if (t.e == hipSuccess)
     t.e = launch_policy_rollout(h->sp, h->d, n_samples, first, count, dxs, nullptr, 0, phase, nullptr,
-                                nullptr, nullptr, drec, h->stream);
+                                nullptr, nullptr, drec, h->main.s1);
   if (t.fetch() != hipSuccess) return dev_fail("mhpc_rollout_policy_phase", t.e);
   // device records [count][N][PREC_W][n_s] (the sample fastest: coalesced stores); the last
   // knot has no u, y and an SRB knot no y: zero rows
@@ -1431,11 +1386,11 @@ int api_advance_x0(Handle* h, int n_phases, const double* dx) {
   std::vector<double> hdx;
   if (dx && (rc = policy_pack(h, 0, B, 1, dx, "dx", hdx))) return rc;
   HIPCHK(hipSetDevice(h->device));
-  DevTemp<real> t(h->stream);
+  DevTemp<real> t(h->main.s1);
   const double* ddx = dx ? t.in_double(std::move(hdx)) : nullptr;  // added in double
   if (t.e == hipSuccess)
     t.e = launch_policy_rollout(h->sp, h->d, 1, 0, B, h->d.x0, ddx, n_phases, 0, nullptr, nullptr,
-                                h->d.x0, nullptr, h->stream);
+                                h->d.x0, nullptr, h->main.s1);
   if (t.fetch() != hipSuccess) return dev_fail("mhpc_advance_x0", t.e);  // no outputs: the sync
   h->x0_set = true;
   h->x0_changed = true;  // as after mhpc_set_x0
@@ -1486,9 +1441,9 @@ static int check_dev_dtype(int dtype) {
 // The handle's stream behind everything queued on the caller's stream at this call: an event
 // recorded there (created at the first such call), no host-side wait.
 static int wait_for_caller(Handle* h, void* stream) {
-  if (!h->evctl) HIPCHK(hipEventCreateWithFlags(&h->evctl, hipEventDisableTiming));
+  HIPCHK(h->evctl.ensure());
   HIPCHK(hipEventRecord(h->evctl, (hipStream_t)stream));
-  HIPCHK(hipStreamWaitEvent(h->stream, h->evctl, 0));
+  HIPCHK(hipStreamWaitEvent(h->main.s1, h->evctl, 0));
   return MHPC_OK;
 }
 // The steps to the handle's device array [B] (allocated at the first call with steps, after every
@@ -1496,11 +1451,11 @@ static int wait_for_caller(Handle* h, void* stream) {
 static int upload_steps(Handle* h, const int32_t* step, const int** dstep) {
   *dstep = nullptr;
   if (!step) return MHPC_OK;
-  if (!h->dstep) HIPCHK(hipMalloc((void**)&h->dstep, (size_t)h->sp.B * sizeof(int)));
+  if (!h->dstep.get()) HIPCHK(h->dstep.alloc(h->sp.B));
   h->hstep.assign(step, step + h->sp.B);  // (the copy may outlive a call that fails after it)
-  HIPCHK(hipMemcpyAsync(h->dstep, h->hstep.data(), (size_t)h->sp.B * sizeof(int),
-                        hipMemcpyHostToDevice, h->stream));
-  *dstep = h->dstep;
+  HIPCHK(hipMemcpyAsync(h->dstep.get(), h->hstep.data(), (size_t)h->sp.B * sizeof(int),
+                        hipMemcpyHostToDevice, h->main.s1));
+  *dstep = h->dstep.get();
   return MHPC_OK;
 }
 
@@ -1525,7 +1480,7 @@ int api_control(Handle* h, const int32_t* step, const double* x, double* u, doub
   HIPCHK(hipSetDevice(h->device));
   const int* dstep;
   if ((rc = upload_steps(h, step, &dstep))) return rc;
-  DevTemp<double> t(h->stream);
+  DevTemp<double> t(h->main.s1);
   const double* dx = u ? t.in(x, B * r) : nullptr;
   double* du = u ? t.out(u, B * 4) : nullptr;
   double* dxn = x_nom ? t.out(x_nom, B * r) : nullptr;
@@ -1533,7 +1488,7 @@ int api_control(Handle* h, const int32_t* step, const double* x, double* u, doub
   double* dK = K ? t.out(K, B * 4 * r) : nullptr;
   if (t.e == hipSuccess)
     t.e = launch_control(h->sp, h->d, dstep, dx, (long)r, du, 4, dxn, dun, dK, (int)r, MHPC_DEV_F64,
-                         h->stream);
+                         h->main.s1);
   if (t.fetch() != hipSuccess) return dev_fail("mhpc_control", t.e);
   return MHPC_OK;
 }
@@ -1556,8 +1511,8 @@ int api_control_device(Handle* h, const int32_t* step, const void* x, int64_t ld
   if ((rc = upload_steps(h, step, &dstep))) return rc;
   if ((rc = wait_for_caller(h, stream))) return rc;
   HIPCHK(launch_control(h->sp, h->d, dstep, u ? x : nullptr, (long)ldx, u, (long)ldu, x_nom, u_nom,
-                        K, r, dtype, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+                        K, r, dtype, h->main.s1));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   return MHPC_OK;
 }
 
@@ -1569,8 +1524,8 @@ int api_set_x0_device(Handle* h, const void* x0, int64_t ld, int dtype, void* st
   HIPCHK(hipSetDevice(h->device));
   if ((rc = check_device_ptr(h, x0, "x0"))) return rc;
   if ((rc = wait_for_caller(h, stream))) return rc;
-  HIPCHK(launch_x0_in(h->sp, h->d, x0, (long)ld, dtype, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(launch_x0_in(h->sp, h->d, x0, (long)ld, dtype, h->main.s1));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   h->x0_set = true;
   h->x0_changed = true;  // as after mhpc_set_x0
   return MHPC_OK;
@@ -1583,14 +1538,14 @@ int api_get_cost_gradients(Handle* h, int phase, int first, int count, double* l
   int rc = range_phase_shape(h, phase, first, count, &n, &N);
   if (rc) return rc;
   HIPCHK(hipSetDevice(h->device));
-  DevTemp<real> t(h->stream);
+  DevTemp<real> t(h->main.s1);
   real *dlx = t.out(lx, (size_t)count * (N - 1) * n), *dph = t.out(Phix, (size_t)count * n);
   // one launch per run of problems of the same group
   if (t.e == hipSuccess)
     for_runs(first, count, [&](int b) { return h->plan.lid[b]; }, [&](int r0, int nb) {
       const size_t o = (size_t)(r0 - first);
       t.e = launch_cost_grad(h->sp, h->d, h->plan.lid[r0], phase, N, r0, nb, dlx + o * (N - 1) * n,
-                             dph + o * n, h->stream);
+                             dph + o * n, h->main.s1);
       return t.e != hipSuccess;
     });
   if (t.fetch() != hipSuccess) return dev_fail("mhpc_get_cost_gradients", t.e);
@@ -1617,14 +1572,13 @@ static int ensure_store(Handle* h) {
   int nbk, spmax;
   store_shape(h, &nbk, &spmax);
   const size_t bytes = (size_t)h->sp.B * spmax * nbk * kStoreRec * sizeof(real);
-  if (!h->store || nbk != h->nbk || spmax != h->spmax) {
-    if (h->store) HIPCHK(hipFree(h->store));
-    h->store = nullptr;
-    HIPCHK(hipMalloc((void**)&h->store, bytes));
+  if (!h->store.get() || nbk != h->nbk || spmax != h->spmax) {
+    h->store.reset();  // (before the new one is allocated, as ever: the two never coexist)
+    HIPCHK(h->store.alloc(bytes / sizeof(real)));
     h->nbk = nbk;
     h->spmax = spmax;
   }
-  HIPCHK(hipMemsetAsync(h->store, 0, bytes, h->stream));
+  HIPCHK(hipMemsetAsync(h->store.get(), 0, bytes, h->main.s1));
   h->store_valid = true;
   return MHPC_OK;
 }
@@ -1668,21 +1622,21 @@ int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const in
   }
   // phases write through to their buffers in the reference: save the current layouts (also when
   // the regrouping below is refused, as ever: the rows are the current solution's either way)
-  HIPCHK(launch_store(h->sp, h->d, h->store, h->nbk, h->spmax, 1, h->stream));
+  HIPCHK(launch_store(h->sp, h->d, h->store.get(), h->nbk, h->spmax, 1, h->main.s1));
   GroupPlan plan;
   const char* msg = nullptr;
   if ((rc = plan_groups(npl, h->pset_of, plan, &msg))) {  // too many layouts: the old ones stay
-    (void)hipStreamSynchronize(h->stream);
+    (void)hipStreamSynchronize(h->main.s1);
     return fail(rc, msg);
   }
   if ((rc = commit_groups(h, std::move(plan), false, &npl))) return rc;
   h->cmode = ncm;
   for (int b = 0; b < B; ++b)
     if ((steps ? steps[b] : 1) > 0) h->led.stepped(b);
-  HIPCHK(launch_reset(h->sp, h->d, h->stream));  // refs from x0, AL/ReB init, nom_slot = 0
-  if (own_init_values(h)) HIPCHK(launch_init_params(h->sp, h->d, 0, h->stream));
-  HIPCHK(launch_store(h->sp, h->d, h->store, h->nbk, h->spmax, 0, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(launch_reset(h->sp, h->d, h->main.s1));  // refs from x0, AL/ReB init, nom_slot = 0
+  if (own_init_values(h)) HIPCHK(launch_init_params(h->sp, h->d, 0, h->main.s1));
+  HIPCHK(launch_store(h->sp, h->d, h->store.get(), h->nbk, h->spmax, 0, h->main.s1));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   h->need_full = true;
   mark_current(h);
   return MHPC_OK;
@@ -1759,11 +1713,11 @@ int api_tick_problems(Handle* h, int n, const int32_t* problems, const double* x
   if (x0) rows = pack_rows<real>(h->plan, n, 1, x0, 0, problems);
   // ---- nothing of the handle or the device has changed up to here ----
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (!h->evt0) HIPCHK(hipEventCreate(&h->evt0));
-  if (!h->evt1) HIPCHK(hipEventCreate(&h->evt1));
-  DevTemp<int> ti(h->stream);
-  DevTemp<real> tr(h->stream);
+  HIPCHK(hipStreamSynchronize(h->main.s1));
+  HIPCHK(h->evt0.ensure(EV_TIMING));
+  HIPCHK(h->evt1.ensure(EV_TIMING));
+  DevTemp<int> ti(h->main.s1);
+  DevTemp<real> tr(h->main.s1);
   const int* dlist = ti.in(std::vector<int>(list));
   const int* dorder = ti.in(std::vector<int>(ss.order));
   int* dstatus = status ? ti.alloc(n) : nullptr;
@@ -1773,30 +1727,30 @@ int api_tick_problems(Handle* h, int n, const int32_t* problems, const double* x
   // from here a failure leaves the listed problems undefined (as a failed mhpc_reset_problems);
   // nothing of the handle's may stay queued behind it
   auto run = [&]() -> int {
-    HIPCHK(hipEventRecord(h->evt0, h->stream));
-    if (drows) HIPCHK(launch_scatter_x0(h->d, n, dlist, drows, h->stream));
+    HIPCHK(hipEventRecord(h->evt0, h->main.s1));
+    if (drows) HIPCHK(launch_scatter_x0(h->d, n, dlist, drows, h->main.s1));
     if (int rc = ensure_store(h)) return rc;
     // phases write through to their buffers in the reference: the listed problems' current
     // solutions under their layouts before the commit
-    HIPCHK(launch_store_list(h->sp, h->d, n, dlist, h->store, h->nbk, h->spmax, 1, h->stream));
+    HIPCHK(launch_store_list(h->sp, h->d, n, dlist, h->store.get(), h->nbk, h->spmax, 1, h->main.s1));
     if (any_step) {
       if (int rc = commit_groups(h, std::move(plan), true, &npl)) return rc;
       for (int i = 0; i < n; ++i) h->cmode[problems[i]] = ncm[problems[i]];
     }
     Scope sc = make_scope(h, &ss, dorder, scope_caps(h->otab, list.data(), n), true);
-    HIPCHK(launch_reset(sc.sp, sc.d, h->stream));  // refs from x0 and the command, AL/ReB init, nom_slot = 0
-    if (own_init_values(h)) HIPCHK(launch_init_params(sc.sp, sc.d, 0, h->stream));
-    HIPCHK(launch_store_list(h->sp, h->d, n, dlist, h->store, h->nbk, h->spmax, 0, h->stream));
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    HIPCHK(launch_reset(sc.sp, sc.d, h->main.s1));  // refs from x0 and the command, AL/ReB init, nom_slot = 0
+    if (own_init_values(h)) HIPCHK(launch_init_params(sc.sp, sc.d, 0, h->main.s1));
+    HIPCHK(launch_store_list(h->sp, h->d, n, dlist, h->store.get(), h->nbk, h->spmax, 0, h->main.s1));
+    HIPCHK(hipEventRecord(h->ev0, h->main.s1));
     if (int rc = solve_async(h, sc)) return rc;
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    if (dstatus) HIPCHK(launch_status_list(h->d, n, dlist, dstatus, h->stream));
-    HIPCHK(hipEventRecord(h->evt1, h->stream));
-    HIPCHK(hipMemcpyAsync(h->gcnt, h->dcnt, (size_t)sc.sp.ngrp * NCNT * sizeof(unsigned long long),
-                          hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipEventRecord(h->ev1, h->main.s1));
+    if (dstatus) HIPCHK(launch_status_list(h->d, n, dlist, dstatus, h->main.s1));
+    HIPCHK(hipEventRecord(h->evt1, h->main.s1));
+    HIPCHK(hipMemcpyAsync(h->gcnt, h->dcnt.get(), (size_t)sc.sp.ngrp * NCNT * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, h->main.s1));
     if (dstatus)
-      HIPCHK(hipMemcpyAsync(status, dstatus, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+      HIPCHK(hipMemcpyAsync(status, dstatus, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->main.s1));
+    HIPCHK(hipStreamSynchronize(h->main.s1));
     if (ms) HIPCHK(hipEventElapsedTime(ms, h->evt0, h->evt1));
     return account_solve(h, sc);
   };
@@ -1804,7 +1758,7 @@ int api_tick_problems(Handle* h, int n, const int32_t* problems, const double* x
   // the listed problems have their references and their solve, whatever came of it: no longer
   // fresh, no command pending
   h->led.ticked(n, problems);
-  if (rc) drain({h->stream3, h->stream2, h->stream});
+  if (rc) drain({h->main.s3, h->main.s2, h->main.s1});
   return rc;
 }
 
@@ -1834,7 +1788,7 @@ int api_set_layouts(Handle* h, int n_desc, const mhpc_problem_desc* descs, const
   for (int b = 0; lop && b < B; ++b)
     if (lop[b] < 0 || lop[b] >= n_desc) return fail(MHPC_ERR_INVALID, "layout index out of range");
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   std::vector<ProbLayout> npl(B);
   for (int b = 0; b < B; ++b) npl[b] = ProbLayout{norm_desc(descs[lop ? lop[b] : b % n_desc]), 0, 0};
   GroupPlan plan;
@@ -1855,25 +1809,25 @@ int api_set_layouts(Handle* h, int n_desc, const mhpc_problem_desc* descs, const
 // restricted parameters (make_scope).  Every launch counts as k_init under profiling.
 static int reset_launches(Handle* h, const SolveScope& ss, std::vector<real>&& rows) {
   const int n = ss.size();
-  DevTemp<int> ti(h->stream);
-  DevTemp<real> tr(h->stream);
+  DevTemp<int> ti(h->main.s1);
+  DevTemp<real> tr(h->main.s1);
   const int* dlist = ti.in(std::vector<int>(ss.order));
   const real* drows = rows.empty() ? nullptr : tr.in(std::move(rows));
   if (ti.e != hipSuccess) return dev_fail("mhpc_reset_problems", ti.e);
   if (tr.e != hipSuccess) return dev_fail("mhpc_reset_problems", tr.e);
   const Scope rs = make_scope(h, &ss, dlist, ScopeCaps(), false);
-  HIPCHK(hipEventRecord(h->evfork, h->stream));
-  HIPCHK(hipStreamWaitEvent(h->stream2, h->evfork, 0));
-  LAUNCH_ON(h, K_INIT, h->stream2,
-            launch_reset_list(h->sp, h->d, n, dlist, h->store_valid ? h->store : nullptr, h->nbk,
-                              h->spmax, h->stream2));
-  HIPCHK(hipEventRecord(h->evjoin, h->stream2));
-  if (drows) LAUNCH(h, K_INIT, launch_scatter_x0(h->d, n, dlist, drows, h->stream));
-  LAUNCH(h, K_INIT, launch_init(rs.sp, rs.d, h->stream));
+  HIPCHK(hipEventRecord(h->main.fork, h->main.s1));
+  HIPCHK(hipStreamWaitEvent(h->main.s2, h->main.fork, 0));
+  LAUNCH_ON(h, K_INIT, h->main.s2,
+            launch_reset_list(h->sp, h->d, n, dlist, h->store_valid ? h->store.get() : nullptr, h->nbk,
+                              h->spmax, h->main.s2));
+  HIPCHK(hipEventRecord(h->main.join, h->main.s2));
+  if (drows) LAUNCH(h, K_INIT, launch_scatter_x0(h->d, n, dlist, drows, h->main.s1));
+  LAUNCH(h, K_INIT, launch_init(rs.sp, rs.d, h->main.s1));
   // (k_init wrote the AL / ReB initial values of problem 0's set)
-  if (own_init_values(h)) LAUNCH(h, K_INIT, launch_init_params(rs.sp, rs.d, 1, h->stream));
-  HIPCHK(hipStreamWaitEvent(h->stream, h->evjoin, 0));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  if (own_init_values(h)) LAUNCH(h, K_INIT, launch_init_params(rs.sp, rs.d, 1, h->main.s1));
+  HIPCHK(hipStreamWaitEvent(h->main.s1, h->main.join, 0));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   return MHPC_OK;
 }
 
@@ -1908,7 +1862,7 @@ int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* 
   }
   if (x0_row_of(npl) != r) return fail(MHPC_ERR_INVALID, "the x0 row width would change");
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   GroupPlan plan;
   PLANCHK(plan_groups, npl, h->pset_of, plan);  // too many groups: nothing changed
   int rc = commit_groups(h, std::move(plan), true, &npl);
@@ -1924,7 +1878,7 @@ int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* 
   }
   rc = reset_launches(h, ss, std::move(rows));
   if (rc) {  // nothing of the handle's may stay queued behind a failed launch
-    drain({h->stream2, h->stream});
+    drain({h->main.s2, h->main.s1});
     return rc;
   }
   return collect_profile(h);
@@ -1932,7 +1886,7 @@ int api_reset_problems(Handle* h, int n, const int32_t* problems, const double* 
 
 // ---- copies of live problems (mhpc_copy_problems, mhpc_restore_problems) ------------------------
 static CopySide copy_side(const Handle* h) {
-  return CopySide{h->d, h->store_valid ? h->store : nullptr, h->sp.NK, h->sp.nslot, h->nbk, h->spmax};
+  return CopySide{h->d, h->store_valid ? h->store.get() : nullptr, h->sp.NK, h->sp.nslot, h->nbk, h->spmax};
 }
 
 // The host state of one source problem that travels with a copy -- and, byte for byte, the entry
@@ -2037,7 +1991,7 @@ static int copy_into(Handle* d, const int32_t* dp, int n, const CopySource& src,
     return fail(MHPC_ERR_STATE, "the handles are at different points of the call order");
   merge_sets(nsets, nof);
   HIPCHK(hipSetDevice(d->device));
-  HIPCHK(hipStreamSynchronize(d->stream));
+  HIPCHK(hipStreamSynchronize(d->main.s1));
   GroupPlan plan;
   PLANCHK(plan_groups, npl, nof, plan);  // too many groups: nothing changed
   // Until the launch is queued the destination can go back to what it was: the commit swaps its
@@ -2058,11 +2012,11 @@ static int copy_into(Handle* d, const int32_t* dp, int n, const CopySource& src,
     ent[2 * (size_t)i] = dp[i];
     ent[2 * (size_t)i + 1] = nslot_of[i];
   }
-  DevTemp<int> t(d->stream);
+  DevTemp<int> t(d->main.s1);
   const int* dent = t.in(std::move(ent));
   if (t.e == hipSuccess) t.e = mv.prepare(d, dp, n);
   if (t.e != hipSuccess) {  // nothing of the copy is queued yet
-    drain({d->stream2, d->stream});
+    drain({d->main.s2, d->main.s1});
     (void)commit_groups(d, std::move(plan), true, &npl, &nsets, &nof);
     return dev_fail(src.call, t.e);
   }
@@ -2077,12 +2031,12 @@ static int copy_into(Handle* d, const int32_t* dp, int n, const CopySource& src,
   float el = 0;
   t.e = mv.run(d, &el);
   // the option index of the destinations (their rewritten option fields came with the state)
-  if (t.e == hipSuccess) t.e = launch_set_options(d->d, d->doid, n, dent, 0, d->stream);
-  if (t.e == hipSuccess) t.e = hipStreamSynchronize(d->stream);
+  if (t.e == hipSuccess) t.e = launch_set_options(d->d, d->own.oid.get(), n, dent, 0, d->main.s1);
+  if (t.e == hipSuccess) t.e = hipStreamSynchronize(d->main.s1);
   if (t.e != hipSuccess) {
     // a failed launch: the destination problems are undefined (as after a failed reset); nothing
     // of the handle's may stay queued behind it
-    drain({d->stream2, d->stream});
+    drain({d->main.s2, d->main.s1});
     return dev_fail(src.call, t.e);
   }
   // the host table follows the device index once the launches have succeeded (a record the
@@ -2126,16 +2080,16 @@ struct HandleMover : CopyMover {
     copy_block_table(cs, cd, pairs.data() + 2 * (size_t)n);
     dpairs = t.in(std::move(pairs));
     if (t.e == hipSuccess && s != d) {
-      t.e = hipEventRecord(s->evfork, s->stream);
-      if (t.e == hipSuccess) t.e = hipStreamWaitEvent(d->stream, s->evfork, 0);
+      t.e = hipEventRecord(s->main.fork, s->main.s1);
+      if (t.e == hipSuccess) t.e = hipStreamWaitEvent(d->main.s1, s->main.fork, 0);
     }
     return t.e;
   }
   hipError_t run(Handle* d, float* ms) override {
-    hipError_t e = hipEventRecord(d->ev0, d->stream);
-    if (e == hipSuccess) e = launch_copy_problems(cs, cd, n, dpairs, nblk, dpairs + 2 * (size_t)n, d->stream);
-    if (e == hipSuccess) e = hipEventRecord(d->ev1, d->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    hipError_t e = hipEventRecord(d->ev0, d->main.s1);
+    if (e == hipSuccess) e = launch_copy_problems(cs, cd, n, dpairs, nblk, dpairs + 2 * (size_t)n, d->main.s1);
+    if (e == hipSuccess) e = hipEventRecord(d->ev1, d->main.s1);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->main.s1);
     if (e == hipSuccess) e = hipEventElapsedTime(ms, d->ev0, d->ev1);
     return e;
   }
@@ -2158,7 +2112,7 @@ int api_copy_problems(Handle* d, const int32_t* dp, Handle* s, const int32_t* sp
   CopySource src = source_of(s, "mhpc_copy_problems");
   src.p.reserve(n);
   for (int i = 0; i < n; ++i) src.p.push_back(src_problem(s, sp_[i]));
-  HandleMover mv(s, sp_, d->stream);
+  HandleMover mv(s, sp_, d->main.s1);
   return copy_into(d, dp, n, src, mv, ms);
 }
 
@@ -2242,22 +2196,14 @@ int api_snapshot_size(Handle* h, int n, const int32_t* problems, int64_t* bytes)
 // rounds alternate between the handle's two streams, each with a buffer of its own, so a round's
 // launch runs beside the other round's copies and a buffer is reused in stream order.
 struct SnapStage {
-  void* buf[2] = {nullptr, nullptr};
-  std::vector<hipEvent_t> ev;  // [rounds][2]
-  ~SnapStage() {
-    for (void* p : buf)
-      if (p) (void)hipFree(p);
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-  }
+  DevArray<char> buf[2];
+  std::vector<Event> ev;  // [rounds][2]
   hipError_t alloc(size_t bytes, int rounds) {
     for (int k = 0; k < (rounds > 1 ? 2 : 1); ++k)
-      if (hipError_t e = hipMalloc(&buf[k], bytes)) return e;
-    ev.reserve(2 * (size_t)rounds);
-    for (int i = 0; i < 2 * rounds; ++i) {
-      hipEvent_t x;
-      if (hipError_t e = hipEventCreate(&x)) return e;
-      ev.push_back(x);
-    }
+      if (hipError_t e = buf[k].alloc(bytes)) return e;
+    ev.resize(2 * (size_t)rounds);
+    for (Event& x : ev)
+      if (hipError_t e = x.create(EV_TIMING)) return e;
     return hipSuccess;
   }
   hipError_t elapsed(int rounds, float* ms) const {
@@ -2287,7 +2233,7 @@ int api_snapshot_problems(Handle* h, int n, const int32_t* problems, void* blob,
   if (bytes < (int64_t)hd.total_bytes)
     return fail(MHPC_ERR_INVALID, "snapshot buffer too small (mhpc_snapshot_size)");
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   const int NK = hd.NK, nslot = hd.nslot, nbk = hd.nbk, spmax = hd.spmax;
   const int R = snap_round(h, hd.payload_entry_bytes, n), rounds = mhpc_snap::n_rounds(n, R);
   const CopySide cs = copy_side(h), cstage = snap_side(nullptr, R, NK, nslot, nbk, spmax);
@@ -2299,17 +2245,17 @@ int api_snapshot_problems(Handle* h, int n, const int32_t* problems, void* blob,
     pairs[2 * (size_t)i + 1] = i % R;
   }
   copy_block_table(cs, cstage, pairs.data() + 2 * (size_t)n);
-  DevTemp<int> t(h->stream);
+  DevTemp<int> t(h->main.s1);
   const int* dpairs = t.in(std::move(pairs));
   SnapStage st;
   if (t.e == hipSuccess) t.e = st.alloc(snap_stage_bytes(R, NK, nslot, nbk, spmax), rounds);
-  if (t.e == hipSuccess) t.e = hipStreamSynchronize(h->stream);  // the lists are up before stream2 reads them
+  if (t.e == hipSuccess) t.e = hipStreamSynchronize(h->main.s1);  // the lists are up before s2 reads them
   char* payload = (char*)blob + sizeof hd + (size_t)n * sizeof(SrcProblem);
   for (int r = 0; t.e == hipSuccess && r < rounds; ++r) {
     int e0, cnt;
     mhpc_snap::round_of(n, R, r, &e0, &cnt);
-    const hipStream_t q = r & 1 ? h->stream2 : h->stream;
-    void* buf = st.buf[r & 1];
+    const hipStream_t q = r & 1 ? h->main.s2 : h->main.s1;
+    void* buf = st.buf[r & 1].get();
     t.e = hipEventRecord(st.ev[2 * (size_t)r], q);
     if (t.e == hipSuccess)
       t.e = launch_copy_problems(cs, snap_side(buf, R, NK, nslot, nbk, spmax), cnt, dpairs + 2 * (size_t)e0,
@@ -2318,7 +2264,7 @@ int api_snapshot_problems(Handle* h, int n, const int32_t* problems, void* blob,
     if (t.e == hipSuccess) t.e = snap_move(buf, R, NK, nslot, nbk, spmax, payload, n, e0, 0, cnt, true, q);
   }
   // after an error nothing more was queued; either way both streams are idle from here
-  for (hipStream_t q : {h->stream2, h->stream}) {
+  for (hipStream_t q : {(hipStream_t)h->main.s2, (hipStream_t)h->main.s1}) {
     const hipError_t e = hipStreamSynchronize(q);
     if (t.e == hipSuccess) t.e = e;
   }
@@ -2389,7 +2335,7 @@ struct BlobMover : CopyMover {
     dlists = t.in(std::move(lists));
     if (t.e == hipSuccess)
       t.e = st.alloc(snap_stage_bytes(R, (int)hd.NK, (int)hd.nslot, (int)hd.nbk, (int)hd.spmax), rounds);
-    if (t.e == hipSuccess) t.e = hipStreamSynchronize(d->stream);  // the lists are up before stream2 reads them
+    if (t.e == hipSuccess) t.e = hipStreamSynchronize(d->main.s1);  // the lists are up before s2 reads them
     return t.e;
   }
   hipError_t run(Handle* d, float* ms) override {
@@ -2397,8 +2343,8 @@ struct BlobMover : CopyMover {
     for (int r = 0; e == hipSuccess && r < rounds; ++r) {
       int u0, cnt;
       mhpc_snap::round_of((int)uniq.size(), R, r, &u0, &cnt);
-      const hipStream_t q = r & 1 ? d->stream2 : d->stream;
-      void* buf = st.buf[r & 1];
+      const hipStream_t q = r & 1 ? d->main.s2 : d->main.s1;
+      void* buf = st.buf[r & 1].get();
       // consecutive entries of the round travel in one copy per array
       for (int a = 0; e == hipSuccess && a < cnt;) {
         int b = a + 1;
@@ -2414,7 +2360,7 @@ struct BlobMover : CopyMover {
       if (e == hipSuccess) e = hipEventRecord(st.ev[2 * (size_t)r + 1], q);
     }
     // after an error nothing more was queued; either way both streams are idle from here
-    for (hipStream_t q : {d->stream2, d->stream}) {
+    for (hipStream_t q : {(hipStream_t)d->main.s2, (hipStream_t)d->main.s1}) {
       const hipError_t s = hipStreamSynchronize(q);
       if (e == hipSuccess) e = s;
     }
@@ -2451,7 +2397,7 @@ int api_restore_problems(Handle* d, int n, const int32_t* dp, const void* blob, 
     for (int p = 0; p < q.n_wb + q.n_fb; ++p) nk += q.N[p];
     if (nk > (int)hd.NK) return fail(MHPC_ERR_INVALID, "snapshot entry longer than the blob's knot stride");
   }
-  BlobMover mv(hd, blob, entries, d->snap_round_req, d->stream);
+  BlobMover mv(hd, blob, entries, d->snap_round_req, d->main.s1);
   return copy_into(d, dp, n, src, mv, ms);
 }
 
@@ -2517,8 +2463,8 @@ int api_set_commands(Handle* h, const double* vel, const double* height) {
   HIPCHK(hipSetDevice(h->device));
   std::vector<Cmd> hc(B);
   for (size_t b = 0; b < B; ++b) hc[b] = Cmd{(real)nc[2 * b], (real)nc[2 * b + 1]};
-  HIPCHK(hipMemcpyAsync(h->dcmd, hc.data(), B * sizeof(Cmd), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpyAsync(h->own.cmd.get(), hc.data(), B * sizeof(Cmd), hipMemcpyHostToDevice, h->main.s1));
+  HIPCHK(hipStreamSynchronize(h->main.s1));
   if (h->initialized) {  // the problems whose value changed: pending until their next references
     for (size_t b = 0; b < B; ++b)
       if (nc[2 * b] != h->cmd[2 * b] || nc[2 * b + 1] != h->cmd[2 * b + 1]) h->led.command_changed((int)b);
@@ -2544,7 +2490,7 @@ int api_get_reference(Handle* h, int phase, int first, int count, double* xref) 
   int rc = range_phase_shape(h, phase, first, count, &n, &N);
   if (rc) return rc;
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(launch_export_ref(h->sp, h->d, first, count, h->stream));
+  HIPCHK(launch_export_ref(h->sp, h->d, first, count, h->main.s1));
   std::vector<real> buf;
   auto ko = [&](int b) { return h->plan.lays[h->plan.lid[b]].ko[phase]; };
   return for_runs(first, count, ko, [&](int r0, int nb) -> int {
@@ -2672,36 +2618,7 @@ void api_destroy(Handle* h) {
   (void)hipSetDevice(h->device);
   // every stream of the handle drains before its buffers go (an error inside a solve can
   // leave work queued on the partials' or a sub-batch's streams)
-  for (hipStream_t q : {h->stream, h->stream2, h->stream3})
-    if (q) (void)hipStreamSynchronize(q);
-  for (Handle::SubStreams& s : h->subs)
-    for (hipStream_t q : {s.s1, s.s2, s.s3})
-      if (q) (void)hipStreamSynchronize(q);
-  free_bufs(h);
-  if (h->dcnt) (void)hipFree(h->dcnt);
-  if (h->store) (void)hipFree(h->store);
-  if (h->dsplit) (void)hipFree(h->dsplit);
-  if (h->dstep) (void)hipFree(h->dstep);
-  if (h->evctl) (void)hipEventDestroy(h->evctl);
-  if (h->evt0) (void)hipEventDestroy(h->evt0);
-  if (h->evt1) (void)hipEventDestroy(h->evt1);
-  for (hipEvent_t e : h->evpool) (void)hipEventDestroy(e);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->evfork) (void)hipEventDestroy(h->evfork);
-  if (h->evjoin) (void)hipEventDestroy(h->evjoin);
-  if (h->stream2) (void)hipStreamDestroy(h->stream2);
-  if (h->stream3) (void)hipStreamDestroy(h->stream3);
-  if (h->evpfork) (void)hipEventDestroy(h->evpfork);
-  if (h->evpjoin) (void)hipEventDestroy(h->evpjoin);
-  for (Handle::SubStreams& s : h->subs) {
-    for (hipStream_t q : {s.s1, s.s2, s.s3})
-      if (q) (void)hipStreamDestroy(q);
-    for (hipEvent_t e : {s.fork, s.join, s.gate, s.done, s.pfork, s.pjoin})
-      if (e) (void)hipEventDestroy(e);
-  }
-  if (h->evstart) (void)hipEventDestroy(h->evstart);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  (void)sync_streams(h);
   delete h;
 }
 
