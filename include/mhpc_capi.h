@@ -66,6 +66,10 @@
  *                        mhpc_control_device the same on device arrays of the caller's,
  *                        mhpc_set_x0_device set_initial_condition from one (the reference has
  *                        neither: its controller is one object on one CPU)
+ *   mhpc_export_plan_device   get_nominal_ms_ptr() / get_CTG_info_ptr() of the next control steps
+ *                        (SinglePhase.h's per-knot x, u, y and K, du, G) of the listed problems, and
+ *                        mhpc_export_results_device their _actual_cost, _exp_cost_change,
+ *                        _tconstr_violation, _V, _dV, into device arrays of the caller's
  */
 #ifndef MHPC_CAPI_H
 #define MHPC_CAPI_H
@@ -733,6 +737,68 @@ int mhpc_control_device(mhpc_handle* h, const int32_t* step, const void* x, int6
  * SRB-only problem's row tail zero, x0 pending for the next mhpc_initialize /
  * mhpc_update_problem(s)).  MHPC_ERR_INVALID for a null or non-device x0, ld < r or a bad dtype. */
 int mhpc_set_x0_device(mhpc_handle* h, const void* x0, int64_t ld, int dtype, void* stream);
+
+/* ---- device-resident plan export: policy windows and results into device arrays ------------
+ * What a solve produces, for callers that keep it on the device: the next W control steps of
+ * each listed problem's policy (a simulator that sub-steps between re-plans applies
+ * u = u_nom + K (x - x_nom) itself) and the scalars of its last solve (a learner's dataset).
+ * There is no host flavour: mhpc_get_phase(_problems) and mhpc_get_scalars are the host getters,
+ * and every value here is exactly what they report.
+ *  - Addressing.  Steps are the control steps of mhpc_control (above): the whole-body phases of
+ *    a problem that has any, all phases of an SRB-only problem, N[p] - 1 steps a phase, by the
+ *    problem's current layout and nominal trajectory.  Row i of every output belongs to
+ *    problems[i]: a host list of n entries, each in range and none twice; NULL: n == batch, in
+ *    order.  first_step: a host array of n entries (NULL: 0 for every problem),
+ *    0 <= first_step[i] < mhpc_num_control_steps(problems[i]).  1 <= window <= MHPC_MAX_KNOTS.
+ *    Window row w of problem i is step first_step[i] + w; a window runs across phase boundaries
+ *    exactly as consecutive steps do (a phase's last knot, which has no control, is no step).
+ *    valid[i] = min(window, steps of the problem - first_step[i]).
+ *  - Values.  r is the handle's x0 row length (14 or 6); the problem's state size is n.  x_nom,
+ *    u_nom, y: the knot's record of the nominal trajectory; K: the knot's 4 x n gain, row-major in
+ *    rows of r; du: the feed-forward row; Vx: the value gradient; mode: the mode 1..4 of the
+ *    step's phase.  Entries past n (columns of x_nom, Vx and of K's rows, for an SRB-only problem
+ *    in rows of 14) are +0, and so is every row past valid (mode 0).  Nothing is written outside
+ *    the [window][c] block of a listed problem: a caller's padding between blocks (ld_* larger
+ *    than dense) keeps its bytes.  No arithmetic but the element-type conversion of the control
+ *    I/O: widened exactly for a double array, rounded to nearest for a float array of an fp64
+ *    handle or of the results' scalars (which are double in both precisions).
+ *  - Results: J, dV_exp, viol, V_phase, dV_phase as mhpc_get_scalars reports them (V_phase,
+ *    dV_phase in rows of P = mhpc_max_phases, zero past a problem's own phases), status as
+ *    mhpc_solve reports it.
+ *  - Call order, refusals and streams as mhpc_control_device: MHPC_ERR_STATE before
+ *    mhpc_initialize (or after mhpc_set_layouts until the next one) and while commands or
+ *    parameters are pending, a pending x0 does not block; right after mhpc_initialize the policy is
+ *    the PD warm start (K = 0, Vx = 0).  MHPC_ERR_INVALID, before anything is launched: a null
+ *    out, no array wanted, a bad list, first step, window or dtype, an ld_* that is neither 0 nor
+ *    at least the dense block, a pointer that is not device memory of the handle's device.  A
+ *    refused call changes nothing, and no call modifies anything the handle owns.  The work is
+ *    ordered behind everything queued on `stream` at the call and has finished when the call
+ *    returns.  ms (optional): the device time of the launch. */
+typedef struct {
+  /* each array optional (NULL = not wanted); ld_* = elements between two listed problems'
+     blocks, 0 = dense, otherwise >= the dense block size */
+  void* x_nom;   int64_t ld_x_nom;  /* [n][W][r]                                            */
+  void* u_nom;   int64_t ld_u_nom;  /* [n][W][4]                                            */
+  void* K;       int64_t ld_K;      /* [n][W][4][r] row-major                               */
+  void* du;      int64_t ld_du;     /* [n][W][4]                                            */
+  void* Vx;      int64_t ld_Vx;     /* [n][W][r]                                            */
+  void* y;       int64_t ld_y;      /* [n][W][4]                                            */
+  int32_t* mode; int64_t ld_mode;   /* [n][W] mode 1..4 of the step's phase; 0 past `valid` */
+  int32_t* valid;                   /* [n] steps of the window that exist                   */
+} mhpc_plan_out;
+
+int mhpc_export_plan_device(mhpc_handle* h, int n, const int32_t* problems,
+                            const int32_t* first_step, int window, const mhpc_plan_out* out,
+                            int dtype, void* stream, float* ms);
+
+typedef struct {
+  void *J, *dV_exp, *viol;     /* [n]        */
+  void *V_phase, *dV_phase;    /* [n][P], P = mhpc_max_phases, zero past a problem's own phases */
+  int32_t* status;             /* [n] mhpc_solve_status of the problem's last solve */
+} mhpc_results_out;
+
+int mhpc_export_results_device(mhpc_handle* h, int n, const int32_t* problems,
+                               const mhpc_results_out* out, int dtype, void* stream);
 
 /* Per-kernel device timing (HIP events around every launch on the handle's stream) and the
  * algorithmic HBM bytes each kernel must move (model in DESIGN.md §Roofline), accumulated

@@ -649,6 +649,33 @@ class MHPCLocomotion {
                               K, dtype, stream),
           "mhpc_control_device");
   }
+  // `window` control steps of each listed problem's policy from first_step[i] (empty: 0) into the
+  // device arrays `out` names (mhpc_export_plan_device): row i belongs to problems[i] (empty: the
+  // whole batch in order), rows past valid[i] and columns past a problem's state size are +0, every
+  // value is what mhpc_get_phase_problems reports for the step's knot.  Returns the device ms of
+  // the launch.  Ordered after everything queued on `stream`, finished when the call returns.
+  float export_plan_device(const std::vector<int32_t>& problems, const std::vector<int32_t>& first_step,
+                           int window, const mhpc_plan_out& out, int dtype = MHPC_DEV_F64,
+                           void* stream = nullptr) {
+    const int n = problems.empty() ? batch_ : (int)problems.size();
+    if (!first_step.empty() && first_step.size() != (size_t)n)
+      throw std::runtime_error("export_plan_device: first_step must have one entry per listed problem, or none");
+    float ms = 0;
+    check(mhpc_export_plan_device(h_, n, problems.empty() ? nullptr : problems.data(),
+                                  first_step.empty() ? nullptr : first_step.data(), window, &out,
+                                  dtype, stream, &ms),
+          "mhpc_export_plan_device");
+    return ms;
+  }
+  // J, dV_exp, viol, V_phase, dV_phase (rows of max_phases) and status of the listed problems'
+  // last solve into the device arrays `out` names (mhpc_export_results_device)
+  void export_results_device(const std::vector<int32_t>& problems, const mhpc_results_out& out,
+                             int dtype = MHPC_DEV_F64, void* stream = nullptr) {
+    check(mhpc_export_results_device(h_, problems.empty() ? batch_ : (int)problems.size(),
+                                     problems.empty() ? nullptr : problems.data(), &out, dtype,
+                                     stream),
+          "mhpc_export_results_device");
+  }
   // set_initial_conditions from a device array, at once (mhpc_set_x0_device): rows of x0_width()
   // at x0 + b * ld; the device rows are then the current ones, update_problem() /
   // initialization() push no host copy over them

@@ -41,12 +41,35 @@ MHPC_VARIANT_RO_STORE = 4  # line-search trials storing their records (0 = defau
 MHPC_VARIANT_SWEEP_BITS = 5  # backward-sweep arithmetic: 64 double (default) / 32 float (fp32)
 MHPC_VARIANT_SNAP_ROUND = 6  # problems a round of snapshot / restore (0 = by the staging cap)
 MHPC_SNAPSHOT_VERSION = 1
-# element type of a caller's device array (mhpc_control_device, mhpc_set_x0_device)
+# element type of a caller's device array (mhpc_control_device, mhpc_set_x0_device, the exports)
 MHPC_DEV_F64 = 0
 MHPC_DEV_F32 = 1
 MHPC_SOLVE_OK = 0
 MHPC_SOLVE_REG_ABORT = 1
 MHPC_SOLVE_NONFINITE = 2
+
+
+class PlanOut(ctypes.Structure):
+    """mhpc_plan_out: the wanted arrays of mhpc_export_plan_device (device pointers; 0 = not
+    wanted) and the elements between two listed problems' blocks (0 = dense)."""
+    _fields_ = [
+        ("x_nom", ctypes.c_void_p), ("ld_x_nom", ctypes.c_int64),
+        ("u_nom", ctypes.c_void_p), ("ld_u_nom", ctypes.c_int64),
+        ("K", ctypes.c_void_p), ("ld_K", ctypes.c_int64),
+        ("du", ctypes.c_void_p), ("ld_du", ctypes.c_int64),
+        ("Vx", ctypes.c_void_p), ("ld_Vx", ctypes.c_int64),
+        ("y", ctypes.c_void_p), ("ld_y", ctypes.c_int64),
+        ("mode", ctypes.c_void_p), ("ld_mode", ctypes.c_int64),
+        ("valid", ctypes.c_void_p),
+    ]
+
+
+class ResultsOut(ctypes.Structure):
+    """mhpc_results_out: the wanted arrays of mhpc_export_results_device (device pointers)."""
+    _fields_ = [
+        ("J", ctypes.c_void_p), ("dV_exp", ctypes.c_void_p), ("viol", ctypes.c_void_p),
+        ("V_phase", ctypes.c_void_p), ("dV_phase", ctypes.c_void_p), ("status", ctypes.c_void_p),
+    ]
 
 
 class GaitC(ctypes.Structure):
@@ -270,6 +293,12 @@ SIGNATURES = [
                                            ctypes.c_void_p]),
     ("mhpc_set_x0_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                           ctypes.c_int, ctypes.c_void_p]),
+    ("mhpc_export_plan_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _IP, _IP, ctypes.c_int,
+                                               ctypes.POINTER(PlanOut), ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    ("mhpc_export_results_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _IP,
+                                                  ctypes.POINTER(ResultsOut), ctypes.c_int,
+                                                  ctypes.c_void_p]),
     ("mhpc_destroy", None, [ctypes.c_void_p]),
     ("mhpc_kernel_name", ctypes.c_char_p, [ctypes.c_int]),
     ("mhpc_set_profiling", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),

@@ -27,6 +27,10 @@ int api_control(Handle* h, const int32_t* step, const double* x, double* u, doub
 int api_control_device(Handle* h, const int32_t* step, const void* x, int64_t ldx, void* u,
                        int64_t ldu, void* x_nom, void* u_nom, void* K, int dtype, void* stream);
 int api_set_x0_device(Handle* h, const void* x0, int64_t ld, int dtype, void* stream);
+int api_export_plan_device(Handle* h, int n, const int32_t* problems, const int32_t* first_step,
+                           int window, const mhpc_plan_out* out, int dtype, void* stream, float* ms);
+int api_export_results_device(Handle* h, int n, const int32_t* problems,
+                              const mhpc_results_out* out, int dtype, void* stream);
 int api_get_cost_gradients(Handle* h, int phase, int first, int count, double* lx, double* Phix);
 int api_update_problem(Handle* h, const mhpc_gait* gait);
 int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const int32_t* gait_of,

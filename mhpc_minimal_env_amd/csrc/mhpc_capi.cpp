@@ -159,6 +159,16 @@ extern "C" int mhpc_set_x0_device(mhpc_handle* h, const void* x0, int64_t ld, in
                                   void* stream) {
   FWD(set_x0_device, x0, ld, dtype, stream);
 }
+extern "C" int mhpc_export_plan_device(mhpc_handle* h, int n, const int32_t* problems,
+                                       const int32_t* first_step, int window,
+                                       const mhpc_plan_out* out, int dtype, void* stream,
+                                       float* ms) {
+  FWD(export_plan_device, n, problems, first_step, window, out, dtype, stream, ms);
+}
+extern "C" int mhpc_export_results_device(mhpc_handle* h, int n, const int32_t* problems,
+                                          const mhpc_results_out* out, int dtype, void* stream) {
+  FWD(export_results_device, n, problems, out, dtype, stream);
+}
 extern "C" int mhpc_get_cost_gradients(mhpc_handle* h, int phase, double* lx, double* Phix) {
   FWD(get_cost_gradients, phase, 0, batch_of(h), lx, Phix);
 }

@@ -129,6 +129,20 @@ hipError_t launch_control(const SolveParams& sp, const DevBufs& d, const int* st
 hipError_t launch_x0_in(const SolveParams& sp, const DevBufs& d, const void* x0, long ld, int dtype,
                         hipStream_t s);
 
+// ---- mhpc_plan_export.hip -------------------------------------------------------------------
+// launch_plan_export: `window` control steps from first[i] (device, null: 0) of listed problem
+// list[i] (device, null: problem i) into block i of each wanted array, by the map of
+// mhpc_plan_map.h, whose kinds index arrays [NKIND] (null: not wanted; all of dtype but mode,
+// int32) and ld [NKIND] (elements between two blocks, >= the dense block); valid [n] may be null.
+// The host has checked the list and every first step against the same map.
+hipError_t launch_plan_export(const SolveParams& sp, const DevBufs& d, int n, const int* list,
+                              const int* first, int window, int r, void* const* arrays,
+                              const long* ld, int32_t* valid, int dtype, hipStream_t s);
+// launch_results_export: arrays [5] = J, dV_exp, viol [n], V_phase, dV_phase [n][P] of dtype
+// (each may be null) and status [n] (may be null) of the listed problems, in list order
+hipError_t launch_results_export(const DevBufs& d, int n, const int* list, int P,
+                                 void* const* arrays, int32_t* status, int dtype, hipStream_t s);
+
 // ---- mhpc_bws.hip ---------------------------------------------------------------------------
 hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter, int part,
                       hipStream_t s);

@@ -17,6 +17,7 @@
 #include "mhpc_devtemp.h"
 #include "mhpc_launch.h"
 #include "mhpc_plan.h"
+#include "mhpc_plan_map.h"
 #include "mhpc_snapshot_map.h"
 
 extern thread_local std::string mhpc_g_err;  // mhpc_capi.cpp (mhpc_last_error)
@@ -1250,8 +1251,8 @@ static int dev_fail(const char* fn, hipError_t e) {
 }
 // One launch on the handle's stream between its ev0 / ev1, the outputs of t staged after it,
 // and the launch's time to *ms (ms may be null); all of it folded into t.e.
-template <class Launch>
-static void timed_launch(Handle* h, DevTemp<real>& t, float* ms, Launch launch) {
+template <class Temp, class Launch>
+static void timed_launch(Handle* h, Temp& t, float* ms, Launch launch) {
   if (t.e == hipSuccess) t.e = hipEventRecord(h->ev0, h->main.s1);
   if (t.e == hipSuccess) t.e = launch();
   if (t.e == hipSuccess) t.e = hipEventRecord(h->ev1, h->main.s1);
@@ -1528,6 +1529,104 @@ int api_set_x0_device(Handle* h, const void* x0, int64_t ld, int dtype, void* st
   HIPCHK(hipStreamSynchronize(h->main.s1));
   h->x0_set = true;
   h->x0_changed = true;  // as after mhpc_set_x0
+  return MHPC_OK;
+}
+
+// ---- device-resident plan export (k_plan_export, k_results_export: mhpc_plan_export.hip) ----
+// The list of a plan / results export: problems [n] checked (ProblemList), or null for the whole
+// batch in order (n == batch).
+static int export_list(const Handle* h, int n, const int32_t* problems) {
+  if (!problems) {
+    if (n != h->sp.B) return fail(MHPC_ERR_INVALID, "n must be the batch when problems is null");
+    return MHPC_OK;
+  }
+  ProblemList listed;
+  PLANCHK(listed.begin, n, h->sp.B, false);
+  for (int i = 0; i < n; ++i) PLANCHK(listed.add, problems[i]);
+  return MHPC_OK;
+}
+
+int api_export_plan_device(Handle* h, int n, const int32_t* problems, const int32_t* first_step,
+                           int window, const mhpc_plan_out* out, int dtype, void* stream,
+                           float* ms) {
+  namespace pm = mhpc_plan_map;
+  if (!h || !out) return fail(MHPC_ERR_INVALID, "null argument");
+  int rc = policy_ready(h);
+  if (rc) return rc;
+  if ((rc = check_dev_dtype(dtype))) return rc;
+  if ((rc = export_list(h, n, problems))) return rc;
+  if (window < 1 || window > MHPC_MAX_KNOTS)
+    return fail(MHPC_ERR_INVALID, "window must be 1..MHPC_MAX_KNOTS");
+  // every first step against the map the kernel runs, on each problem's own layout
+  for (int i = 0; first_step && i < n; ++i) {
+    const Layout& L = h->plan.lays[h->plan.lid[problems ? problems[i] : i]];
+    mhpc_ctrl::Knot q;
+    if (!mhpc_ctrl::knot_of(L.P, L.n_wb, L.N, L.ko, first_step[i], &q))
+      return fail(MHPC_ERR_INVALID, "first step outside 0..mhpc_num_control_steps - 1");
+  }
+  const int r = x0_row_of(h->plan);
+  void* arrays[pm::NKIND];
+  int64_t lds[pm::NKIND];
+  arrays[pm::X_NOM] = out->x_nom, lds[pm::X_NOM] = out->ld_x_nom;
+  arrays[pm::U_NOM] = out->u_nom, lds[pm::U_NOM] = out->ld_u_nom;
+  arrays[pm::GAIN] = out->K, lds[pm::GAIN] = out->ld_K;
+  arrays[pm::DU] = out->du, lds[pm::DU] = out->ld_du;
+  arrays[pm::VX] = out->Vx, lds[pm::VX] = out->ld_Vx;
+  arrays[pm::Y] = out->y, lds[pm::Y] = out->ld_y;
+  arrays[pm::MODE] = out->mode, lds[pm::MODE] = out->ld_mode;
+  const char* names[pm::NKIND] = {"x_nom", "u_nom", "K", "du", "Vx", "y", "mode"};
+  long ld[pm::NKIND];
+  bool any = out->valid != nullptr;
+  for (int k = 0; k < pm::NKIND; ++k) {
+    const long dense = pm::block(k, r, window);
+    ld[k] = dense;
+    if (!arrays[k]) continue;
+    any = true;
+    if (lds[k] != 0 && lds[k] < dense)
+      return fail(MHPC_ERR_INVALID, std::string("ld_") + names[k] + " below the dense block");
+    if (lds[k] != 0) ld[k] = (long)lds[k];
+  }
+  if (!any) return fail(MHPC_ERR_INVALID, "no array wanted");
+  HIPCHK(hipSetDevice(h->device));
+  for (int k = 0; k < pm::NKIND; ++k)
+    if (arrays[k] && (rc = check_device_ptr(h, arrays[k], names[k]))) return rc;
+  if (out->valid && (rc = check_device_ptr(h, out->valid, "valid"))) return rc;
+  // the list and the first steps: temporaries of this call, no array of the handle
+  DevTemp<int> t(h->main.s1);
+  const int* dlist = problems ? t.in(std::vector<int>(problems, problems + n)) : nullptr;
+  const int* dfirst = first_step ? t.in(std::vector<int>(first_step, first_step + n)) : nullptr;
+  if (t.e != hipSuccess) return dev_fail("mhpc_export_plan_device", t.e);
+  if ((rc = wait_for_caller(h, stream))) return rc;
+  timed_launch(h, t, ms, [&] {
+    return launch_plan_export(h->sp, h->d, n, dlist, dfirst, window, r, arrays, ld, out->valid,
+                              dtype, h->main.s1);
+  });
+  if (t.e != hipSuccess) return dev_fail("mhpc_export_plan_device", t.e);
+  return MHPC_OK;
+}
+
+int api_export_results_device(Handle* h, int n, const int32_t* problems,
+                              const mhpc_results_out* out, int dtype, void* stream) {
+  if (!h || !out) return fail(MHPC_ERR_INVALID, "null argument");
+  int rc = policy_ready(h);
+  if (rc) return rc;
+  if ((rc = check_dev_dtype(dtype))) return rc;
+  if ((rc = export_list(h, n, problems))) return rc;
+  void* arrays[5] = {out->J, out->dV_exp, out->viol, out->V_phase, out->dV_phase};
+  const char* names[5] = {"J", "dV_exp", "viol", "V_phase", "dV_phase"};
+  bool any = out->status != nullptr;
+  for (int k = 0; k < 5; ++k) any = any || arrays[k];
+  if (!any) return fail(MHPC_ERR_INVALID, "no array wanted");
+  HIPCHK(hipSetDevice(h->device));
+  for (int k = 0; k < 5; ++k)
+    if (arrays[k] && (rc = check_device_ptr(h, arrays[k], names[k]))) return rc;
+  if (out->status && (rc = check_device_ptr(h, out->status, "status"))) return rc;
+  DevTemp<int> t(h->main.s1);
+  const int* dlist = problems ? t.in(std::vector<int>(problems, problems + n)) : nullptr;
+  if (t.e != hipSuccess) return dev_fail("mhpc_export_results_device", t.e);
+  if ((rc = wait_for_caller(h, stream))) return rc;
+  t.e = launch_results_export(h->d, n, dlist, h->sp.pmax, arrays, out->status, dtype, h->main.s1);
+  if (t.fetch() != hipSuccess) return dev_fail("mhpc_export_results_device", t.e);  // the sync
   return MHPC_OK;
 }
 

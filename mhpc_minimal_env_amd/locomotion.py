@@ -1075,6 +1075,149 @@ class MHPCLocomotion:
                    "mhpc_control_device")
         return res
 
+    # -- device-resident plan export: policy windows and results into tensors -------------------
+    def _export_list(self, problems):
+        """(int32 list or None, n) of an export's problems; None: the whole batch in order."""
+        if problems is None:
+            return None, self.batch
+        lst = np.asarray(problems)
+        if lst.ndim != 1 or lst.size < 1 or not np.issubdtype(lst.dtype, np.integer):
+            raise ValueError("problems must be a list of ints")
+        if lst.min() < 0 or lst.max() >= self.batch or np.unique(lst).size != lst.size:
+            raise ValueError("problems: each in 0..batch-1, none twice")
+        return np.ascontiguousarray(lst, dtype=np.int32), int(lst.size)
+
+    def _export_dtype(self, dtype, out, int_names):
+        """The element type of an export's float tensors: dtype, or that of out's, or float64."""
+        import torch
+        floats = [t for k, t in (out or {}).items() if k not in int_names and isinstance(t, torch.Tensor)]
+        if dtype is None:
+            dtype = floats[0].dtype if floats else torch.float64
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("dtype must be torch.float32 or torch.float64")
+        return dtype
+
+    def _device_block(self, t, shape, dtype, name: str):
+        """(pointer, elements between two problems' blocks) of a torch tensor [n][...] on the
+        handle's device whose blocks are dense inside (a view with a larger leading stride is
+        fine: a slice [:, t] of a dataset buffer); ValueError for anything the library could
+        not address, as _device_rows."""
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must be {dtype}")
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"{name} must be on the handle's device")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} must be {list(shape)}")
+        dense = 1
+        for d in range(t.dim() - 1, 0, -1):
+            if t.shape[d] != 1 and t.stride(d) != dense:
+                raise ValueError(f"{name} must be contiguous inside a problem's block")
+            dense *= t.shape[d]
+        if shape[0] > 1 and t.stride(0) < dense:
+            raise ValueError(f"{name} must have a leading stride >= {dense}")
+        return t.data_ptr(), (int(t.stride(0)) if shape[0] > 1 else 0)
+
+    def export_plan(self, problems=None, first_step=0, window=None,
+                    want=("x_nom", "u_nom", "K"), dtype=None, out=None) -> dict:
+        """The next `window` control steps of every listed problem's policy, from first_step (an
+        int, or one per listed problem), into torch tensors on the handle's device
+        (mhpc_export_plan_device; nothing crosses the host).  Row i belongs to problems[i] (None:
+        the whole batch in order); window None: the largest step count among the listed problems.
+        Entries of want: "x_nom" [n][W][r], "u_nom" [n][W][4], "K" [n][W][4][r], "du" [n][W][4],
+        "Vx" [n][W][r], "y" [n][W][4] of dtype (torch.float64, the default, or torch.float32) and
+        "mode" [n][W] int32; "valid" [n] int32 -- the steps of each window that exist -- is always
+        returned.  Every value is what get_phase_problems reports for the step's (phase, knot);
+        rows past valid and columns past a problem's state size are +0.  out: {name: tensor} to
+        write into the caller's own tensors (wanted too), inner-contiguous views with any leading
+        stride >= the block -- a slice [:, t] of a dataset buffer [n][T][W][c]; the bytes between
+        the blocks are kept.  The device time of the launch is left in self.last_export_ms."""
+        import ctypes
+        import torch
+        kinds = ("x_nom", "u_nom", "K", "du", "Vx", "y", "mode")
+        out = dict(out or {})
+        names = list(dict.fromkeys([*want, *out]))
+        if any(k not in kinds + ("valid",) for k in names):
+            raise ValueError('want: some of "x_nom", "u_nom", "K", "du", "Vx", "y", "mode"')
+        lst, n = self._export_list(problems)
+        if self.descs is None:  # one layout: one count
+            steps = np.full(n, self.num_control_steps(0))
+        else:
+            steps = np.array([self.num_control_steps(int(b)) for b in (range(n) if lst is None else lst)])
+        fs = np.asarray(first_step)
+        if not np.issubdtype(fs.dtype, np.integer) or fs.ndim > 1:
+            raise ValueError("first_step must be an int or one int per listed problem")
+        fs = np.full(n, int(fs)) if fs.ndim == 0 else fs
+        if fs.shape != (n,):
+            raise ValueError("first_step must be an int or one int per listed problem")
+        if ((fs < 0) | (fs >= steps)).any():
+            raise ValueError("first_step outside 0..num_control_steps - 1")
+        fs = np.ascontiguousarray(fs, dtype=np.int32) if fs.any() else None  # (None: step 0, no upload)
+        W = int(steps.max()) if window is None else int(window)
+        if W < 1 or W > capi.MHPC_MAX_KNOTS:
+            raise ValueError("window must be 1..MHPC_MAX_KNOTS")
+        dtype = self._export_dtype(dtype, out, ("mode", "valid"))
+        r = self._x0_row()
+        dev = torch.device("cuda", self.device)
+        inner = {"x_nom": (r,), "u_nom": (4,), "K": (4, r), "du": (4,), "Vx": (r,), "y": (4,),
+                 "mode": ()}
+        po, res = capi.PlanOut(), {}
+        for k in names:
+            if k == "valid":
+                continue
+            shape, dt = (n, W, *inner[k]), (torch.int32 if k == "mode" else dtype)
+            res[k] = out[k] if k in out else torch.empty(shape, dtype=dt, device=dev)
+            ptr, ld = self._device_block(res[k], shape, dt, k)
+            setattr(po, k, ptr)
+            setattr(po, "ld_" + k, ld)
+        res["valid"] = out["valid"] if "valid" in out else torch.empty((n,), dtype=torch.int32, device=dev)
+        po.valid, _ = self._device_block(res["valid"], (n,), torch.int32, "valid")
+        if n > 1 and res["valid"].stride(0) != 1:
+            raise ValueError("valid must be contiguous")
+        ms = ctypes.c_float(0)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        capi.check(capi.lib().mhpc_export_plan_device(
+            self._h, n, capi.iptr(lst), capi.iptr(fs), W, ctypes.byref(po),
+            capi.MHPC_DEV_F32 if dtype == torch.float32 else capi.MHPC_DEV_F64, stream,
+            ctypes.byref(ms)), "mhpc_export_plan_device")
+        self.last_export_ms = ms.value
+        return res
+
+    def export_results(self, problems=None, want=("J", "viol", "status"), dtype=None,
+                       out=None) -> dict:
+        """The listed problems' results of their last solve into torch tensors on the handle's
+        device (mhpc_export_results_device): "J", "dV_exp", "viol" [n], "V_phase", "dV_phase"
+        [n][max_phases()] (zero past a problem's own phases) of dtype, as get_scalars reports
+        them, and "status" [n] int32 as solve_mhpc returns it.  out: {name: tensor}, contiguous."""
+        import ctypes
+        import torch
+        kinds = ("J", "dV_exp", "viol", "V_phase", "dV_phase", "status")
+        out = dict(out or {})
+        names = list(dict.fromkeys([*want, *out]))
+        if not names or any(k not in kinds for k in names):
+            raise ValueError('want: some of "J", "dV_exp", "viol", "V_phase", "dV_phase", "status"')
+        lst, n = self._export_list(problems)
+        dtype = self._export_dtype(dtype, out, ("status",))
+        dev = torch.device("cuda", self.device)
+        P = self.max_phases()
+        ro, res = capi.ResultsOut(), {}
+        for k in names:
+            shape = (n, P) if k in ("V_phase", "dV_phase") else (n,)
+            dt = torch.int32 if k == "status" else dtype
+            res[k] = out[k] if k in out else torch.empty(shape, dtype=dt, device=dev)
+            ptr, _ = self._device_block(res[k], shape, dt, k)
+            if not res[k].is_contiguous():
+                raise ValueError(f"{k} must be contiguous")
+            setattr(ro, k, ptr)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        capi.check(capi.lib().mhpc_export_results_device(
+            self._h, n, capi.iptr(lst), ctypes.byref(ro),
+            capi.MHPC_DEV_F32 if dtype == torch.float32 else capi.MHPC_DEV_F64, stream),
+            "mhpc_export_results_device")
+        return res
+
     def get_x0(self) -> np.ndarray:
         """The device's current initial states [batch][r] (mhpc_get_x0)."""
         x0 = np.zeros((self.batch, self._x0_row()))
