@@ -23,6 +23,7 @@
 #include <string>
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <thread>
 #include <vector>
 
@@ -1261,6 +1262,45 @@ extern "C" int oracle_rollout_costs(const mhpc_problem_desc* desc, const mhpc_hs
   return 0;
 }
 
+// The feedback policy a solve leaves, u = u_nom + K (x - x_nom), run from other start states:
+// per sample set_initial_condition(x) + forward_sweep_dynamics_only(0) over every phase
+// (SinglePhase.cpp:117-144 with eps = 0; MultiPhaseDDP.cpp:351-379 between phases) -- the
+// counterpart of mhpc_rollout_policy over all phases.  References, AL / ReB parameters,
+// nominal and gains stay as the solve left them; only the start state (and with it the SRB
+// phases' footholds) follows the sample.  xs [batch][n_samples][xsize of phase 0];
+// J / viol: [batch][n_samples].  do_solve = 0 evaluates right after initialization.
+extern "C" int oracle_policy_costs(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt,
+                                   int batch, const double* x0, int nthreads, int do_solve,
+                                   int n_samples, const double* xs, double* J, double* viol) {
+  if (!g_ref.handle) return 3;
+  const int np = desc->n_wb + desc->n_fb;
+  if (np < 1 || np > MHPC_MAX_PHASES || n_samples < 1) return 1;
+  const int n0 = desc->n_wb > 0 ? 14 : 6;
+  std::atomic<int> next(0);
+  auto worker = [&]() {
+    for (;;) {
+      const int b = next.fetch_add(1);
+      if (b >= batch) break;
+      Problem P;
+      build(P, desc, opt, x0 + (size_t)b * n0);
+      if (do_solve) mp_solve(P);
+      for (int s = 0; s < n_samples; ++s) {
+        memset(P.x0, 0, sizeof P.x0);
+        memcpy(P.x0, xs + ((size_t)b * n_samples + s) * n0, sizeof(double) * n0);
+        mp_forward_sweep(P, 0, true);
+        J[(size_t)b * n_samples + s] = P.actual_cost;
+        viol[(size_t)b * n_samples + s] = P.tconstr_violation;
+      }
+    }
+  };
+  if (nthreads < 1) nthreads = 1;
+  std::vector<std::thread> th;
+  for (int t = 1; t < nthreads; ++t) th.emplace_back(worker);
+  worker();
+  for (auto& t : th) t.join();
+  return 0;
+}
+
 // The cost gradients print_debugInfo writes to cost.txt (MHPCLocomotion.cpp:355-377) after
 // a solve: rcost[k].lx of knots 0..N-2 and tcost.Phix of every phase, phase-concatenated:
 // LX [batch][sum_p (N_p - 1) n_p], PHIX [batch][sum_p n_p].
@@ -1306,11 +1346,17 @@ extern "C" int oracle_cost_gradients(const mhpc_problem_desc* desc, const mhpc_h
 // x0s [ticks][batch][n0]; per tick: J, viol [ticks][batch], trace [ticks][batch][TRACE],
 // N_out, modes_out [ticks][n_phases]; after the last tick the nominal X, U and K, G of every
 // phase, phase-concatenated into X [batch][cap_x] etc. with cap = n_phases * 110 knots.
-extern "C" int oracle_mpc(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt,
-                          int n_modes, const int* gait_modes, const float* gait_timings,
-                          int batch, int ticks, const double* x0s, int nthreads, double* J,
-                          double* viol, int32_t* trace, int32_t* N_out, int32_t* modes_out,
-                          double* X, double* U, double* K, double* G) {
+//
+// mpc_impl is the loop itself.  opt_last (may be null) replaces the option record before the
+// last tick's solve (the reference's `_option = o` between two ticks); after (may be null) runs
+// on every problem as the last tick's solve leaves it.
+static int mpc_impl(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt,
+                    int n_modes, const int* gait_modes, const float* gait_timings,
+                    int batch, int ticks, const double* x0s, int nthreads, double* J,
+                    double* viol, int32_t* trace, int32_t* N_out, int32_t* modes_out,
+                    double* X, double* U, double* K, double* G,
+                    const mhpc_hsddp_option* opt_last,
+                    const std::function<void(Problem&, int)>* after) {
   if (!g_ref.handle) return 3;
   const int np = desc->n_wb + desc->n_fb;
   if (np < 1 || np > MHPC_MAX_PHASES || ticks < 1 || n_modes < 1) return 1;
@@ -1385,7 +1431,10 @@ extern "C" int oracle_mpc(const mhpc_problem_desc* desc, const mhpc_hsddp_option
         }
         for (int i = 0; i < MHPC_TRACE_LEN; ++i) P.trace[i] = -1;
         P.ntrace = 0;
+        if (opt_last && t == ticks - 1) P.opt = *opt_last;
         mp_solve(P);
+        if (after && t == ticks - 1) (*after)(P, b);
+        if (!J) continue;  // the caller reads the last tick through `after` alone
         J[(size_t)t * batch + b] = P.actual_cost;
         viol[(size_t)t * batch + b] = P.tconstr_violation;
         memcpy(trace + ((size_t)t * batch + b) * MHPC_TRACE_LEN, P.trace,
@@ -1396,6 +1445,7 @@ extern "C" int oracle_mpc(const mhpc_problem_desc* desc, const mhpc_hsddp_option
             modes_out[t * np + p] = dl.mode_seq[p];
           }
       }
+      if (!X) continue;
       const size_t cap = (size_t)np * NBK;
       double* xo = X + (size_t)b * cap * 14;
       double* uo = U + (size_t)b * cap * 4;
@@ -1416,4 +1466,51 @@ extern "C" int oracle_mpc(const mhpc_problem_desc* desc, const mhpc_hsddp_option
   worker();
   for (auto& t : th) t.join();
   return err.load();
+}
+
+extern "C" int oracle_mpc(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt,
+                          int n_modes, const int* gait_modes, const float* gait_timings,
+                          int batch, int ticks, const double* x0s, int nthreads, double* J,
+                          double* viol, int32_t* trace, int32_t* N_out, int32_t* modes_out,
+                          double* X, double* U, double* K, double* G) {
+  return mpc_impl(desc, opt, n_modes, gait_modes, gait_timings, batch, ticks, x0s, nthreads, J,
+                  viol, trace, N_out, modes_out, X, U, K, G, nullptr, nullptr);
+}
+
+// The receding-horizon loop with the last tick solved under opt_last, and what the gradient
+// identities (tests/_gradient_identities.py) read from the state that solve leaves: J, dV,
+// viol [batch], trace [batch][MHPC_TRACE_LEN], G0 [batch][n0] (Vx at knot 0 of phase 0), the
+// trial rollouts' costs Jeps [batch][n_eps] (as oracle_rollout_costs) and the policy's costs
+// Jpol [batch][n_samples] from xs [batch][n_samples][n0] (as oracle_policy_costs); n_eps or
+// n_samples may be 0.
+extern "C" int oracle_mpc_last_tick(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt,
+                                    const mhpc_hsddp_option* opt_last, int n_modes,
+                                    const int* gait_modes, const float* gait_timings, int batch,
+                                    int ticks, const double* x0s, int nthreads, double* J,
+                                    double* dV, double* viol, int32_t* trace, double* G0,
+                                    int n_eps, const double* eps, double* Jeps, int n_samples,
+                                    const double* xs, double* Jpol) {
+  if (!opt_last || n_eps < 0 || n_samples < 0) return 1;
+  const int n0 = desc->n_wb > 0 ? 14 : 6;
+  const std::function<void(Problem&, int)> after = [&](Problem& P, int b) {
+    J[b] = P.actual_cost;
+    dV[b] = P.exp_cost_change;
+    viol[b] = P.tconstr_violation;
+    for (int i = 0; i < MHPC_TRACE_LEN; ++i)
+      trace[(size_t)b * MHPC_TRACE_LEN + i] = i < P.ntrace ? P.trace[i] : -1;
+    memcpy(G0 + (size_t)b * n0, P.ph[0].ctg[0].G, sizeof(double) * n0);
+    for (int e = 0; e < n_eps; ++e) {
+      mp_forward_sweep(P, eps[e], true);
+      Jeps[(size_t)b * n_eps + e] = P.actual_cost;
+    }
+    for (int s = 0; s < n_samples; ++s) {
+      memset(P.x0, 0, sizeof P.x0);
+      memcpy(P.x0, xs + ((size_t)b * n_samples + s) * n0, sizeof(double) * n0);
+      mp_forward_sweep(P, 0, true);
+      Jpol[(size_t)b * n_samples + s] = P.actual_cost;
+    }
+  };
+  return mpc_impl(desc, opt, n_modes, gait_modes, gait_timings, batch, ticks, x0s, nthreads,
+                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                  opt_last, &after);
 }

@@ -32,6 +32,14 @@ int oracle_solve(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, in
                  double* K, double* DU, double* G, double* J, double* dV, double* viol,
                  double* Vp, double* dVp, int32_t* status, int32_t* trace, int64_t* counters);
 
+/* The policy a solve leaves (u = u_nom + K (x - x_nom)) run from the start states
+ * xs [batch][n_samples][xsize of phase 0] over every phase: per sample the reference's
+ * set_initial_condition + forward_sweep_dynamics_only(0).  References, AL / ReB parameters,
+ * nominal and gains stay untouched.  J, viol [batch][n_samples]. */
+int oracle_policy_costs(const mhpc_problem_desc* desc, const mhpc_hsddp_option* opt, int batch,
+                        const double* x0, int nthreads, int do_solve, int n_samples,
+                        const double* xs, double* J, double* viol);
+
 #ifdef __cplusplus
 }
 #endif

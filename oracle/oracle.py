@@ -116,6 +116,28 @@ def rollout_costs(desc: capi.ProblemDesc, opt: capi.HsddpOption, x0: np.ndarray,
     return {"J": J, "viol": viol, "rollout_cpu_seconds": secs.value}
 
 
+def policy_costs(desc: capi.ProblemDesc, opt: capi.HsddpOption, x0: np.ndarray, xs,
+                 nthreads: int = 1, do_solve: bool = True) -> dict:
+    """The policy the solve leaves, run from the start states xs [batch][n_samples][n0] over
+    every phase (oracle_policy_costs); returns J and viol of shape [batch][n_samples]."""
+    x0 = np.ascontiguousarray(x0, dtype=np.float64)
+    xs = np.ascontiguousarray(xs, dtype=np.float64)
+    B = x0.shape[0]
+    if xs.ndim != 3 or xs.shape[0] != B or xs.shape[2] != x0.shape[1]:
+        raise ValueError("xs must be [batch][n_samples][n0]")
+    S = xs.shape[1]
+    J = np.zeros((B, S))
+    viol = np.zeros((B, S))
+    L = lib()
+    L.oracle_policy_costs.restype = ctypes.c_int
+    rc = L.oracle_policy_costs(ctypes.byref(desc), ctypes.byref(opt), ctypes.c_int(B), _p(x0),
+                               ctypes.c_int(nthreads), ctypes.c_int(1 if do_solve else 0),
+                               ctypes.c_int(S), _p(xs), _p(J), _p(viol))
+    if rc != 0:
+        raise RuntimeError(f"oracle_policy_costs failed ({rc})")
+    return {"J": J, "viol": viol}
+
+
 def cost_gradients(desc: capi.ProblemDesc, opt: capi.HsddpOption, x0: np.ndarray,
                    nthreads: int = 1) -> dict:
     """lx / Phix as print_debugInfo's cost.txt holds them after a solve; phase-concatenated
@@ -163,6 +185,37 @@ def mpc(desc: capi.ProblemDesc, opt: capi.HsddpOption, gait, x0s: np.ndarray,
                                                  "K", "G")])
     if rc != 0:
         raise RuntimeError(f"oracle_mpc failed ({rc})")
+    return out
+
+
+def mpc_last_tick(desc: capi.ProblemDesc, opt: capi.HsddpOption, opt_last: capi.HsddpOption, gait,
+                  x0s: np.ndarray, eps=(), xs=None, nthreads: int = 1) -> dict:
+    """The receding-horizon loop of mpc() with the last tick solved under opt_last
+    (oracle_mpc_last_tick): J, dV_exp, viol [batch], trace, G0 [batch][n0] of that solve, its
+    trial rollouts' costs J_eps [batch][len(eps)] and its policy's costs J_policy
+    [batch][n_samples] from xs [batch][n_samples][n0]."""
+    x0s = np.ascontiguousarray(x0s, dtype=np.float64)
+    T, B, n0 = x0s.shape
+    eps = np.ascontiguousarray(eps, dtype=np.float64)
+    xs = np.zeros((B, 0, n0)) if xs is None else np.ascontiguousarray(xs, dtype=np.float64)
+    if xs.ndim != 3 or xs.shape[0] != B or xs.shape[2] != n0:
+        raise ValueError("xs must be [batch][n_samples][n0]")
+    g = gait.to_c()
+    modes = np.array(list(g.modes)[:g.n_modes], dtype=np.int32)
+    tim = np.array(list(g.timings)[:g.n_modes], dtype=np.float32)
+    out = {"J": np.zeros(B), "dV_exp": np.zeros(B), "viol": np.zeros(B),
+           "trace": np.zeros((B, TRACE_LEN), dtype=np.int32), "G0": np.zeros((B, n0)),
+           "J_eps": np.zeros((B, eps.shape[0])), "J_policy": np.zeros((B, xs.shape[1]))}
+    L = lib()
+    L.oracle_mpc_last_tick.restype = ctypes.c_int
+    rc = L.oracle_mpc_last_tick(
+        ctypes.byref(desc), ctypes.byref(opt), ctypes.byref(opt_last), ctypes.c_int(int(g.n_modes)),
+        _p(modes), _p(tim), ctypes.c_int(B), ctypes.c_int(T), _p(x0s), ctypes.c_int(nthreads),
+        _p(out["J"]), _p(out["dV_exp"]), _p(out["viol"]), _p(out["trace"]), _p(out["G0"]),
+        ctypes.c_int(eps.shape[0]), _p(eps), _p(out["J_eps"]), ctypes.c_int(xs.shape[1]), _p(xs),
+        _p(out["J_policy"]))
+    if rc != 0:
+        raise RuntimeError(f"oracle_mpc_last_tick failed ({rc})")
     return out
 
 
