@@ -394,6 +394,22 @@ struct PendingKnot {
   bool ok;
   int k;
   breal K[4], du[4], G;
+  // state lanes (xrow) store their column of K (NX apart per control) and entry of G, one
+  // control lane (urow) du
+  template <int NX>
+  __device__ __forceinline__ void store(bool xrow, bool urow, real* K0, real* G0, real* du0) {
+    if (ok) {
+      if (xrow) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) K0[k * 56 + a * NX] = K[a];
+        G0[k * 14] = G;
+      } else if (urow) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) du0[k * 4 + a] = du[a];
+      }
+    }
+    ok = false;
+  }
 };
 __device__ __forceinline__ bool any_go(const RowCtx& r) {
   return __builtin_amdgcn_ballot_w64(go(r)) != 0;
@@ -433,38 +449,63 @@ __device__ unsigned long long g_bws_cyc[16];
 #define BWS_ITERS(n) 0
 #endif
 
-template <bool STANCE>
+// Two rows per problem (RPP = 2, the launch shape for batches that leave SIMDs idle).  Both rows
+// hold the value function (row rho(t) on lane t) and the control columns 14..17; row A computes
+// the configuration columns 0..6 of S and Q, row B the velocity columns 7..13 in the same
+// register slots.  Row B's broadcast copy of [A B] puts column 7 + s on lane 2 s, so both rows
+// run the same instruction stream with the same DPP lane immediates (the S/Q blocks shrink from
+// 18 + 1 to 11 + 1 columns per row).  The transpose writes each row's half of Qxx to the shared
+// LDS block; each row updates its seven columns of H, and one v_permlane16_swap per word gives
+// both rows the full rows of H.  Every entry is computed with the one-row sweep's operations in
+// the same order, so the two layouts agree bit for bit (tests/test_gpu_variants.py).
+//
+// The two layouts are one function: what differs sits behind `if constexpr (TWO)`, and the
+// device code of every instantiation is the text the two separate functions compiled to
+// (profiles/bws_refactor_ab.md).
+template <bool STANCE, int RPP>
 __device__ int sweep_wb(const SolveParams& sp, const DevBufs& d, const Layout& L, const CostParams& cw, const ProbState* st, RowLds& rl,
                          RowCtx& rc, int p) {
   using R = Rows<7>;
   using wk = wreal;
-  const int t = rc.t, b = rc.b;
+  constexpr bool TWO = RPP == 2;
+  constexpr int NH = TWO ? 7 : 14;    // H columns a row computes; its first control slot of S / Q
+  constexpr int NSQ = TWO ? 11 : 18;  // S / Q slots of a row: NH columns of x, four of u
+  const int t = rc.t, b = rc.b, rp = TWO ? rc.rp : 0;
   const int N = L.N[p], ko = L.ko[p], mode = L.mode[p];
   const breal dt = L.dt[p];
   const int rho = R::rho(t);
   const bool xl = t < 14;
   const breal coef = xl ? ((t & 1) ? dt : breal(1.0)) : breal(0.0);
+  const breal coefS = rp ? dt : breal(1.0);  // two rows' S init: column s (row A) / 7 + s (row B)
+  // broadcast column of the lane: its own (one row; row A, odd lanes, lanes 14 / 15) or, on
+  // row B's even lanes 2 s, the velocity column 7 + s
+  const int cb = (rp && xl && !(t & 1)) ? 7 + (t >> 1) : rho;
   // identity part of W: W[r][c] = dt * rec + (c == 7 + r)
-  breal base[7];
+  breal base[7], baseb[TWO ? 7 : 1];
 #pragma unroll
-  for (int r = 0; r < 7; ++r) base[r] = rho == 7 + r ? breal(1.0) : breal(0.0);
+  for (int r = 0; r < 7; ++r) {
+    base[r] = rho == 7 + r ? breal(1.0) : breal(0.0);
+    if constexpr (TWO) baseb[r] = cb == 7 + r ? breal(1.0) : breal(0.0);
+  }
   // running-cost weight and fixed reference of state rho (CostBase.cpp:28-31)
   const int xi = xl ? rho : 0;
   const breal w2 = 2 * dt * cw.wQ[mode - 1][xi];
   const breal rxc = xi == 1 ? rc.cm.height : xi == 2 ? breal(0.0)
                    : (xi >= 3 && xi < 7) ? cQjointBias[xi - 3] : xi == 7 ? rc.cm.vel : breal(0.0);
   // lxx + reg on the diagonal of Qxx (Ixx * regularisation): added twice to the transposed
-  // copy in LDS, so that (Qxx + Qxx') / 2 carries it once
-  const breal dg2 = xl ? 2 * (w2 + rc.reg) : breal(0.0);
+  // copy in LDS, so that (Qxx + Qxx') / 2 carries it once -- by the row that owns the
+  // diagonal's column
+  const bool own_diag = xl && (!TWO || (rho < 7) == (rp == 0));
+  const breal dg2 = own_diag ? 2 * (w2 + rc.reg) : breal(0.0);
   const real* pos = d.refpos + (size_t)b * sp.NK + ko;
-  // prefetch registers (record of one knot): the lane's own column of [Ac Bc; C D], the
-  // second control column set (lanes 14, 15), one cost derivative per lane (broadcast below)
+  // prefetch registers (record of one knot): the lane's own column of [Ac Bc; C D], its
+  // broadcast column (two rows), the second control column set (lanes 14, 15), one cost
+  // derivative per lane (broadcast below)
   constexpr int NR = STANCE ? 9 : 7;  // rows of a record column read
   constexpr int NCS = STANCE ? 14 : 8;  // cost derivatives (lu, luu [, ly, lyy])
   // (in the record type: a float record converted at load time would make the compiler wait
   // for the load there, a knot early; converted at the use instead -- the same values)
-  real pr1[NR], pr2[NR], pcv, pxn, ppos;
-  const int c1 = rho;            // record column of W1 (0..15)
+  real pr1[NR], prb[TWO ? NR : 1], pr2[NR], pcv, pxn, ppos;
   const int c2 = 16 + (t & 1);   // second set: control columns 2, 3 (lanes 14, 15)
   const int cq = t < NCS ? t : 0;
   // (the nominal state first: the wait for the last load of a knot then never covers the
@@ -472,16 +513,22 @@ __device__ int sweep_wb(const SolveParams& sp, const DevBufs& d, const Layout& L
   // the phase's operand bases (knot 0): a knot adds k times its record stride
   const real* tk0 = traj_ptr(sp, d, b, rc.nom, ko) + xi;
   const real* jc0 = d.par + par_jac(sp.NK, b, ko) + cq;
-  const real* r10 = d.par + par_col(sp.NK, b, c1, ko);
+  const real* r10 = d.par + par_col(sp.NK, b, rho, ko);
+  const real* rb0 = d.par + par_col(sp.NK, b, cb, ko);
   const real* r20 = d.par + par_col(sp.NK, b, c2, ko);
   auto load = [&](int k) {
     pxn = tk0[k * KS];
     ppos = pos[k];
     pcv = jc0[k * 14];
     const real* r1 = r10 + k * 9;
+    const real* rb = rb0 + k * 9;
     const real* r2 = r20 + k * 9;
 #pragma unroll
     for (int r = 0; r < NR; ++r) pr1[r] = r1[r];
+    if constexpr (TWO) {
+#pragma unroll
+      for (int r = 0; r < NR; ++r) prb[r] = rb[r];
+    }
 #pragma unroll
     for (int r = 0; r < NR; ++r) pr2[r] = r2[r];
   };
@@ -492,7 +539,15 @@ __device__ int sweep_wb(const SolveParams& sp, const DevBufs& d, const Layout& L
     for (int j = 0; j < 14; ++j) H[j] = rl.M[at(hr, j)];
     Gv = rl.Gs[hr];
   }
-  const int cr = rho;  // column of M read in the transpose (Qxu columns for lanes 14, 15)
+  // Column of M read in the transpose.  One row: the lane's own (Qxu columns for lanes 14, 15).
+  // Two rows: lanes 14, 15 (no row of Qxx) read column 0 with lane 0 (a broadcast): columns 14,
+  // 15 are never written in this layout, and a filler lane's H row still enters 0 * x products,
+  // so it must stay finite; in the row-major layout matrix column c is at LDS column mcol(c)
+  // (row B's half 16-byte aligned)
+  auto mcol = [](int c) { return !TWO || MHPC_LDS_COLMAJOR ? c : (c < 7 ? c : c + 1); };
+  const int cr = TWO && !xl ? 0 : mcol(rho);
+  const int wo = rp ? mcol(7) : 0;      // LDS column of the row's first Q slot
+  const int jr = rp ? 7 : 0;            // first matrix row of the row's H columns
   // The outputs (K, du, G) of a knot are stored one knot later, right before the next
   // prefetch: every global operation of a knot is then issued together after the wait for the
   // previous prefetch, and the next such wait (a knot later) finds the stores retired --
@@ -503,36 +558,41 @@ __device__ int sweep_wb(const SolveParams& sp, const DevBufs& d, const Layout& L
   real* const K0 = d.K + rec0 * 56 + rho;
   real* const G0 = d.G + rec0 * 14 + rho;
   real* const du0 = d.du + rec0 * 4;
-  auto store_pending = [&]() {
-    if (pend.ok) {
-      if (xl) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) K0[pend.k * 56 + a * 14] = pend.K[a];
-        G0[pend.k * 14] = pend.G;
-      } else if (t == 14) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) du0[pend.k * 4 + a] = pend.du[a];
-      }
-    }
-    pend.ok = false;
-  };
+  auto store_pending = [&]() { pend.store<14>(xl, t == 14, K0, G0, du0); };
   if (N >= 2) load(N - 2);
   int it = 0;  // knot iterations the wave ran (the cycle accounting's knot count)
   for (int k = N - 2; k >= 0; --k) {
     ++it;
     // ---- the knot's derivatives (prefetched) ----
-    breal W1[7], W2[7], G2o[2], G22[2];
+    // W of the lane's own column, of its broadcast column (one row: the same), of the second
+    // control set; likewise the C, D rows G2o, G2b, G22 (Wrb, G2rb: the two-row storage)
+    breal Wo[7], Wrb[TWO ? 7 : 1], W2[7], G2o[2], G2rb[2], G22[2];
+    const breal* const Wb = TWO ? Wrb : Wo;
+    const breal* const G2b = TWO ? G2rb : G2o;
+    if constexpr (TWO) {
 #pragma unroll
-    for (int r = 0; r < 7; ++r) W1[r] = __builtin_fma(breal(pr1[r]), dt, base[r]);
+      for (int r = 0; r < 7; ++r) {
+        Wo[r] = __builtin_fma(breal(pr1[r]), dt, base[r]);
+        Wrb[r] = __builtin_fma(breal(prb[r]), dt, baseb[r]);
+        W2[r] = __builtin_fma(breal(pr2[r]), dt, breal(0.0));
+      }
+    } else {
 #pragma unroll
-    for (int r = 0; r < 7; ++r) W2[r] = __builtin_fma(breal(pr2[r]), dt, breal(0.0));
+      for (int r = 0; r < 7; ++r) Wo[r] = __builtin_fma(breal(pr1[r]), dt, base[r]);
+#pragma unroll
+      for (int r = 0; r < 7; ++r) W2[r] = __builtin_fma(breal(pr2[r]), dt, breal(0.0));
+    }
     // C, D rows: copied out of the prefetch registers (a fresh value each, so the prefetch
     // buffer is dead before it is reloaded; a buffer live across its own reload costs a copy
     // at the back edge that waits for every outstanding memory operation, stores included)
-    G2o[0] = G2o[1] = G22[0] = G22[1] = breal(0.0);
+    G2o[0] = G2o[1] = G2rb[0] = G2rb[1] = G22[0] = G22[1] = breal(0.0);
     if (STANCE) {
       asm volatile("" : "=v"(G2o[0]) : "0"(breal(pr1[NR - 2])));
       asm volatile("" : "=v"(G2o[1]) : "0"(breal(pr1[NR - 1])));
+      if constexpr (TWO) {
+        asm volatile("" : "=v"(G2rb[0]) : "0"(breal(prb[NR - 2])));
+        asm volatile("" : "=v"(G2rb[1]) : "0"(breal(prb[NR - 1])));
+      }
       asm volatile("" : "=v"(G22[0]) : "0"(breal(pr2[NR - 2])));
       asm volatile("" : "=v"(G22[1]) : "0"(breal(pr2[NR - 1])));
     }
@@ -556,24 +616,33 @@ __device__ int sweep_wb(const SolveParams& sp, const DevBufs& d, const Layout& L
     // everything derived from the prefetch registers before they are reloaded: the loads
     // (memory operations) stay behind these volatile statements, so the buffers of knot k
     // and k - 1 share registers (no copy of a loop-carried buffer at the back edge)
-    asm volatile("" ::"v"(W1[0]), "v"(W1[1]), "v"(W1[2]), "v"(W1[3]), "v"(W1[4]), "v"(W1[5]),
-                 "v"(W1[6]), "v"(W2[0]), "v"(W2[1]), "v"(W2[2]), "v"(W2[3]), "v"(W2[4]),
+    asm volatile("" ::"v"(Wo[0]), "v"(Wo[1]), "v"(Wo[2]), "v"(Wo[3]), "v"(Wo[4]), "v"(Wo[5]),
+                 "v"(Wo[6]), "v"(W2[0]), "v"(W2[1]), "v"(W2[2]), "v"(W2[3]), "v"(W2[4]),
                  "v"(W2[5]), "v"(W2[6]), "v"(l1), "v"(l2));
     asm volatile("" ::"v"(G2o[0]), "v"(G2o[1]), "v"(G22[0]), "v"(G22[1]), "v"(luu[0]),
                  "v"(luu[1]), "v"(luu[2]), "v"(luu[3]), "v"(ly[0]), "v"(ly[1]), "v"(lyy[0]),
                  "v"(lyy[1]), "v"(lyy[2]), "v"(lyy[3]));
+    if constexpr (TWO)
+      asm volatile("" ::"v"(Wb[0]), "v"(Wb[1]), "v"(Wb[2]), "v"(Wb[3]), "v"(Wb[4]), "v"(Wb[5]),
+                   "v"(Wb[6]), "v"(G2b[0]), "v"(G2b[1]));
     store_pending();
     if (k > 0) load(k - 1);
 
     // ---- S = H [A B] (lane: row rho of S) and Q = [A B]' S + ... (lane: row rho of Q),
-    // column block by column block (a Q column needs only its S column) ----
-    breal S[18], Q[18], Q2[2], Qv1, Qv2;
+    // column block by column block (a Q column needs only its S column).  Slots of a row:
+    // its NH columns of x (one row: 0..13; two rows: the row's half of them), then 14..17 ----
+    breal S[NSQ], Q[NSQ], Q2[2], Qv1, Qv2;
+    if constexpr (TWO) {
 #pragma unroll
-    for (int c = 0; c < 7; ++c) S[c] = H[c];
+      for (int s = 0; s < 7; ++s) S[s] = coefS * H[s];
+    } else {
 #pragma unroll
-    for (int c = 7; c < 14; ++c) S[c] = dt * H[c - 7];
+      for (int c = 0; c < 7; ++c) S[c] = H[c];
 #pragma unroll
-    for (int c = 14; c < 18; ++c) S[c] = breal(0.0);
+      for (int c = 7; c < 14; ++c) S[c] = dt * H[c - 7];
+    }
+#pragma unroll
+    for (int c = NH; c < NSQ; ++c) S[c] = breal(0.0);
     breal cc[2] = {0, 0}, cc2[2] = {0, 0};
     if (STANCE) {
       // C' lyy C etc.: cc[z] = sum_y G2[y][rho] lyy[y][z], then Q[.][d] += sum_z cc[z] G2[z][d]
@@ -583,56 +652,77 @@ __device__ int sweep_wb(const SolveParams& sp, const DevBufs& d, const Layout& L
         cc2[z] = G22[0] * lyy[z] + G22[1] * lyy[2 + z];
       }
     }
-    // column blocks 0..5, 6..11, 12..17: S block, then the Q block it feeds
-    wb_s_a(S[0], S[1], S[2], S[3], S[4], S[5], W1, W2, H + 7);
+    // S block, then the Q block it feeds; the first block is columns / slots 0..5 in both layouts
+    wb_s_a(S[0], S[1], S[2], S[3], S[4], S[5], Wb, W2, H + 7);
 #pragma unroll
     for (int c = 0; c < 6; ++c) Q[c] = coef * qperm(S[c]);
-    sb_odd7_6(Q[0], Q[1], Q[2], Q[3], Q[4], Q[5], S + 0, W1);
-    if (STANCE) wb_st_a(Q[0], Q[1], Q[2], Q[3], Q[4], Q[5], G2o, cc);
-    wb_s_b(S[6], S[7], S[8], S[9], S[10], S[11], W1, W2, H + 7);
+    sb_odd7_6(Q[0], Q[1], Q[2], Q[3], Q[4], Q[5], S + 0, Wo);
+    if (STANCE) wb_st_a(Q[0], Q[1], Q[2], Q[3], Q[4], Q[5], G2b, cc);
+    if constexpr (TWO) {
+      // slots 6..10: column 6 / 13 and the control columns 14..17
+      wb2_s_b(S[6], S[7], S[8], S[9], S[10], Wb, W2, H + 7);
 #pragma unroll
-    for (int c = 6; c < 12; ++c) Q[c] = coef * qperm(S[c]);
-    sb_odd7_6(Q[6], Q[7], Q[8], Q[9], Q[10], Q[11], S + 6, W1);
-    if (STANCE) wb_st_b(Q[6], Q[7], Q[8], Q[9], Q[10], Q[11], G2o, cc);
-    wb_s_c(S[12], S[13], S[14], S[15], S[16], S[17], W1, W2, H + 7);
+      for (int s = 6; s < 11; ++s) Q[s] = coef * qperm(S[s]);
+      Qv1 = __builtin_fma(coef, qperm(Gv), l1);
+      Q2[0] = breal(0.0);
+      Q2[1] = breal(0.0);
+      Qv2 = l2;
+      const breal sc[6] = {S[6], S[7], S[8], S[9], S[10], Gv};
+      sb_odd7_6(Q[6], Q[7], Q[8], Q[9], Q[10], Qv1, sc, Wo);
+      const breal s2[3] = {S[9], S[10], Gv};
+      sb_odd7_3(Q2[0], Q2[1], Qv2, s2, W2);
+      if (STANCE) wb2_st_b(Q[6], Q[7], Q[8], Q[9], Q[10], Q2[0], Q2[1], G2b, G22, cc, cc2);
+    } else {
+      // column blocks 6..11, 12..17
+      wb_s_b(S[6], S[7], S[8], S[9], S[10], S[11], Wo, W2, H + 7);
 #pragma unroll
-    for (int c = 12; c < 18; ++c) Q[c] = coef * qperm(S[c]);
-    Qv1 = __builtin_fma(coef, qperm(Gv), l1);
-    Q2[0] = breal(0.0);
-    Q2[1] = breal(0.0);
-    Qv2 = l2;
-    {
+      for (int c = 6; c < 12; ++c) Q[c] = coef * qperm(S[c]);
+      sb_odd7_6(Q[6], Q[7], Q[8], Q[9], Q[10], Q[11], S + 6, Wo);
+      if (STANCE) wb_st_b(Q[6], Q[7], Q[8], Q[9], Q[10], Q[11], G2o, cc);
+      wb_s_c(S[12], S[13], S[14], S[15], S[16], S[17], Wo, W2, H + 7);
+#pragma unroll
+      for (int c = 12; c < 18; ++c) Q[c] = coef * qperm(S[c]);
+      Qv1 = __builtin_fma(coef, qperm(Gv), l1);
+      Q2[0] = breal(0.0);
+      Q2[1] = breal(0.0);
+      Qv2 = l2;
       const breal sc[7] = {S[12], S[13], S[14], S[15], S[16], S[17], Gv};
-      sb_odd7_7(Q[12], Q[13], Q[14], Q[15], Q[16], Q[17], Qv1, sc, W1);
+      sb_odd7_7(Q[12], Q[13], Q[14], Q[15], Q[16], Q[17], Qv1, sc, Wo);
       // control rows 2, 3 (second set of lanes 14, 15): only their control columns
       const breal s2[3] = {S[16], S[17], Gv};
       sb_odd7_3(Q2[0], Q2[1], Qv2, s2, W2);
+      if (STANCE) wb_st_c(Q[12], Q[13], Q[14], Q[15], Q[16], Q[17], Q2[0], Q2[1], G2o, G22, cc, cc2);
     }
     if (STANCE) {
-      wb_st_c(Q[12], Q[13], Q[14], Q[15], Q[16], Q[17], Q2[0], Q2[1], G2o, G22, cc, cc2);
       Qv1 = (Qv1 + G2o[0] * ly[0]) + G2o[1] * ly[1];
       Qv2 = (Qv2 + G22[0] * ly[0]) + G22[1] * ly[1];
     }
 
-    // ---- Qxx transpose through LDS (symmetrisation, MHPC_CompoundTypes.h:134) ----
+    // ---- Qxx transpose through LDS (symmetrisation, MHPC_CompoundTypes.h:134): a row writes
+    // its row rho (two rows: each its half of it) and reads its columns' rows ----
+    if constexpr (TWO) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) rl.M[at(rho, j)] = Q[j];
+      for (int s = 0; s < 7; ++s) rl.M[at(rho, wo + s)] = Q[s];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) rl.M[at(rho, j)] = Q[j];
+    }
     // + 2 (lxx + reg) on the diagonal of the transposed copy: an LDS atomic add, in order with
     // this wave's other LDS operations, no round trip
-    atomicAdd(&rl.M[at(rho, rho)], dg2);
+    atomicAdd(&rl.M[at(rho, xl ? mcol(rho) : rho)], dg2);
     wave_lds_order();
-    breal T[14];
+    breal T[NH];
     {
-      lds_creal* tq = (lds_creal*)&rl.M[at(0, cr)];
+      lds_creal* tq = (lds_creal*)&rl.M[at(jr, cr)];
 #pragma unroll
-      for (int j = 0; j < 14; ++j) T[j] = lds_single(tq, at(j, 0));
+      for (int j = 0; j < NH; ++j) T[j] = lds_single(tq, at(j, 0));
     }
     wave_lds_order();
 
-    // ---- the control block on every lane ----
+    // ---- the control block on every lane (two rows: both alike) ----
     wk q[4][4], Qu[4];
-    q[0][0] = rbc<14>(Q[14]); q[0][1] = rbc<14>(Q[15]); q[0][2] = rbc<14>(Q[16]); q[0][3] = rbc<14>(Q[17]);
-    q[1][1] = rbc<15>(Q[15]); q[1][2] = rbc<15>(Q[16]); q[1][3] = rbc<15>(Q[17]);
+    q[0][0] = rbc<14>(Q[NH]); q[0][1] = rbc<14>(Q[NH + 1]); q[0][2] = rbc<14>(Q[NH + 2]); q[0][3] = rbc<14>(Q[NH + 3]);
+    q[1][1] = rbc<15>(Q[NH + 1]); q[1][2] = rbc<15>(Q[NH + 2]); q[1][3] = rbc<15>(Q[NH + 3]);
     q[2][2] = rbc<14>(Q2[0]); q[2][3] = rbc<14>(Q2[1]); q[3][3] = rbc<15>(Q2[1]);
     Qu[0] = rbc<14>(Qv1); Qu[1] = rbc<15>(Qv1); Qu[2] = rbc<14>(Qv2); Qu[3] = rbc<15>(Qv2);
     // luu + reg on the diagonal (Iuu * regularisation)
@@ -652,283 +742,37 @@ __device__ int sweep_wb(const SolveParams& sp, const DevBufs& d, const Layout& L
     // K = -Quu^-1 Qux: column rho on lane rho (Qux[m][rho] = Q[rho][14 + m], own)
     wk Qxu[4], K[4];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) Qxu[m] = wk(Q[14 + m]);
+    for (int m = 0; m < 4; ++m) Qxu[m] = wk(Q[NH + m]);
     F.neg_solve(Qxu, K);
     // G = Qx - Qux' Quu^-1 Qu
     wk Gn = wk(Qv1);
 #pragma unroll
     for (int a = 0; a < 4; ++a) Gn += K[a] * Qu[a];
     // H = sym(Qxx) - Qux' Quu^-1 Qux: H[rho][j] = Qs[j] + sum_a K[a] Qux[a][j]
-    wk Hn[14];
+    wk Hn[NH];
+    if constexpr (TWO) {
+      // H columns of the row: Qux[a][7 + s] lives on lane 2 s + 1; row B moves it to lane 2 s
+      wk QxuS[4];
 #pragma unroll
-    for (int j = 0; j < 14; ++j) Hn[j] = wk((Q[j] + T[j]) / 2);
-    wb_h_a(Hn[0], Hn[1], Hn[2], Hn[3], Hn[4], Hn[5], Hn[6], Qxu, K);
-    wb_h_b(Hn[7], Hn[8], Hn[9], Hn[10], Hn[11], Hn[12], Hn[13], Qxu, K);
+      for (int m = 0; m < 4; ++m) QxuS[m] = qshift_rowB(Qxu[m]);
 #pragma unroll
-    for (int j = 0; j < 14; ++j) H[j] = breal(Hn[j]);
+      for (int s = 0; s < 7; ++s) Hn[s] = wk((Q[s] + T[s]) / 2);
+      wb_h_a(Hn[0], Hn[1], Hn[2], Hn[3], Hn[4], Hn[5], Hn[6], QxuS, K);
+      // both rows get both halves
+#pragma unroll
+      for (int s = 0; s < 7; ++s) row_pair_swap(breal(Hn[s]), H[s], H[7 + s]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 14; ++j) Hn[j] = wk((Q[j] + T[j]) / 2);
+      wb_h_a(Hn[0], Hn[1], Hn[2], Hn[3], Hn[4], Hn[5], Hn[6], Qxu, K);
+      wb_h_b(Hn[7], Hn[8], Hn[9], Hn[10], Hn[11], Hn[12], Hn[13], Qxu, K);
+#pragma unroll
+      for (int j = 0; j < 14; ++j) H[j] = breal(Hn[j]);
+    }
     Gv = breal(Gn);
     // ---- outputs of knot k (only while the row's attempt is alive) ----
     const bool ok = gate && psd;
-    // outputs of knot k, stored at the top of the next knot (see store_pending)
-    pend.ok = ok;
-    pend.k = k;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      pend.K[a] = breal(K[a]);
-      pend.du[a] = breal(du[a]);
-    }
-    pend.G = breal(Gn);
-    if (ok) rc.dV += acc(dv);
-    rc.failed = rc.failed || (gate && !psd);
-    if (!any_go(rc)) break;
-  }
-  store_pending();
-  // value function of knot 0 back to LDS
-  __syncthreads();
-  if (xl) {
-#pragma unroll
-    for (int j = 0; j < 14; ++j) rl.M[at(rho, j)] = H[j];
-    rl.Gs[rho] = Gv;
-  }
-  __syncthreads();
-  return BWS_ITERS(it);
-}
-
-// ---------------------------------------------------------------------------------------
-// Whole-body phase, two rows per problem (sweep_wb2, the launch shape for batches that leave
-// SIMDs idle).  Both rows hold the value function (row rho(t) on lane t) and the control
-// columns 14..17; row A computes the configuration columns 0..6 of S and Q, row B the
-// velocity columns 7..13 in the same register slots.  Row B's broadcast copy of [A B] puts
-// column 7 + s on lane 2 s, so both rows run the same instruction stream with the same DPP
-// lane immediates (the S/Q blocks shrink from 18 + 1 to 11 + 1 columns per row).  The
-// transpose writes each row's half of Qxx to the shared LDS block; each row updates its seven
-// columns of H, and one v_permlane16_swap per word gives both rows the full rows of H.  Every
-// entry is computed with the one-row sweep's operations in the same order, so the two
-// layouts agree bit for bit (tests/test_gpu_variants.py).
-template <bool STANCE>
-__device__ int sweep_wb2(const SolveParams& sp, const DevBufs& d, const Layout& L, const CostParams& cw, const ProbState* st, RowLds& rl,
-                          RowCtx& rc, int p) {
-  using R = Rows<7>;
-  using wk = wreal;
-  const int t = rc.t, b = rc.b, rp = rc.rp;
-  const int N = L.N[p], ko = L.ko[p], mode = L.mode[p];
-  const breal dt = L.dt[p];
-  const int rho = R::rho(t);
-  const bool xl = t < 14;
-  const breal coef = xl ? ((t & 1) ? dt : breal(1.0)) : breal(0.0);
-  const breal coefS = rp ? dt : breal(1.0);  // S init: column s (row A) / 7 + s (row B)
-  // broadcast column of the lane: its own (row A, odd lanes, lanes 14 / 15) or, on row B's
-  // even lanes 2 s, the velocity column 7 + s
-  const int cb = (rp && xl && !(t & 1)) ? 7 + (t >> 1) : rho;
-  breal base[7], baseb[7];
-#pragma unroll
-  for (int r = 0; r < 7; ++r) {
-    base[r] = rho == 7 + r ? breal(1.0) : breal(0.0);
-    baseb[r] = cb == 7 + r ? breal(1.0) : breal(0.0);
-  }
-  const int xi = xl ? rho : 0;
-  const breal w2 = 2 * dt * cw.wQ[mode - 1][xi];
-  const breal rxc = xi == 1 ? rc.cm.height : xi == 2 ? breal(0.0)
-                   : (xi >= 3 && xi < 7) ? cQjointBias[xi - 3] : xi == 7 ? rc.cm.vel : breal(0.0);
-  // lxx + reg on the diagonal, added by the row that owns the diagonal's column
-  const bool own_diag = xl && ((rho < 7) == (rp == 0));
-  const breal dg2 = own_diag ? 2 * (w2 + rc.reg) : breal(0.0);
-  const real* pos = d.refpos + (size_t)b * sp.NK + ko;
-  constexpr int NR = STANCE ? 9 : 7;
-  constexpr int NCS = STANCE ? 14 : 8;
-  real pr1[NR], prb[NR], pr2[NR], pcv, pxn, ppos;  // record type, see sweep_wb
-  const int c2 = 16 + (t & 1);
-  const int cq = t < NCS ? t : 0;
-  // the phase's operand / output bases (knot 0): a knot adds k times its record stride
-  const real* tk0 = traj_ptr(sp, d, b, rc.nom, ko) + xi;
-  const real* jc0 = d.par + par_jac(sp.NK, b, ko) + cq;
-  const real* r10 = d.par + par_col(sp.NK, b, rho, ko);
-  const real* rb0 = d.par + par_col(sp.NK, b, cb, ko);
-  const real* r20 = d.par + par_col(sp.NK, b, c2, ko);
-  auto load = [&](int k) {
-    pxn = tk0[k * KS];
-    ppos = pos[k];
-    pcv = jc0[k * 14];
-    const real* r1 = r10 + k * 9;
-    const real* rb = rb0 + k * 9;
-    const real* r2 = r20 + k * 9;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) pr1[r] = r1[r];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) prb[r] = rb[r];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) pr2[r] = r2[r];
-  };
-  breal H[14], Gv;
-  {
-    const int hr = xl ? rho : 0;
-#pragma unroll
-    for (int j = 0; j < 14; ++j) H[j] = rl.M[at(hr, j)];
-    Gv = rl.Gs[hr];
-  }
-  // column read in the transpose; lanes 14, 15 (no row of Qxx) read column 0 with lane 0 (a
-  // broadcast): columns 14, 15 are never written in this layout, and a filler lane's H row
-  // still enters 0 * x products, so it must stay finite
-  // row-major layout: matrix column c at LDS column mcol(c) (row B's half 16-byte aligned)
-  auto mcol = [](int c) { return MHPC_LDS_COLMAJOR ? c : (c < 7 ? c : c + 1); };
-  const int cr = xl ? mcol(rho) : 0;
-  const int wo = rp ? mcol(7) : 0;      // LDS column of the row's first Q slot
-  const int jr = rp ? 7 : 0;            // first matrix row of the row's H columns
-  PendingKnot pend;
-  pend.ok = false;
-  const size_t rec0 = (size_t)b * sp.NK + ko;
-  real* const K0 = d.K + rec0 * 56 + rho;
-  real* const G0 = d.G + rec0 * 14 + rho;
-  real* const du0 = d.du + rec0 * 4;
-  auto store_pending = [&]() {
-    if (pend.ok) {
-      if (xl) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) K0[pend.k * 56 + a * 14] = pend.K[a];
-        G0[pend.k * 14] = pend.G;
-      } else if (t == 14) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) du0[pend.k * 4 + a] = pend.du[a];
-      }
-    }
-    pend.ok = false;
-  };
-  if (N >= 2) load(N - 2);
-  int it = 0;  // knot iterations the wave ran (the cycle accounting's knot count)
-  for (int k = N - 2; k >= 0; --k) {
-    ++it;
-    breal Wo[7], Wb[7], W2[7], G2o[2], G2b[2], G22[2];
-#pragma unroll
-    for (int r = 0; r < 7; ++r) {
-      Wo[r] = __builtin_fma(breal(pr1[r]), dt, base[r]);
-      Wb[r] = __builtin_fma(breal(prb[r]), dt, baseb[r]);
-      W2[r] = __builtin_fma(breal(pr2[r]), dt, breal(0.0));
-    }
-    G2o[0] = G2o[1] = G2b[0] = G2b[1] = G22[0] = G22[1] = breal(0.0);
-    if (STANCE) {  // fresh values (see sweep_wb)
-      asm volatile("" : "=v"(G2o[0]) : "0"(breal(pr1[NR - 2])));
-      asm volatile("" : "=v"(G2o[1]) : "0"(breal(pr1[NR - 1])));
-      asm volatile("" : "=v"(G2b[0]) : "0"(breal(prb[NR - 2])));
-      asm volatile("" : "=v"(G2b[1]) : "0"(breal(prb[NR - 1])));
-      asm volatile("" : "=v"(G22[0]) : "0"(breal(pr2[NR - 2])));
-      asm volatile("" : "=v"(G22[1]) : "0"(breal(pr2[NR - 1])));
-    }
-    breal luu[4], ly[2] = {0, 0}, lyy[4] = {0, 0, 0, 0};
-    const breal pcvd = pcv;
-    const breal lu0 = rbc<0>(pcvd), lu1 = rbc<1>(pcvd), lu2 = rbc<2>(pcvd), lu3 = rbc<3>(pcvd);
-    luu[0] = rbc<4>(pcvd); luu[1] = rbc<5>(pcvd); luu[2] = rbc<6>(pcvd); luu[3] = rbc<7>(pcvd);
-    if (STANCE) {
-      ly[0] = rbc<8>(pcvd); ly[1] = rbc<9>(pcvd);
-      lyy[0] = rbc<10>(pcvd); lyy[1] = rbc<11>(pcvd); lyy[2] = rbc<12>(pcvd); lyy[3] = rbc<13>(pcvd);
-    }
-    const breal rxi = rho == 0 ? breal(ppos) : rxc;
-    const breal lx = w2 * (breal(pxn) - rxi);
-    const breal lu01 = (t & 1) ? lu1 : lu0;
-    const breal l1 = xl ? lx : lu01;
-    const breal l2 = (t & 1) ? lu3 : lu2;
-    const bool gate = go(rc);
-    rc.kn += gate ? 1 : 0;
-    rc.kn_wb += gate ? 1 : 0;
-    asm volatile("" ::"v"(Wo[0]), "v"(Wo[1]), "v"(Wo[2]), "v"(Wo[3]), "v"(Wo[4]), "v"(Wo[5]),
-                 "v"(Wo[6]), "v"(Wb[0]), "v"(Wb[1]), "v"(Wb[2]), "v"(Wb[3]), "v"(Wb[4]),
-                 "v"(Wb[5]), "v"(Wb[6]), "v"(l1), "v"(l2));
-    asm volatile("" ::"v"(W2[0]), "v"(W2[1]), "v"(W2[2]), "v"(W2[3]), "v"(W2[4]), "v"(W2[5]),
-                 "v"(W2[6]), "v"(G2o[0]), "v"(G2o[1]), "v"(G2b[0]), "v"(G2b[1]), "v"(G22[0]),
-                 "v"(G22[1]));
-    asm volatile("" ::"v"(luu[0]), "v"(luu[1]), "v"(luu[2]), "v"(luu[3]), "v"(ly[0]), "v"(ly[1]),
-                 "v"(lyy[0]), "v"(lyy[1]), "v"(lyy[2]), "v"(lyy[3]));
-    store_pending();
-    if (k > 0) load(k - 1);
-
-    // ---- S and Q, slots 0..6 (the row's half of columns 0..13) and 7..10 (columns 14..17)
-    breal S[11], Q[11], Q2[2], Qv1, Qv2;
-#pragma unroll
-    for (int s = 0; s < 7; ++s) S[s] = coefS * H[s];
-#pragma unroll
-    for (int s = 7; s < 11; ++s) S[s] = breal(0.0);
-    breal cc[2] = {0, 0}, cc2[2] = {0, 0};
-    if (STANCE) {
-#pragma unroll
-      for (int z = 0; z < 2; ++z) {
-        cc[z] = G2o[0] * lyy[z] + G2o[1] * lyy[2 + z];
-        cc2[z] = G22[0] * lyy[z] + G22[1] * lyy[2 + z];
-      }
-    }
-    wb_s_a(S[0], S[1], S[2], S[3], S[4], S[5], Wb, W2, H + 7);
-#pragma unroll
-    for (int s = 0; s < 6; ++s) Q[s] = coef * qperm(S[s]);
-    sb_odd7_6(Q[0], Q[1], Q[2], Q[3], Q[4], Q[5], S + 0, Wo);
-    if (STANCE) wb_st_a(Q[0], Q[1], Q[2], Q[3], Q[4], Q[5], G2b, cc);
-    wb2_s_b(S[6], S[7], S[8], S[9], S[10], Wb, W2, H + 7);
-#pragma unroll
-    for (int s = 6; s < 11; ++s) Q[s] = coef * qperm(S[s]);
-    Qv1 = __builtin_fma(coef, qperm(Gv), l1);
-    Q2[0] = breal(0.0);
-    Q2[1] = breal(0.0);
-    Qv2 = l2;
-    {
-      const breal sc[6] = {S[6], S[7], S[8], S[9], S[10], Gv};
-      sb_odd7_6(Q[6], Q[7], Q[8], Q[9], Q[10], Qv1, sc, Wo);
-      const breal s2[3] = {S[9], S[10], Gv};
-      sb_odd7_3(Q2[0], Q2[1], Qv2, s2, W2);
-    }
-    if (STANCE) {
-      wb2_st_b(Q[6], Q[7], Q[8], Q[9], Q[10], Q2[0], Q2[1], G2b, G22, cc, cc2);
-      Qv1 = (Qv1 + G2o[0] * ly[0]) + G2o[1] * ly[1];
-      Qv2 = (Qv2 + G22[0] * ly[0]) + G22[1] * ly[1];
-    }
-
-    // ---- Qxx transpose: each row writes its half of the row rho ----
-#pragma unroll
-    for (int s = 0; s < 7; ++s) rl.M[at(rho, wo + s)] = Q[s];
-    atomicAdd(&rl.M[at(rho, xl ? mcol(rho) : rho)], dg2);
-    wave_lds_order();
-    breal T[7];
-    {
-      lds_creal* tq = (lds_creal*)&rl.M[at(jr, cr)];
-#pragma unroll
-      for (int s = 0; s < 7; ++s) T[s] = lds_single(tq, at(s, 0));
-    }
-    wave_lds_order();
-
-    // ---- the control block on every lane (both rows alike) ----
-    wk q[4][4], Qu[4];
-    q[0][0] = rbc<14>(Q[7]); q[0][1] = rbc<14>(Q[8]); q[0][2] = rbc<14>(Q[9]); q[0][3] = rbc<14>(Q[10]);
-    q[1][1] = rbc<15>(Q[8]); q[1][2] = rbc<15>(Q[9]); q[1][3] = rbc<15>(Q[10]);
-    q[2][2] = rbc<14>(Q2[0]); q[2][3] = rbc<14>(Q2[1]); q[3][3] = rbc<15>(Q2[1]);
-    Qu[0] = rbc<14>(Qv1); Qu[1] = rbc<15>(Qv1); Qu[2] = rbc<14>(Qv2); Qu[3] = rbc<15>(Qv2);
-#pragma unroll
-    for (int a = 0; a < 4; ++a) q[a][a] = q[a][a] + wk(luu[a] + rc.reg);
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int c = 0; c < a; ++c) q[a][c] = q[c][a];
-    bool psd;
-    const Ldl4<wk> F = control_factor<wk>(q, sp.eps9, t, psd);
-    wk du[4], dv = wk(0.0);
-    F.neg_solve(Qu, du);
-#pragma unroll
-    for (int a = 0; a < 4; ++a) dv += Qu[a] * du[a];
-    wk Qxu[4], K[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) Qxu[m] = wk(Q[7 + m]);
-    F.neg_solve(Qxu, K);
-    wk Gn = wk(Qv1);
-#pragma unroll
-    for (int a = 0; a < 4; ++a) Gn += K[a] * Qu[a];
-    // H columns of the row: Qux[a][7 + s] lives on lane 2 s + 1; row B moves it to lane 2 s
-    wk QxuS[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) QxuS[m] = qshift_rowB(Qxu[m]);
-    wk Hn[7];
-#pragma unroll
-    for (int s = 0; s < 7; ++s) Hn[s] = wk((Q[s] + T[s]) / 2);
-    wb_h_a(Hn[0], Hn[1], Hn[2], Hn[3], Hn[4], Hn[5], Hn[6], QxuS, K);
-    // both rows get both halves
-#pragma unroll
-    for (int s = 0; s < 7; ++s) row_pair_swap(breal(Hn[s]), H[s], H[7 + s]);
-    Gv = breal(Gn);
-    const bool ok = gate && psd;
+    // outputs of knot k, stored at the top of the next knot (see store_pending) by row A
     pend.ok = ok && rp == 0;
     pend.k = k;
 #pragma unroll
@@ -942,6 +786,7 @@ __device__ int sweep_wb2(const SolveParams& sp, const DevBufs& d, const Layout& 
     if (!any_go(rc)) break;
   }
   store_pending();
+  // value function of knot 0 back to LDS
   __syncthreads();
   if (xl && rp == 0) {
 #pragma unroll
@@ -1096,19 +941,7 @@ __device__ int sweep_srb(const SolveParams& sp, const DevBufs& d, const Layout& 
   real* const K0 = d.K + rec0 * 56 + rho;
   real* const G0 = d.G + rec0 * 14 + rho;
   real* const du0 = d.du + rec0 * 4;
-  auto store_pending = [&]() {
-    if (pend.ok) {
-      if (xl) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) K0[pend.k * 56 + a * 6] = pend.K[a];
-        G0[pend.k * 14] = pend.G;
-      } else if (t == 6) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) du0[pend.k * 4 + a] = pend.du[a];
-      }
-    }
-    pend.ok = false;
-  };
+  auto store_pending = [&]() { pend.store<6>(xl, t == 6, K0, G0, du0); };
   Ops oa, ob;
 #ifdef MHPC_BWS_TIMING
   unsigned long long segacc[5] = {0, 0, 0, 0, 0};
@@ -1371,7 +1204,8 @@ __device__ void impact_step(const SolveParams& sp, const DevBufs& d, const Layou
 // rc.dV the matching dVnext.
 // WB_CODE = false: SRB phases only (the SRB half of a split sweep), no whole-body code in the
 // kernel (its register allocation is the SRB knot's, so a partials wave fits beside it).
-// RPP: rows per problem (2: the whole-body phases run sweep_wb2, SRB phases on both rows).
+// RPP: rows per problem (2: the whole-body phases run sweep_wb's two-row layout, SRB phases on
+// both rows).
 template <bool WB_CODE, int RPP>
 __device__ void sweep_phases(const SolveParams& sp, const DevBufs& d, const Layout& L, const CostParams& cw, ProbState* st, RowLds& rl,
                              RowCtx& rc, int p_hi, int p_lo) {
@@ -1394,13 +1228,8 @@ __device__ void sweep_phases(const SolveParams& sp, const DevBufs& d, const Layo
         BWS_T(tw0);
         const int mode = L.mode[p];
         int nit;
-        if (RPP == 2) {
-          if (mode == 1 || mode == 3) nit = sweep_wb2<true>(sp, d, L, cw, st, rl, rc, p);
-          else nit = sweep_wb2<false>(sp, d, L, cw, st, rl, rc, p);
-        } else {
-          if (mode == 1 || mode == 3) nit = sweep_wb<true>(sp, d, L, cw, st, rl, rc, p);
-          else nit = sweep_wb<false>(sp, d, L, cw, st, rl, rc, p);
-        }
+        if (mode == 1 || mode == 3) nit = sweep_wb<true, RPP>(sp, d, L, cw, st, rl, rc, p);
+        else nit = sweep_wb<false, RPP>(sp, d, L, cw, st, rl, rc, p);
         BWS_ADD(0, clock64() - tw0);
         BWS_ADD(1, nit);
         (void)nit;
@@ -1439,7 +1268,7 @@ __device__ void zero_value(RowLds& rl, RowCtx& rc) {
 #endif
 
 // RPW problems per wave, RPP rows per problem (rows 0..RPW*RPP-1 of the wave; the others
-// idle).  RPP = 2 (RPW = 2): problem q on rows 2q, 2q+1 sharing one RowLds (sweep_wb2).
+// idle).  RPP = 2 (RPW = 2): problem q on rows 2q, 2q+1 sharing one RowLds (sweep_wb).
 //
 // PART 0: the whole sweep with its regularisation retries (MultiPhaseDDP.cpp:196-241).
 // PART 1: the SRB phases of the attempts until one passes them (an attempt that fails there
@@ -1603,28 +1432,28 @@ int bws_auto_variant(int B) {
   return B <= MHPC_BWS_PAIRS_MAX_B ? MHPC_VARIANT_BWS_PAIRS2 : MHPC_VARIANT_BWS_ROWS4;
 }
 
+template <int RPW, int PART, int RPP>
+static void launch_k_bws(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter, hipStream_t s) {
+  hipLaunchKernelGGL((k_bws<RPW, PART, RPP>), dim3(bws_grid(sp, RPW)), dim3(64), 0, s, sp, d, al_iter, ddp_iter);
+}
+// The launch of one part for RPW problems per wave on RPP rows each.  The SRB half always has
+// one row per problem; beside the two-row layout it runs four problems per wave (its knot is
+// short).
+template <int RPW, int RPP>
+static void launch_bws_part(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter, int part,
+                            hipStream_t s) {
+  if (part == 1) launch_k_bws<RPP == 2 ? 4 : RPW, 1, 1>(sp, d, al_iter, ddp_iter, s);
+  else if (part == 2) launch_k_bws<RPW, 2, RPP>(sp, d, al_iter, ddp_iter, s);
+  else launch_k_bws<RPW, 0, RPP>(sp, d, al_iter, ddp_iter, s);
+}
 hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter, int part,
                       hipStream_t s) {
-  const int v = sp.var_bws ? sp.var_bws : bws_auto_variant(launch_problems(sp));
-  const int rpw = v == MHPC_VARIANT_BWS_ROWS1 ? 1 : (v == MHPC_VARIANT_BWS_ROWS2 ||
-                                                     v == MHPC_VARIANT_BWS_PAIRS2) ? 2 : 4;
-  const dim3 grid(bws_grid(sp, rpw));
-  const dim3 grid4(bws_grid(sp, 4));
-#define MHPC_LAUNCH_BWS(R)                                                                    \
-  do {                                                                                        \
-    if (part == 1) hipLaunchKernelGGL((k_bws<R, 1, 1>), grid, dim3(64), 0, s, sp, d, al_iter, ddp_iter); \
-    else if (part == 2) hipLaunchKernelGGL((k_bws<R, 2, 1>), grid, dim3(64), 0, s, sp, d, al_iter, ddp_iter); \
-    else hipLaunchKernelGGL((k_bws<R, 0, 1>), grid, dim3(64), 0, s, sp, d, al_iter, ddp_iter);           \
-  } while (0)
-  if (v == MHPC_VARIANT_BWS_PAIRS2) {
-    // the SRB half keeps one row per problem (its knot is short; four problems per wave)
-    if (part == 1) hipLaunchKernelGGL((k_bws<4, 1, 1>), grid4, dim3(64), 0, s, sp, d, al_iter, ddp_iter);
-    else if (part == 2) hipLaunchKernelGGL((k_bws<2, 2, 2>), grid, dim3(64), 0, s, sp, d, al_iter, ddp_iter);
-    else hipLaunchKernelGGL((k_bws<2, 0, 2>), grid, dim3(64), 0, s, sp, d, al_iter, ddp_iter);
-  } else if (rpw == 1) MHPC_LAUNCH_BWS(1);
-  else if (rpw == 2) MHPC_LAUNCH_BWS(2);
-  else MHPC_LAUNCH_BWS(4);
-#undef MHPC_LAUNCH_BWS
+  switch (sp.var_bws ? sp.var_bws : bws_auto_variant(launch_problems(sp))) {
+    case MHPC_VARIANT_BWS_PAIRS2: launch_bws_part<2, 2>(sp, d, al_iter, ddp_iter, part, s); break;
+    case MHPC_VARIANT_BWS_ROWS1: launch_bws_part<1, 1>(sp, d, al_iter, ddp_iter, part, s); break;
+    case MHPC_VARIANT_BWS_ROWS2: launch_bws_part<2, 1>(sp, d, al_iter, ddp_iter, part, s); break;
+    default: launch_bws_part<4, 1>(sp, d, al_iter, ddp_iter, part, s); break;
+  }
   return hipGetLastError();
 }
 
@@ -1649,15 +1478,22 @@ hipError_t launch_eval_recip(int n, const breal* a, breal* out, hipStream_t s) {
 #endif
 }  // namespace MHPC_NS
 
-#ifdef MHPC_BWS_TIMING
+// The timing build's reader: one per library, from the default fp64 object (whose counters it
+// reads; the other objects of a timing build count into their own g_bws_cyc, unread).
+#if defined(MHPC_BWS_TIMING) && !defined(MHPC_FP32)
+#ifdef MHPC_BWS_VARIANT_NS
+#define MHPC_BWS_CYC MHPC_NS::MHPC_BWS_VARIANT_NS::g_bws_cyc
+#else
+#define MHPC_BWS_CYC MHPC_NS::g_bws_cyc
+#endif
 extern "C" int mhpc_dbg_bws_cycles(unsigned long long* out, int reset) {
   if (hipDeviceSynchronize() != hipSuccess) return 1;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(MHPC_NS::g_bws_cyc), sizeof(unsigned long long) * 16) !=
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(MHPC_BWS_CYC), sizeof(unsigned long long) * 16) !=
       hipSuccess)
     return 1;
   if (reset) {
     unsigned long long z[16] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(MHPC_NS::g_bws_cyc), z, sizeof(z)) != hipSuccess) return 1;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(MHPC_BWS_CYC), z, sizeof(z)) != hipSuccess) return 1;
   }
   return 0;
 }

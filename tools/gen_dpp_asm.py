@@ -144,7 +144,7 @@ def blocks():
     for c in (7, 8):
         B.append(lane_block(f"sb_even7_{c}", even7, c, ["s", "m"],
                             f"acc a += sum_r bcast(s[a], 2r) * m[r], r < 7, {c} accumulators"))
-    # ---- whole body, two rows per problem (sweep_wb2): row A holds the configuration
+    # ---- whole body, two rows per problem (sweep_wb<., 2>): row A holds the configuration
     # columns 0..6, row B the velocity columns 7..13 in the same slots (its broadcast set puts
     # column 7 + s on lane 2 s), both the control columns 14..17 ----
     terms = []
