@@ -1048,69 +1048,6 @@ __global__ void k_cost_grad(SolveParams sp, DevBufs d, int g, int p, int b0, int
 }
 
 // ============================================================================================
-// Phase buffers of the receding-horizon loop (MHPCLocomotion::update_problem,
-// MHPCLocomotion.cpp:107-158): the reference keeps one N_TIMESTEPS_MAX-knot buffer per WB
-// and per SRB phase slot (nominal x,u,y and cost-to-go) and rotates which buffer each phase
-// uses.  store [B][spmax][nbk][SREC]: x,u,y (a traj record), K 56, du 4, G 14.  Phase p of a
-// problem's layout lives in its buffer L.buf[p]; k_store_save runs with the layouts before
-// an update, k_store_load with those after it.
-// ============================================================================================
-constexpr int SREC = kStoreRec;
-
-__global__ void k_store_save(SolveParams sp, DevBufs d, real* store, int nbk, int spmax) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (long)sp.B * sp.NK) return;
-  const int b = (int)(t / sp.NK), kk = (int)(t - (long)b * sp.NK);
-  const Layout& L = d.grp[d.lid[b]].lay;  // the problem's layout (per lane: not a hot kernel)
-  if (kk >= L.NK) return;
-  int p = 0;
-  while (p + 1 < L.P && kk >= L.ko[p + 1]) ++p;
-  const int k = kk - L.ko[p];
-  real* o = store + (((size_t)b * spmax + L.buf[p]) * nbk + k) * SREC;
-  const real* r = traj_ptr(sp, d, b, d.st[b].nom_slot, kk);
-  for (int i = 0; i < KS; ++i) o[i] = r[i];
-  const size_t rec = (size_t)b * sp.NK + kk;
-  for (int i = 0; i < 56; ++i) o[KS + i] = d.K[rec * 56 + i];
-  for (int i = 0; i < 4; ++i) o[KS + 56 + i] = d.du[rec * 4 + i];
-  for (int i = 0; i < 14; ++i) o[KS + 60 + i] = d.G[rec * 14 + i];
-}
-
-__global__ void k_store_load(SolveParams sp, DevBufs d, const real* store, int nbk, int spmax) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (long)sp.B * sp.NK) return;
-  const int b = (int)(t / sp.NK), kk = (int)(t - (long)b * sp.NK);
-  const Layout& L = d.grp[d.lid[b]].lay;  // the problem's layout (per lane: not a hot kernel)
-  if (kk >= L.NK) return;
-  int p = 0;
-  while (p + 1 < L.P && kk >= L.ko[p + 1]) ++p;
-  const int k = kk - L.ko[p];
-  const real* o = store + (((size_t)b * spmax + L.buf[p]) * nbk + k) * SREC;
-  real* r = traj_ptr(sp, d, b, 0, kk);  // k_init(warm = 0) sets nom_slot = 0
-  for (int i = 0; i < KS; ++i) r[i] = o[i];
-  if (k == L.N[p] - 1)  // u, y of the last knot are never rewritten by a sweep (B11): the
-    for (int sl = 1; sl < sp.nslot; ++sl) {  // buffer's stale tail must follow any trial
-      real* q = traj_ptr(sp, d, b, sl, kk);
-      for (int i = 0; i < KS; ++i) q[i] = o[i];
-    }
-  const size_t rec = (size_t)b * sp.NK + kk;
-  for (int i = 0; i < 56; ++i) d.K[rec * 56 + i] = o[KS + i];
-  for (int i = 0; i < 4; ++i) d.du[rec * 4 + i] = o[KS + 56 + i];
-  for (int i = 0; i < 14; ++i) d.G[rec * 14 + i] = o[KS + 60 + i];
-}
-
-hipError_t launch_store(const SolveParams& sp, const DevBufs& d, real* store, int nbk, int spmax,
-                        int save, hipStream_t s) {
-  const long n = (long)sp.B * sp.NK;
-  if (save)
-    hipLaunchKernelGGL(k_store_save, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, sp, d,
-                       store, nbk, spmax);
-  else
-    hipLaunchKernelGGL(k_store_load, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, sp, d,
-                       store, nbk, spmax);
-  return hipGetLastError();
-}
-
-// ============================================================================================
 // k_partials: forward_sweep_partials_only (SinglePhase.cpp:147-180) -- the dynamics
 // Jacobians of every WB knot of the nominal, by implicit differentiation of the contact KKT
 // system at the knot's solution (mhpc_model.h, WbKnot): the lane solves the knot's forward
@@ -1289,295 +1226,6 @@ __global__ void k_al_end(SolveParams sp, DevBufs d, int al, int last) {
 }
 
 // ============================================================================================
-// initialization: references, state, PD warm start (MHPCLocomotion.cpp:47-53,200-215)
-// ============================================================================================
-// warm = 0 (mhpc_update_problem): references and per-problem state only -- the reference's
-// update_problem() regenerates the references and re-initialises the AL / ReB parameters of
-// every phase but keeps the (rotated) nominal trajectories and gains as the warm start.
-// References (ReferenceGen.h:94-109) and the per-problem solver state of one problem;
-// warm = 1 also resets the option fields a solve rewrites (see ProbState).
-// AL_REB_PARAMETER of phase p's mode (MHPCConstraints.cpp:43-88, mhpc_set_constraint_params)
-static __device__ __forceinline__ void init_al_reb(ProbState* st, const Layout& L,
-                                                   const CostParams& cw, int p) {
-  const bool wb = p < L.n_wb && p < L.P;
-  const int m = p < L.P ? L.mode[p] - 1 : 0;
-  st->sigma[p] = (wb && ntc_of(L.mode[p], true)) ? cw.sigma0[m] : real(0.0);
-  st->delta[p] = cw.delta0[m];
-  st->eps_tq[p] = cw.eps_tq0[m];
-  st->eps_grf[p] = cw.eps_grf0[m];
-}
-__device__ void k_init_state(const SolveParams& sp, const DevBufs& d, const Layout& L, int b,
-                             int warm) {
-  const real* x0 = d.x0 + (size_t)b * 14;
-  real* pos = d.refpos + (size_t)b * sp.NK;
-  const real vel = cmd_of(d, b).vel;
-  for (int p = 0; p < L.P; ++p) {
-    const int ko = L.ko[p];
-    pos[ko] = p == 0 ? x0[0] : pos[L.ko[p - 1] + L.N[p - 1] - 1];
-    for (int k = 1; k < L.N[p]; ++k) pos[ko + k] = pos[ko + k - 1] + vel * L.dt[p];
-  }
-  ProbState* st = &d.st[b];
-  st->J = 0; st->viol = 0; st->dV_exp = 0; st->reg = 0; st->cost_prev = 0;
-  for (int p = 0; p < MAXP; ++p) {
-    st->V[p] = 0; st->dV[p] = 0; st->h[p] = 0; st->lambda[p] = 0;
-    init_al_reb(st, L, sp.cw, p);  // (problem 0's set: see k_init_params)
-  }
-  st->status = MHPC_SOLVE_OK;
-  // ReB flag as the options set it (what a sweep right after initialization() sees); the
-  // first forward_sweep(0) applies the per-AL-iteration rule (MultiPhaseDDP.cpp:178-183)
-  st->active = 1; st->ddp_active = 0; st->reb_active = sp.ReB_active ? 1 : 0; st->al_partials = 0;
-  st->nom_slot = 0; st->al_iter = 0; st->ddp_iter = 0; st->bws_iter = 0; st->ntrace = 0;
-  for (int i = 0; i < TRACE; ++i) st->trace[i] = -1;
-  for (int i = 0; i < NCNT; ++i) st->cnt[i] = 0;
-  st->par_slot = 0;
-  st->par_al = 0;
-  st->ls_nt = 0;
-  st->ls_nom = 0;
-  st->reroll_j = -1;
-  st->reroll_nom = 0;
-  st->reroll_eps = real(0.0);
-  for (int p = 0; p < MAXP; ++p) {
-    st->par_sigma[p] = 0; st->par_lambda[p] = 0; st->ls_sigma[p] = 0; st->ls_lambda[p] = 0;
-  }
-  if (!warm) return;
-  st->opt_reb = sp.ReB_active ? 1 : 0;
-  st->opt_pen = sp.update_penalty;
-  st->cap_reb = st->opt_reb;
-  st->cap_pen = st->opt_pen;
-}
-
-// A lane pair per problem (even lane: front leg, odd: back leg of the pair dynamics,
-// mhpc_model_pair.h): the warm-start rollout is one serial chain per problem, so halving its
-// per-knot latency is what counts; both lanes carry the same state and controls (the pair
-// model returns xdot and y on both, bit for bit the single-lane model's), the even lane
-// writes the references and the per-problem state, each lane half of every knot record.
-// memory_reset (MHPCLocomotion.cpp:265-288), launched on the second stream beside k_init and
-// hidden behind its serial warm-start chains: K, du and G of every knot, and u and y of
-// every phase's last knot in every trajectory slot (no rollout writes them, quirk B11; a slot
-// becoming the nominal carries them into the exports).  Everything else of traj is written
-// before it is read (slot 0 by k_init, the candidate slots by the line search), so initialize
-// does not clear the whole array (2.8 GB at batch 4096).  k_init reads none of these arrays
-// and writes other elements of the tail records.
-__device__ void init_reset_arrays(const SolveParams& sp, const DevBufs& d, long t, long nt) {
-  const long nk = (long)sp.B * sp.NK;
-  for (long i = t; i < nk * 56; i += nt) d.K[i] = real(0.0);
-  for (long i = t; i < nk * 4; i += nt) d.du[i] = real(0.0);
-  for (long i = t; i < nk * 14; i += nt) d.G[i] = real(0.0);
-  const long n = (long)sp.B * sp.nslot * sp.pmax;
-  for (long i = t; i < n; i += nt) {
-    const int p = (int)(i % sp.pmax);
-    const long bs = i / sp.pmax;
-    const int slot = (int)(bs % sp.nslot), b = (int)(bs / sp.nslot);
-    const Layout& L = d.grp[d.lid[b]].lay;  // the problem's layout (per lane; hidden beside k_init)
-    if (p >= L.P) continue;
-    const int nx = p < L.n_wb ? 14 : 6;
-    real* r = traj_ptr(sp, d, b, slot, L.ko[p] + L.N[p] - 1);
-    for (int e = nx; e < KS; ++e) r[e] = real(0.0);
-  }
-}
-
-__global__ __launch_bounds__(256) void k_reset_arrays(SolveParams sp, DevBufs d) {
-  init_reset_arrays(sp, d, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256);
-}
-
-// ---- per-problem re-initialisation (mhpc_reset_problems): list-driven, work ~ n not B ----------
-// The padded x0 rows [n][14] of the listed problems to their device rows.
-__global__ __launch_bounds__(64) void k_scatter_x0(DevBufs d, int n, const int* list,
-                                                   const real* rows) {
-  const int t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= n * 14) return;
-  d.x0[(size_t)list[t / 14] * 14 + t % 14] = rows[t];
-}
-
-// memory_reset of the listed problems: what k_reset_arrays does for the batch (K, du, G over the
-// whole knot stride; u, y of every phase's last knot in every slot, by the problem's current
-// layout) and, when the phase-buffer store exists, their store rows (ensure_store's memset for
-// one problem).  A block per (listed problem, chunk of RL_CH items): item t is knot t of the
-// stride and record t of the problem's spmax * nbk store records (spmax = 0 without a store;
-// nch = chunks per problem over the longer of the two).  A chunk's K, du, G and store records are
-// contiguous, so the block's lanes stride over their elements (whole lines per wave).
-constexpr int RL_CH = 64;
-__global__ __launch_bounds__(256) void k_reset_list(SolveParams sp, DevBufs d, const int* list,
-                                                    int nch, real* store, int nbk, int spmax) {
-  const int b = list[blockIdx.x / nch], i0 = (int)(blockIdx.x % nch) * RL_CH, t = threadIdx.x;
-  const int k1 = min(i0 + RL_CH, sp.NK);
-  if (i0 < k1) {
-    const size_t r0 = (size_t)b * sp.NK + i0;
-    const int nk = k1 - i0;
-    for (int e = t; e < nk * 56; e += 256) d.K[r0 * 56 + e] = real(0.0);
-    for (int e = t; e < nk * 4; e += 256) d.du[r0 * 4 + e] = real(0.0);
-    for (int e = t; e < nk * 14; e += 256) d.G[r0 * 14 + e] = real(0.0);
-    const Layout& L = d.grp[d.lid[b]].lay;
-    for (int e = t; e < L.P * sp.nslot; e += 256) {  // a lane per (phase, slot) tail
-      const int p = e / sp.nslot, slot = e % sp.nslot;
-      const int kk = L.ko[p] + L.N[p] - 1;
-      if (kk < i0 || kk >= k1) continue;
-      real* r = traj_ptr(sp, d, b, slot, kk);
-      for (int q = p < L.n_wb ? 14 : 6; q < KS; ++q) r[q] = real(0.0);
-    }
-  }
-  const int s1 = min(i0 + RL_CH, spmax * nbk);
-  if (i0 < s1) {
-    real* o = store + ((size_t)b * spmax * nbk + i0) * SREC;
-    for (int e = t; e < (s1 - i0) * SREC; e += 256) o[e] = real(0.0);
-  }
-}
-
-// The AL / ReB initial values of every problem from its group's parameter record, after k_init
-// (which wrote problem 0's set for all): launched only when the handle holds more than one set
-// (mhpc_set_param_sets).  k_init keeps its own read of the parameter block, SolveParams::cw:
-// with that read gone or moved to the table the fp32 build's SLP vectoriser packs the
-// warm-start rollout below differently, three of its multiply-adds no longer contract, and
-// every fp32 result changes in the last bits (k_init has no MHPC_NO_FMA_F32: its rounding is
-// part of the fp32 results as they stand).
-// The same holds for the option fields k_init_state writes (the ReB flag; warm: the fields a
-// solve rewrites): k_init writes problem 0's record for all, from SolveParams::ReB_active /
-// update_penalty, and with more than one option set (mhpc_set_option_sets) this kernel then
-// writes each problem's own.  warm: as k_init's.
-// A problem whose record has no AL iteration (n_al = 0) never runs forward_sweep(0): in the
-// reference its SRB phases keep the zero states memory_reset left, since only that first sweep
-// rolls them out.  k_init completed them ahead of that sweep (see there), so with warm the states
-// of its SRB knots in slot 0 go back to zero here (their u and y are zero already); the host
-// makes the problem's first forward_sweep(0) the real rollout should its budget be raised before
-// its next solve (Handle::srb_open).
-__global__ __launch_bounds__(64) void k_init_params(SolveParams sp, DevBufs d, int warm) {
-  const GrpBlk gb = block_group(sp, blockIdx.x, 64);
-  if (gb.g < 0 || gb.p0 + (int)threadIdx.x >= gb.p1) return;
-  const Layout& L = layout_of(d, gb.g);
-  const CostParams& cw = params_of(d, gb.g);
-  const int b = prob_at(sp, d, gb.p0 + threadIdx.x);
-  ProbState* st = &d.st[b];
-  for (int p = 0; p < MAXP; ++p) init_al_reb(st, L, cw, p);
-  const OptRec& o = opt_of(d, b);
-  st->reb_active = o.ReB_active ? 1 : 0;
-  if (!warm) return;
-  st->opt_reb = o.ReB_active ? 1 : 0;
-  st->opt_pen = o.update_penalty;
-  st->cap_reb = st->opt_reb;
-  st->cap_pen = st->opt_pen;
-  if (o.n_al == 0)
-    for (int p = L.n_wb; p < L.P; ++p)
-      for (int k = 0; k < L.N[p]; ++k) {
-        real* r = traj_ptr(sp, d, b, 0, L.ko[p] + k);
-        for (int i = 0; i < 6; ++i) r[i] = real(0.0);
-      }
-}
-
-__global__ __launch_bounds__(64) void k_init(SolveParams sp, DevBufs d, int warm) {
-  // blocks by group, 32 problems a block
-  const GrpBlk gb = block_group(sp, blockIdx.x, 32);
-  const int i0 = threadIdx.x >> 1;
-  const bool back = (threadIdx.x & 1) != 0;
-  if (gb.g < 0 || gb.p0 + i0 >= gb.p1) return;  // both lanes of a pair
-  const Layout& L = layout_of(d, gb.g);
-  const int b = prob_at(sp, d, gb.p0 + i0);
-  const real* x0 = d.x0 + (size_t)b * 14;
-  if (!back) k_init_state(sp, d, L, b, warm);
-  if (!warm) return;
-  // warm start of the WB phases into slot 0 (bounding_PDcontrol, boundingPDControl.cpp:3-46)
-  real x[14];
-  for (int i = 0; i < 14; ++i) x[i] = x0[i];
-  const real qnom[4] = {PI / 4, -PI * 7 / 12, PI / 4, -PI * 7 / 12};
-  const real Kp[4] = {5 * real(8.0), 5 * real(1.0), 5 * real(12.0), 5 * real(10.0)};
-  SinCosK scK = kSinCosK;  // VGPR copies (see k_rollout)
-  MHPC_PIN_VGPRS(scK);
-  for (int p = 0; p < L.n_wb; ++p) {
-    const int mode = L.mode[p], N = L.N[p], ko = L.ko[p];
-    const real dt = L.dt[p];
-    for (int k = 0; k < N - 1; ++k) {
-      // the state-only part of the dynamics first: the stance controller reuses its geometry
-      WbPairPrep P;
-      wb_pair_prep(x, back, P, scK);
-      real u[4];
-#ifdef MHPC_FP32
-      // (fp32: the reference-ordered evaluation below; its C5 accuracy is chaotic in the warm
-      // start's last bits -- the pair-geometry form moved the X 95th percentile of
-      // tests/test_gpu_fp32.py from 7.9e-3 to 1.2e-2, past the 1e-2 target)
-      if (mode == 1 || mode == 3) {
-        real J[14], Jd[14], v[2];
-        if (mode == 1) { wb_foot_jacobian_f<kBack>(x, J, Jd); wb_leg_ext<kBack>(x, v); }
-        else { wb_foot_jacobian_f<kFront>(x, J, Jd); wb_leg_ext<kFront>(x, v); }
-        const real sq = v[0] * v[0] + v[1] * v[1], nrm = sqrt(sq);
-        const real n0 = v[0] / nrm, n1 = v[1] / nrm;
-        const real F0 = -n0 * real(2200.0) * (nrm - real(0.2462)), F1 = -n1 * real(2200.0) * (nrm - real(0.2462));
-        const real gain = mode == 1 ? 3 : real(2.2);
-        for (int i = 0; i < 4; ++i) u[i] = (J[3 + i] * F0 + J[7 + 3 + i] * F1) * gain;
-      }
-#else
-      if (mode == 1 || mode == 3) {
-        // the stance foot's Jacobian (wb_foot_jacobian_f: its leg's hip / knee columns; the
-        // other leg's are exact zeros) and hip-to-foot vector (wb_leg_ext) from the stance
-        // lane's own-leg geometry -- the same expressions on the same sines / cosines
-        const bool mine = (mode == 1) == back;
-        real jx[5], jz[5], jdx, jdz;
-        pair_point_jac(P.L, P.sg, P.sth, P.cth, kThighLen, kShankLen, jx, jz, &jdx, &jdz);
-        const real ve0 = -kThighLen * P.L.s1 - kShankLen * P.L.s2;
-        const real ve1 = -kThighLen * P.L.c1 - kShankLen * P.L.c2;
-        const real v[2] = {mode == 1 ? pair_from<1>(ve0) : pair_from<0>(ve0),
-                           mode == 1 ? pair_from<1>(ve1) : pair_from<0>(ve1)};
-        const real sq = v[0] * v[0] + v[1] * v[1], nrm = sqrt(sq);
-        const real n0 = v[0] / nrm, n1 = v[1] / nrm;
-        const real F0 = -n0 * real(2200.0) * (nrm - real(0.2462)), F1 = -n1 * real(2200.0) * (nrm - real(0.2462));
-        const real gain = mode == 1 ? 3 : real(2.2);
-        real uo[2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-          const real jxa = mine ? jx[3 + a] : real(0.0), jza = mine ? jz[3 + a] : real(0.0);
-          uo[a] = (jxa * F0 + jza * F1) * gain;
-        }
-        u[0] = pair_from<0>(uo[0]); u[1] = pair_from<0>(uo[1]);
-        u[2] = pair_from<1>(uo[0]); u[3] = pair_from<1>(uo[1]);
-      }
-#endif
-      else {
-        for (int i = 0; i < 4; ++i) u[i] = Kp[i] * (qnom[i] - x[3 + i]) - x[10 + i];
-      }
-      const real u2[2] = {back ? u[2] : u[0], back ? u[3] : u[1]};
-      real xd[14], y[4];
-      wb_pair_finish(x, u2, mode, back, P, xd, y);
-      // record x (14) u (4) y (4): even lane entries 0..10, odd lane 11..21
-      real rec[22];
-      for (int i = 0; i < 14; ++i) rec[i] = x[i];
-      for (int i = 0; i < 4; ++i) { rec[14 + i] = u[i]; rec[18 + i] = y[i]; }
-      real* o = traj_ptr(sp, d, b, 0, ko + k) + (back ? 11 : 0);
-#pragma unroll
-      for (int i = 0; i < 11; ++i) o[i] = back ? rec[11 + i] : rec[i];
-      for (int i = 0; i < 14; ++i) x[i] = x[i] + xd[i] * dt;
-    }
-    real* oe = traj_ptr(sp, d, b, 0, ko + N - 1);
-    if (!back) for (int i = 0; i < 14; ++i) oe[i] = x[i];
-    wb_phase_transition(L, p, x);  // the forward sweep's
-  }
-  // SRB phases: the reference's first forward_sweep(0) rolls them out with the initial
-  // (zero) controls and zero gains -- u = (0 + 0*0) + sum 0*(x - 0) = +0 exactly -- so the
-  // nominal is completed here and forward_sweep(0) reduces to a cost evaluation (k_cost).
-  // Both lanes run the (cheap) SRB chain; each writes half of every record.
-  if (L.n_wb == 0)
-    for (int i = 0; i < 6; ++i) x[i] = x0[i];
-  for (int p = L.n_wb; p < L.P; ++p) {
-    const int mode = L.mode[p], N = L.N[p], ko = L.ko[p];
-    const real dt = L.dt[p];
-    real f[4], s[2];
-    plan_foothold(x, dt * N, mode, f);
-    srb_contact(mode, s);
-    const real u[4] = {real(0.0), real(0.0), real(0.0), real(0.0)};
-    for (int k = 0; k < N - 1; ++k) {
-      real xd[6];
-      srb_dynamics(x, u, f, s, xd);
-      real rec[14];
-      for (int i = 0; i < 6; ++i) rec[i] = x[i];
-      for (int i = 0; i < 4; ++i) { rec[6 + i] = u[i]; rec[10 + i] = real(0.0); }
-      real* o = traj_ptr(sp, d, b, 0, ko + k) + (back ? 7 : 0);
-#pragma unroll
-      for (int i = 0; i < 7; ++i) o[i] = back ? rec[7 + i] : rec[i];
-      for (int i = 0; i < 6; ++i) x[i] = x[i] + xd[i] * dt;
-    }
-    real* oe = traj_ptr(sp, d, b, 0, ko + N - 1);
-    if (!back) for (int i = 0; i < 6; ++i) oe[i] = x[i];
-  }
-}
-
-// ============================================================================================
 // k_cost: forward_sweep(0) at the top of an AL iteration (MultiPhaseDDP.cpp:172-190).
 // With eps = 0 the rollout reproduces the nominal trajectory bit for bit (u = u_nom + 0 +
 // K * 0 and the same dynamics code on the same state), so only the costs change (new ReB
@@ -1662,179 +1310,6 @@ __global__ __launch_bounds__(64) void k_cost(SolveParams sp, DevBufs d, int al_i
   }
 }
 
-// Copy each problem's nominal trajectory (slot nom_slot) to a dense staging buffer.
-__global__ void k_export(SolveParams sp, DevBufs d) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long per = (long)sp.NK * KS;
-  const int b = (int)(t / per);
-  if (b >= sp.B) return;
-  const long r = t - (long)b * per;
-  const int nom = d.st[b].nom_slot;
-  d.out[(size_t)b * per + r] = d.traj[(((size_t)b * sp.nslot + nom) * sp.NK) * KS + r];
-}
-
-// The tracking reference x of every knot of problems [b0, b0 + nb) into the staging buffer
-// (mhpc_get_reference_problems): the reference's ms_ref_*[p][k].x as ReferenceGen::generate_ref
-// leaves it (ReferenceGen.h:53-109), built by the helpers the cost kernels use.  Lane =
-// (problem, knot of the knot stride); a record's entries past the phase's state size are zero.
-__global__ void k_export_ref(SolveParams sp, DevBufs d, int b0, int nb) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (long)nb * sp.NK) return;
-  const int b = b0 + (int)(t / sp.NK), kk = (int)(t % sp.NK);
-  const Layout& L = d.grp[d.lid[b]].lay;  // the problem's layout (per lane: not a hot kernel)
-  if (kk >= L.NK) return;
-  int p = 0;
-  while (p + 1 < L.P && kk >= L.ko[p + 1]) ++p;
-  const bool wb = p < L.n_wb, last = kk - L.ko[p] == L.N[p] - 1;
-  const Cmd cm = cmd_of(d, b);
-  const real pos = d.refpos[(size_t)b * sp.NK + kk];
-  real rx[14];
-#pragma unroll
-  for (int i = 0; i < 14; ++i) rx[i] = real(0.0);
-  if (wb) {
-    if (last) wb_term_ref(cm, L.mode[p], pos, rx);
-    else wb_run_ref(cm, pos, rx);
-  } else {
-    if (last) fb_term_ref(cm, pos, rx);
-    else fb_run_ref(cm, pos, rx);
-  }
-  real* o = d.out + ((size_t)b * sp.NK + kk) * KS;
-#pragma unroll
-  for (int i = 0; i < 14; ++i) o[i] = rx[i];
-}
-
-// ---- kernel-level parity hooks (batched CasADi replacements) -----------------------------
-__global__ void k_eval_wb_dyn(int n, int mode, const real* x, const real* u, real* xd,
-                              real* y) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  wb_dynamics<real>(x + (size_t)i * 14, u + (size_t)i * 4, mode, xd + (size_t)i * 14, y + (size_t)i * 4);
-}
-
-// The line search's lane-pair dynamics (mhpc_model_pair.h): lane 2i + leg of point i, both
-// lanes' xdot / y written ([n][2][14], [n][2][4]) so a test can check that each equals the
-// single-lane model.  Lanes past 2n hold whole idle pairs (the DPP swaps stay inside pairs).
-__global__ void k_eval_wb_dyn_pair(int n, int mode, const real* x, const real* u, real* xd,
-                                   real* y) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int i = t >> 1;
-  const bool back = t & 1;
-  if (i >= n) return;
-  const real* xi = x + (size_t)i * 14;
-  const real u2[2] = {u[(size_t)i * 4 + (back ? 2 : 0)], u[(size_t)i * 4 + (back ? 3 : 1)]};
-  real f[14], yy[4];
-  wb_dynamics_pair(xi, u2, mode, back, f, yy);
-  for (int r = 0; r < 14; ++r) xd[(size_t)t * 14 + r] = f[r];
-  for (int r = 0; r < 4; ++r) y[(size_t)t * 4 + r] = yy[r];
-}
-
-// Touchdown constraint (WB_FL1/FL2_terminal_constr) as the kernels evaluate it: h both from
-// the derivative routine (backward sweep) and from the value-only one (line search), hx, hxx;
-// and the foot Jacobian (Jacob_F / Jacob_B) of the PD warm start.
-__global__ void k_eval_wb_aux(int n, int foot, const real* x, real* h, real* hx, real* hxx,
-                              real* J, real* Jd) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const real* xi = x + (size_t)i * 14;
-  wb_touchdown(xi, foot, h + (size_t)i * 2, hx + (size_t)i * 14, hxx + (size_t)i * 196);
-  h[(size_t)i * 2 + 1] = foot == kFront ? wb_touchdown_value<kFront>(xi) : wb_touchdown_value<kBack>(xi);
-  wb_foot_jacobian(xi, foot, J + (size_t)i * 14, Jd + (size_t)i * 14);
-}
-
-__global__ void k_eval_wb_par(int n, int mode, const real* x, const real* u, real* Ac,
-                              real* Bc, real* C, real* D) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n * 18) return;
-  const int i = t / 18, dir = t % 18;
-  // the partials kernel's method (implicit differentiation at the point's solution)
-  real a[14], c[4];
-  wb_partial_column(x + (size_t)i * 14, u + (size_t)i * 4, mode, dir, a, c);
-  if (dir < 14) {
-    for (int r = 0; r < 14; ++r) Ac[(size_t)i * 196 + r * 14 + dir] = a[r];
-    for (int r = 0; r < 4; ++r) C[(size_t)i * 56 + r * 14 + dir] = c[r];
-  } else {
-    for (int r = 0; r < 14; ++r) Bc[(size_t)i * 56 + r * 4 + dir - 14] = a[r];
-    for (int r = 0; r < 4; ++r) D[(size_t)i * 16 + r * 4 + dir - 14] = c[r];
-  }
-}
-
-__global__ void k_eval_wb_impact(int n, int foot, const real* x, real* xp, real* Px) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n * 14) return;
-  const int i = t / 14, dir = t % 14;
-  Dual xx[14], yy[14], lam[2];
-  for (int a = 0; a < 14; ++a) xx[a] = Dual(x[(size_t)i * 14 + a], a == dir ? real(1.0) : real(0.0));
-  wb_impact<Dual>(xx, foot, yy, lam);
-  for (int r = 0; r < 14; ++r) Px[(size_t)i * 196 + r * 14 + dir] = yy[r].d;
-  if (dir == 0)
-    for (int r = 0; r < 14; ++r) xp[(size_t)i * 14 + r] = yy[r].v;
-}
-
-__global__ void k_eval_srb(int n, const real* x, const real* u, const real* p,
-                           const real* s, real* xd, real* Ac, real* Bc) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  srb_dynamics(x + (size_t)i * 6, u + (size_t)i * 4, p + (size_t)i * 4, s + (size_t)i * 2, xd + (size_t)i * 6);
-  srb_jacobians(x + (size_t)i * 6, u + (size_t)i * 4, p + (size_t)i * 4, s + (size_t)i * 2, Ac + (size_t)i * 36, Bc + (size_t)i * 24);
-}
-
-// One hand-written elementary function per point, called as the solve kernels call it
-// (mhpc_eval_primitive, MHPC_PRIM_*).  Lane t of a 64-lane block evaluates point t of the
-// launch, so the caller decides which arguments share a wave (the wave-uniform library
-// fallback of sin_cos); of the sin_cos_n functions, group t of N consecutive angles.  out is
-// [n][w]: w = 2 (sin, cos), 3 (B, Bz, Bzz) or 1.
-template <int N>
-static __device__ __forceinline__ void eval_sin_cos_n(int n, bool vk, const real* a, real* out) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  // the knot loops' VGPR copy of the constants (k_rollout); lanes past the last group run the
-  // functions too, on zeros: the ballot inside is over the whole wave
-  SinCosK scK = kSinCosK;
-  if (vk) MHPC_PIN_VGPRS(scK);
-  const bool live = (g + 1) * N <= n;
-  real v[N], s[N], c[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = live ? a[(size_t)g * N + i] : real(0.0);
-  if (vk) sin_cos_n<N>(v, s, c, scK);
-  else sin_cos_n<N>(v, s, c);
-  if (!live) return;
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    out[((size_t)g * N + i) * 2] = s[i];
-    out[((size_t)g * N + i) * 2 + 1] = c[i];
-  }
-}
-__global__ void k_eval_prim(int fn, int n, const real* a, const real* b, real* out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  switch (fn) {  // uniform
-    case MHPC_PRIM_SINCOS_N5: eval_sin_cos_n<5>(n, false, a, out); return;
-    case MHPC_PRIM_SINCOS_N3: eval_sin_cos_n<3>(n, false, a, out); return;
-    case MHPC_PRIM_SINCOS_N5_VK: eval_sin_cos_n<5>(n, true, a, out); return;
-    case MHPC_PRIM_SINCOS_N3_VK: eval_sin_cos_n<3>(n, true, a, out); return;
-    default: break;
-  }
-  const bool live = i < n;
-  const real ai = live ? a[i] : real(1.0);
-  if (fn == MHPC_PRIM_SINCOS) {  // every lane of the wave reaches the ballot
-    real s, c;
-    sin_cos(ai, &s, &c);
-    if (live) { out[(size_t)i * 2] = s; out[(size_t)i * 2 + 1] = c; }
-    return;
-  }
-  if (!live) return;
-  if (fn == MHPC_PRIM_PIVOT_RCP) {
-    out[i] = pivot_rcp(ai);
-  } else if (fn == MHPC_PRIM_LOG_POS) {
-    out[i] = log_pos(ai);
-  } else if (fn == MHPC_PRIM_REDUCED_BARRIER) {
-    real B, Bz, Bzz;
-    reduced_barrier(ai, b[i], &B, &Bz, &Bzz);
-    out[(size_t)i * 3] = B; out[(size_t)i * 3 + 1] = Bz; out[(size_t)i * 3 + 2] = Bzz;
-  } else if (fn == MHPC_PRIM_DIV_CONST) {  // b: 0 the SRB mass, otherwise its inertia
-    out[i] = b[i] == real(0.0) ? div_const(ai, kSrbMass, kSrbMassRcp)
-                               : div_const(ai, kSrbInertia, kSrbInertiaRcp);
-  }
-}
-
 // Sum the per-problem counters of each group (int64 atomics into NCNT slots per group).
 // One block of 256 threads, strided over the batch, tree-reduced in LDS: NCNT atomics per
 // block instead of per problem (the per-problem atomics on NCNT words serialised, ~35 us).
@@ -1864,59 +1339,13 @@ __global__ __launch_bounds__(256) void k_reduce_counters(SolveParams sp, DevBufs
 }
 
 // ---- launchers (called by mhpc_runtime.cpp) ---------------------------------------------
-// Blocks of a launch over the groups with `per` problems a block (block_group)
-static unsigned grid_of(const SolveParams& sp, int per) {
-  long n = 0;
-  for (int g = 0; g < sp.ngrp; ++g) n += (sp.go[g + 1] - sp.go[g] + per - 1) / per;
-  return (unsigned)n;
-}
-// ... and with items[g] (or n_items) work items per problem, nt a block (block_group_items)
-static unsigned grid_items(const SolveParams& sp, const int* items, int n_items, int nt) {
-  long n = 0;
-  for (int g = 0; g < sp.ngrp; ++g)
-    n += ((long)(sp.go[g + 1] - sp.go[g]) * (items ? items[g] : n_items) + nt - 1) / nt;
-  return (unsigned)n;
-}
+// (grid_of / grid_items, the block counts of a launch over the groups, are in mhpc_launch.h)
 // Problems of a launch (a sub-batch's share of the batch)
 int launch_problems(const SolveParams& sp) { return sp.go[sp.ngrp] - sp.go[0]; }
 hipError_t launch_reduce_counters(const SolveParams& sp, const DevBufs& d,
                                   unsigned long long* out, hipStream_t s) {
   const int nb = std::min((sp.B + 255) / 256, 64);
   hipLaunchKernelGGL(k_reduce_counters, dim3(nb, sp.ngrp), dim3(256), 0, s, sp, d, out);
-  return hipGetLastError();
-}
-hipError_t launch_reset(const SolveParams& sp, const DevBufs& d, hipStream_t s) {
-  hipLaunchKernelGGL(k_init, dim3(grid_of(sp, 32)), dim3(64), 0, s, sp, d, 0);
-  return hipGetLastError();
-}
-hipError_t launch_reset_arrays(const SolveParams& sp, const DevBufs& d, hipStream_t s) {
-  // ~64 elements per lane, at most 2 blocks per CU
-  const long e = (long)sp.B * sp.NK * 74 + (long)sp.B * sp.nslot * sp.pmax;
-  const long nb = std::min((e + 256 * 64 - 1) / (256 * 64), 2L * sp.ncu);
-  hipLaunchKernelGGL(k_reset_arrays, dim3((unsigned)nb), dim3(256), 0, s, sp, d);
-  return hipGetLastError();
-}
-hipError_t launch_scatter_x0(const DevBufs& d, int n, const int* list, const real* rows,
-                             hipStream_t s) {
-  hipLaunchKernelGGL(k_scatter_x0, dim3((unsigned)((n * 14L + 63) / 64)), dim3(64), 0, s, d, n, list,
-                     rows);
-  return hipGetLastError();
-}
-// store == nullptr: no phase-buffer store yet (nbk, spmax ignored)
-hipError_t launch_reset_list(const SolveParams& sp, const DevBufs& d, int n, const int* list,
-                             real* store, int nbk, int spmax, hipStream_t s) {
-  if (!store) nbk = spmax = 0;
-  const int nch = (std::max(sp.NK, spmax * nbk) + RL_CH - 1) / RL_CH;
-  hipLaunchKernelGGL(k_reset_list, dim3((unsigned)n * nch), dim3(256), 0, s, sp, d, list, nch, store,
-                     nbk, spmax);
-  return hipGetLastError();
-}
-hipError_t launch_init_params(const SolveParams& sp, const DevBufs& d, int warm, hipStream_t s) {
-  hipLaunchKernelGGL(k_init_params, dim3(grid_of(sp, 64)), dim3(64), 0, s, sp, d, warm);
-  return hipGetLastError();
-}
-hipError_t launch_init(const SolveParams& sp, const DevBufs& d, hipStream_t s) {
-  hipLaunchKernelGGL(k_init, dim3(grid_of(sp, 32)), dim3(64), 0, s, sp, d, 1);
   return hipGetLastError();
 }
 hipError_t launch_cost(const SolveParams& sp, const DevBufs& d, int al_iter, hipStream_t s) {
@@ -2068,61 +1497,6 @@ hipError_t launch_partials(const SolveParams& sp, const DevBufs& d, int al_iter,
 }
 hipError_t launch_al_end(const SolveParams& sp, const DevBufs& d, int al, int last, hipStream_t s) {
   hipLaunchKernelGGL(k_al_end, dim3(grid_of(sp, 64)), dim3(64), 0, s, sp, d, al, last);
-  return hipGetLastError();
-}
-hipError_t launch_export(const SolveParams& sp, const DevBufs& d, hipStream_t s) {
-  const long total = (long)sp.B * sp.NK * KS;
-  hipLaunchKernelGGL(k_export, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sp, d);
-  return hipGetLastError();
-}
-hipError_t launch_export_ref(const SolveParams& sp, const DevBufs& d, int b0, int nb, hipStream_t s) {
-  const long total = (long)nb * sp.NK;
-  hipLaunchKernelGGL(k_export_ref, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sp, d, b0,
-                     nb);
-  return hipGetLastError();
-}
-hipError_t launch_eval_wb_dyn(int n, int mode, const real* x, const real* u, real* xd,
-                              real* y, hipStream_t s) {
-  hipLaunchKernelGGL(k_eval_wb_dyn, dim3((n + 63) / 64), dim3(64), 0, s, n, mode, x, u, xd, y);
-  return hipGetLastError();
-}
-hipError_t launch_eval_wb_dyn_pair(int n, int mode, const real* x, const real* u, real* xd,
-                                   real* y, hipStream_t s) {
-  hipLaunchKernelGGL(k_eval_wb_dyn_pair, dim3((2 * n + 63) / 64), dim3(64), 0, s, n, mode, x, u, xd,
-                     y);
-  return hipGetLastError();
-}
-hipError_t launch_eval_wb_aux(int n, int foot, const real* x, real* h, real* hx, real* hxx,
-                              real* J, real* Jd, hipStream_t s) {
-  hipLaunchKernelGGL(k_eval_wb_aux, dim3((n + 63) / 64), dim3(64), 0, s, n, foot, x, h, hx, hxx, J,
-                     Jd);
-  return hipGetLastError();
-}
-hipError_t launch_eval_wb_par(int n, int mode, const real* x, const real* u, real* Ac,
-                              real* Bc, real* C, real* D, hipStream_t s) {
-  hipLaunchKernelGGL(k_eval_wb_par, dim3((n * 18 + 63) / 64), dim3(64), 0, s, n, mode, x, u, Ac,
-                     Bc, C, D);
-  return hipGetLastError();
-}
-hipError_t launch_eval_wb_impact(int n, int foot, const real* x, real* xp, real* Px,
-                                 hipStream_t s) {
-  hipLaunchKernelGGL(k_eval_wb_impact, dim3((n * 14 + 63) / 64), dim3(64), 0, s, n, foot, x, xp, Px);
-  return hipGetLastError();
-}
-hipError_t launch_eval_srb(int n, const real* x, const real* u, const real* p,
-                           const real* c, real* xd, real* Ac, real* Bc, hipStream_t s) {
-  hipLaunchKernelGGL(k_eval_srb, dim3((n + 63) / 64), dim3(64), 0, s, n, x, u, p, c, xd, Ac, Bc);
-  return hipGetLastError();
-}
-int eval_prim_group(int fn) {
-  return fn == MHPC_PRIM_SINCOS_N5 || fn == MHPC_PRIM_SINCOS_N5_VK   ? 5
-         : fn == MHPC_PRIM_SINCOS_N3 || fn == MHPC_PRIM_SINCOS_N3_VK ? 3
-                                                                     : 1;
-}
-hipError_t launch_eval_prim(int fn, int n, const real* a, const real* b, real* out,
-                            hipStream_t s) {
-  const int lanes = n / eval_prim_group(fn);  // n is a multiple of the group (the hook checks)
-  hipLaunchKernelGGL(k_eval_prim, dim3((lanes + 63) / 64), dim3(64), 0, s, fn, n, a, b, out);
   return hipGetLastError();
 }
 

@@ -9,7 +9,48 @@
 
 namespace MHPC_NS {
 
+// Blocks of a launch over the groups with `per` problems a block (block_group)
+static inline unsigned grid_of(const SolveParams& sp, int per) {
+  long n = 0;
+  for (int g = 0; g < sp.ngrp; ++g) n += (sp.go[g + 1] - sp.go[g] + per - 1) / per;
+  return (unsigned)n;
+}
+// ... and with items[g] (or n_items) work items per problem, nt a block (block_group_items)
+static inline unsigned grid_items(const SolveParams& sp, const int* items, int n_items, int nt) {
+  long n = 0;
+  for (int g = 0; g < sp.ngrp; ++g)
+    n += ((long)(sp.go[g + 1] - sp.go[g]) * (items ? items[g] : n_items) + nt - 1) / nt;
+  return (unsigned)n;
+}
+
 // ---- mhpc_kernels.hip -----------------------------------------------------------------------
+hipError_t launch_cost(const SolveParams& sp, const DevBufs& d, int al_iter, hipStream_t s);
+hipError_t launch_rollout(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter,
+                          int full, hipStream_t s);
+// (al_iter, ddp_iter: the op of the solve schedule a launch belongs to -- every kernel of the
+// schedule leaves out the problems whose own iteration caps exclude that op, in_op, mhpc_device.h)
+hipError_t launch_partials(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter,
+                           hipStream_t s, hipStream_t s3, hipEvent_t fork, hipEvent_t join);
+hipError_t launch_al_end(const SolveParams& sp, const DevBufs& d, int al, int last, hipStream_t s);
+hipError_t launch_reduce_counters(const SolveParams& sp, const DevBufs& d,
+                                  unsigned long long* out, hipStream_t s);
+int launch_problems(const SolveParams& sp);  // problems of a launch (a sub-batch's share)
+int ro_store_default();
+int ro_store_auto(const SolveParams& sp);
+
+// the serial rollouts beside the schedule and the debug gradient: not part of a solve, kept in
+// mhpc_kernels.hip because k_policy_rollout's code changes without k_partials_impact beside it
+// (profiles/kernels_split_ab.md)
+hipError_t launch_cost_grad(const SolveParams& sp, const DevBufs& d, int g, int p, int N, int b0,
+                            int nb, real* lx, real* phix, hipStream_t s);
+hipError_t launch_eps_rollout(const SolveParams& sp, const DevBufs& d, int n_eps,
+                              const real* eps, real* J, real* viol, hipStream_t s);
+constexpr int PREC_W = 22;  // k_policy_rollout's knot record: x 14, u 4, y 4
+hipError_t launch_policy_rollout(const SolveParams& sp, const DevBufs& d, int n_s, int b0, int nb,
+                                 const real* xs, const double* dx, int n_phases, int rec_p,
+                                 real* J, real* viol, real* xe, real* rec, hipStream_t s);
+
+// ---- mhpc_init.hip --------------------------------------------------------------------------
 hipError_t launch_init(const SolveParams& sp, const DevBufs& d, hipStream_t s);
 hipError_t launch_init_params(const SolveParams& sp, const DevBufs& d, int warm, hipStream_t s);
 hipError_t launch_reset(const SolveParams& sp, const DevBufs& d, hipStream_t s);
@@ -20,38 +61,18 @@ hipError_t launch_scatter_x0(const DevBufs& d, int n, const int* list, const rea
                              hipStream_t s);
 hipError_t launch_reset_list(const SolveParams& sp, const DevBufs& d, int n, const int* list,
                              real* store, int nbk, int spmax, hipStream_t s);
-hipError_t launch_cost(const SolveParams& sp, const DevBufs& d, int al_iter, hipStream_t s);
-hipError_t launch_rollout(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter,
-                          int full, hipStream_t s);
-// (al_iter, ddp_iter: the op of the solve schedule a launch belongs to -- every kernel of the
-// schedule leaves out the problems whose own iteration caps exclude that op, in_op, mhpc_device.h)
-hipError_t launch_partials(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter,
-                           hipStream_t s, hipStream_t s3, hipEvent_t fork, hipEvent_t join);
-hipError_t launch_al_end(const SolveParams& sp, const DevBufs& d, int al, int last, hipStream_t s);
-hipError_t launch_export(const SolveParams& sp, const DevBufs& d, hipStream_t s);
-hipError_t launch_export_ref(const SolveParams& sp, const DevBufs& d, int b0, int nb, hipStream_t s);
-hipError_t launch_reduce_counters(const SolveParams& sp, const DevBufs& d,
-                                  unsigned long long* out, hipStream_t s);
-int launch_problems(const SolveParams& sp);  // problems of a launch (a sub-batch's share)
-int ro_store_default();
-int ro_store_auto(const SolveParams& sp);
 
+// ---- mhpc_store.hip -------------------------------------------------------------------------
 // Phase-buffer store of the receding-horizon loop, [B][spmax][nbk][kStoreRec]: buffers of
 // N_TIMESTEPS_MAX (MHPCLocomotion.h) knots at least; record = x,u,y + K + du + G
 constexpr int kPhaseBufKnots = 110;
 constexpr int kStoreRec = KS + 56 + 4 + 14;
 hipError_t launch_store(const SolveParams& sp, const DevBufs& d, real* store, int nbk, int spmax,
                         int save, hipStream_t s);
+hipError_t launch_export(const SolveParams& sp, const DevBufs& d, hipStream_t s);
+hipError_t launch_export_ref(const SolveParams& sp, const DevBufs& d, int b0, int nb, hipStream_t s);
 
-hipError_t launch_cost_grad(const SolveParams& sp, const DevBufs& d, int g, int p, int N, int b0,
-                            int nb, real* lx, real* phix, hipStream_t s);
-hipError_t launch_eps_rollout(const SolveParams& sp, const DevBufs& d, int n_eps,
-                              const real* eps, real* J, real* viol, hipStream_t s);
-constexpr int PREC_W = 22;  // k_policy_rollout's knot record: x 14, u 4, y 4
-hipError_t launch_policy_rollout(const SolveParams& sp, const DevBufs& d, int n_s, int b0, int nb,
-                                 const real* xs, const double* dx, int n_phases, int rec_p,
-                                 real* J, real* viol, real* xe, real* rec, hipStream_t s);
-
+// ---- mhpc_eval.hip --------------------------------------------------------------------------
 // model evaluation hooks (n points each)
 hipError_t launch_eval_wb_dyn(int n, int mode, const real* x, const real* u, real* xd,
                               real* y, hipStream_t s);

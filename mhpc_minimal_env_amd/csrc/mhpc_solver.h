@@ -147,7 +147,7 @@ struct SolveParams {
   int split_ok, stage_fits;
   // problem 0's parameter set (what mhpc_get_cost_weights / mhpc_get_constraint_params report).
   // Only k_init reads it, for the AL / ReB initial values it writes for every problem; the
-  // groups' own values then come from the table (k_init_params, mhpc_kernels.hip, which says
+  // groups' own values then come from the table (k_init_params, mhpc_init.hip, which says
   // why k_init keeps this read).  Every other kernel reads the group table alone.
   CostParams cw;
 };

@@ -1,6 +1,6 @@
 // Device code of mhpc_tick_problems that the batch-wide update has no list-driven form of: the
 // phase-buffer save / load of the listed problems (k_store_save / k_store_load of
-// mhpc_kernels.hip walk B * NK threads) and the gather of their status words.  Every other kernel
+// mhpc_store.hip walk B * NK threads) and the gather of their status words.  Every other kernel
 // of a tick is one of the solve's own, launched over the tick's scope.
 //
 // Pure memory traffic, list-driven: device work is proportional to the number of listed problems,
@@ -14,7 +14,7 @@
 namespace MHPC_NS {
 
 // store [B][spmax][nbk][kStoreRec]: x,u,y (a traj record, KS), K 56, du 4, G 14 per knot; phase p
-// of a problem's layout lives in its buffer L.buf[p] (mhpc_kernels.hip, k_store_save).
+// of a problem's layout lives in its buffer L.buf[p] (mhpc_store.hip, k_store_save).
 constexpr int SREC = kStoreRec;
 constexpr int TL_CH = 64;  // knots of the stride a block serves (k_reset_list's chunk)
 

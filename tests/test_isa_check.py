@@ -97,9 +97,13 @@ def test_generated_dpp_header_is_current():
 def test_shipping_kernels_have_no_misplaced_join_copy():
     r = subprocess.run(["make", "-j4", "-C", CSRC, "isa-check"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    isa = [os.path.join(CSRC, "_build", f) for f in ("kernels.s", "bws.s", "kernels32.s", "bws32.s")]
+    def listed(target):  # the Makefile's own lists: every kernel unit in every variant
+        out = subprocess.run(["make", "-s", "-C", CSRC, target], capture_output=True, text=True, check=True)
+        return [os.path.join(CSRC, f) for f in out.stdout.split()]
+    isa, sweeps = listed("print-isa"), listed("print-sweeps")
+    assert len(isa) >= 15 and len(sweeps) == 3 and set(sweeps) <= set(isa)
+    assert all(os.path.exists(p) for p in isa)
     assert C.scan_all(isa) == []
-    sweeps = [os.path.join(CSRC, "_build", f) for f in ("bws.s", "bws32.s")]
     assert D.main(sweeps) == 0
     assert S.main(isa) == 0
     for p in sweeps:  # the row-broadcast FMAs are there (the gate checked something)
