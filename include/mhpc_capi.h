@@ -70,6 +70,15 @@
  *                        (SinglePhase.h's per-knot x, u, y and K, du, G) of the listed problems, and
  *                        mhpc_export_results_device their _actual_cost, _exp_cost_change,
  *                        _tconstr_violation, _V, _dV, into device arrays of the caller's
+ *   mhpc_import_plan_device   a write into _phases[p]->get_nominal_ms_ptr() / get_CTG_info_ptr()
+ *                        between initialization() or update_problem() and solve_mhpc(): the
+ *                        reference's own warmstart() does exactly that for the whole-body phases'
+ *                        controls (MHPCLocomotion.cpp:47-53, 200-215), and MultiPhaseDDP::solve
+ *                        starts with forward_sweep(0) (MultiPhaseDDP.cpp:187), a real rollout of
+ *                        u = u_nom + 0 du + K (x - x_nom) from _x0 (SinglePhase.cpp:62-114, :76).
+ *                        Here: the listed problems' u_nom (and K, x_nom) from device arrays of the
+ *                        caller's, and their next first sweep the real rollout; mhpc_import_plan
+ *                        the same from host arrays, mhpc_num_plan_steps counts the steps
  */
 #ifndef MHPC_CAPI_H
 #define MHPC_CAPI_H
@@ -799,6 +808,68 @@ typedef struct {
 
 int mhpc_export_results_device(mhpc_handle* h, int n, const int32_t* problems,
                                const mhpc_results_out* out, int dtype, void* stream);
+
+/* ---- device-resident plan import: warm-start listed problems from device arrays -------------
+ * The other direction of mhpc_export_plan_device: "start problem b from these controls".  The
+ * nominal controls of the listed problems at a window of steps are overwritten, optionally the
+ * gains and the nominal states they refer to as well, and the problems are marked so that the
+ * first forward_sweep(0) of their next mhpc_solve / mhpc_tick_problems is the real rollout of
+ * u = u_nom + K (x - x_nom) from x0, exactly as after mhpc_update_problem(s).  Nothing else changes.
+ *  - Steps.  scope chooses the step map.  MHPC_STEPS_CONTROL: the control steps of mhpc_control
+ *    and mhpc_export_plan_device -- the whole-body phases of a problem that has any (the scope of
+ *    the reference's warmstart(); the SRB phases keep what they hold, zero controls after
+ *    mhpc_initialize), all phases of an SRB-only problem; an exported window can be imported as it
+ *    is.  MHPC_STEPS_ALL: every phase of the problem in order.  Either way phase p contributes
+ *    N[p] - 1 steps (its last knot has no control), by the problem's current layout.
+ *    mhpc_num_plan_steps counts a problem's steps under a scope.
+ *  - Addressing as the export's: row i belongs to problems[i] (a host list of n entries, each in
+ *    range and none twice; NULL: n == batch, in order); first_step a host array of n entries
+ *    (NULL: 0), 0 <= first_step[i] < mhpc_num_plan_steps(problems[i], scope); 1 <= window <=
+ *    MHPC_MAX_KNOTS; window row w is step first_step[i] + w; rows past the problem's valid =
+ *    min(window, steps - first_step[i]) are ignored.  ld_* = elements between two listed
+ *    problems' blocks, 0 = dense.
+ *  - Values.  r is the handle's x0 row length (14 or 6); a step's state size n is its phase's: 14
+ *    in a whole-body phase, 6 in an SRB phase.  u_nom [n][W][4] (required) goes into entries
+ *    n..n+4 of the knot's record in the problem's current nominal trajectory; x_nom [n][W][r] into
+ *    entries 0..n; K [n][W][4][r], row-major, into the knot's dense 4 n gain words.  Columns past n
+ *    (of x_nom and of K's rows) are not read.  K is optional and x_nom required exactly when K is
+ *    given.  Without K the written knots' 56 gain words become +0 -- the guess is open-loop -- and
+ *    their x_nom entries stay.  Never written: y, du, Vx, any other trajectory, the partials, the
+ *    problem's state and scalars, any knot outside the window, any unlisted problem.  (The rollout
+ *    at eps = 0 multiplies du by zero, and the next backward sweep rewrites du and Vx before
+ *    anything reads them.)  Element types: widened exactly, rounded to nearest into an fp32
+ *    handle.  The device flavour does not inspect values: a non-finite guess ends as
+ *    MHPC_SOLVE_NONFINITE like any problem that blows up.  The host flavour (dense double arrays,
+ *    staged into the same kernel) refuses non-finite entries among those it would read.
+ *  - Call order.  A problem that has been given a guess stops being fresh (mhpc_reset_problems):
+ *    its next first sweep is the rollout.  On a handle that is initialised and not yet solved with
+ *    no rollout due, the next mhpc_solve starts with the rollout for the guessed problems and with
+ *    the cost evaluation for all others, which therefore come out bit for bit as without the
+ *    import.  A problem whose option record has max_AL_iter = 0 never rolls anything out, in the
+ *    reference either: its guess stays as written.  A later mhpc_reset_problems of the same
+ *    problem wins; a second import overlays the first.  Snapshots carry the marks as before.
+ *  - Refusals and streams as mhpc_export_plan_device: MHPC_ERR_STATE before mhpc_initialize and
+ *    while commands or parameters are pending, a pending x0 does not block.  MHPC_ERR_INVALID,
+ *    before anything is written: a null `in` or u_nom, K without x_nom (or x_nom without K), a bad
+ *    list, first step, window, scope or dtype, an ld_* that is neither 0 nor at least the dense
+ *    block, a pointer that is not device memory of the handle's device.  A refused call changes
+ *    nothing.  The work is ordered behind everything queued on `stream` at the call and has
+ *    finished when the call returns.  ms (optional): the device time of the launch. */
+#define MHPC_STEPS_CONTROL 0
+#define MHPC_STEPS_ALL 1
+typedef struct {
+  const void* u_nom; int64_t ld_u_nom;  /* [n][W][4]     required                      */
+  const void* K;     int64_t ld_K;      /* [n][W][4][r]  optional, row-major           */
+  const void* x_nom; int64_t ld_x_nom;  /* [n][W][r]     given exactly when K is given */
+} mhpc_plan_in;
+
+int mhpc_num_plan_steps(mhpc_handle* h, int problem, int scope, int* n);
+int mhpc_import_plan_device(mhpc_handle* h, int n, const int32_t* problems,
+                            const int32_t* first_step, int window, int scope,
+                            const mhpc_plan_in* in, int dtype, void* stream, float* ms);
+int mhpc_import_plan(mhpc_handle* h, int n, const int32_t* problems, const int32_t* first_step,
+                     int window, int scope, const double* u_nom, const double* K,
+                     const double* x_nom);
 
 /* Per-kernel device timing (HIP events around every launch on the handle's stream) and the
  * algorithmic HBM bytes each kernel must move (model in DESIGN.md §Roofline), accumulated

@@ -676,6 +676,52 @@ class MHPCLocomotion {
                                      stream),
           "mhpc_export_results_device");
   }
+  // ---- plan import: warm-start listed problems from a guess ---------------------------------
+  // steps of problem b under a scope (mhpc_num_plan_steps): MHPC_STEPS_CONTROL the control steps
+  // above, MHPC_STEPS_ALL every phase in order
+  int num_plan_steps(int b = 0, int scope = MHPC_STEPS_CONTROL) {
+    int n = 0;
+    check(mhpc_num_plan_steps(h_, b, scope, &n), "mhpc_num_plan_steps");
+    return n;
+  }
+  // `window` steps of each listed problem's nominal from first_step[i] (empty: 0) out of the
+  // device arrays `in` names (mhpc_import_plan_device): u_nom, optionally K with x_nom; without K
+  // the written knots' gains become +0.  The listed problems' next solve or tick starts with the
+  // real rollout of the guess from x0, as after update_problem().  Returns the device ms of the
+  // launch.  Ordered after everything queued on `stream`, finished when the call returns.
+  float import_plan_device(const std::vector<int32_t>& problems, const std::vector<int32_t>& first_step,
+                           int window, const mhpc_plan_in& in, int scope = MHPC_STEPS_CONTROL,
+                           int dtype = MHPC_DEV_F64, void* stream = nullptr) {
+    const int n = problems.empty() ? batch_ : (int)problems.size();
+    if (!first_step.empty() && first_step.size() != (size_t)n)
+      throw std::runtime_error("import_plan_device: first_step must have one entry per listed problem, or none");
+    float ms = 0;
+    check(mhpc_import_plan_device(h_, n, problems.empty() ? nullptr : problems.data(),
+                                  first_step.empty() ? nullptr : first_step.data(), window, scope,
+                                  &in, dtype, stream, &ms),
+          "mhpc_import_plan_device");
+    return ms;
+  }
+  // the same from dense host arrays (mhpc_import_plan): u_nom [n][window][4], K
+  // [n][window][4][x0_width()] and x_nom [n][window][x0_width()] (both or neither); non-finite
+  // entries are refused
+  void import_plan(const std::vector<int32_t>& problems, const std::vector<int32_t>& first_step,
+                   int window, const std::vector<double>& u_nom,
+                   const std::vector<double>& K = {}, const std::vector<double>& x_nom = {},
+                   int scope = MHPC_STEPS_CONTROL) {
+    const size_t n = problems.empty() ? (size_t)batch_ : problems.size();
+    const size_t W = window > 0 ? (size_t)window : 0;
+    if (!first_step.empty() && first_step.size() != n)
+      throw std::runtime_error("import_plan: first_step must have one entry per listed problem, or none");
+    if (u_nom.size() != n * W * 4 || (!K.empty() && K.size() != n * W * 4 * xw_) ||
+        (!x_nom.empty() && x_nom.size() != n * W * xw_))
+      throw std::runtime_error("import_plan: u_nom must be [n][window][4], K [n][window][4][x0_width()], x_nom [n][window][x0_width()]");
+    check(mhpc_import_plan(h_, (int)n, problems.empty() ? nullptr : problems.data(),
+                           first_step.empty() ? nullptr : first_step.data(), window, scope,
+                           u_nom.data(), K.empty() ? nullptr : K.data(),
+                           x_nom.empty() ? nullptr : x_nom.data()),
+          "mhpc_import_plan");
+  }
   // set_initial_conditions from a device array, at once (mhpc_set_x0_device): rows of x0_width()
   // at x0 + b * ld; the device rows are then the current ones, update_problem() /
   // initialization() push no host copy over them

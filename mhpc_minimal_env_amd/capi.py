@@ -44,6 +44,8 @@ MHPC_SNAPSHOT_VERSION = 1
 # element type of a caller's device array (mhpc_control_device, mhpc_set_x0_device, the exports)
 MHPC_DEV_F64 = 0
 MHPC_DEV_F32 = 1
+MHPC_STEPS_CONTROL = 0
+MHPC_STEPS_ALL = 1
 MHPC_SOLVE_OK = 0
 MHPC_SOLVE_REG_ABORT = 1
 MHPC_SOLVE_NONFINITE = 2
@@ -61,6 +63,16 @@ class PlanOut(ctypes.Structure):
         ("y", ctypes.c_void_p), ("ld_y", ctypes.c_int64),
         ("mode", ctypes.c_void_p), ("ld_mode", ctypes.c_int64),
         ("valid", ctypes.c_void_p),
+    ]
+
+
+class PlanIn(ctypes.Structure):
+    """mhpc_plan_in: the given arrays of mhpc_import_plan_device (device pointers; 0 = not given)
+    and the elements between two listed problems' blocks (0 = dense)."""
+    _fields_ = [
+        ("u_nom", ctypes.c_void_p), ("ld_u_nom", ctypes.c_int64),
+        ("K", ctypes.c_void_p), ("ld_K", ctypes.c_int64),
+        ("x_nom", ctypes.c_void_p), ("ld_x_nom", ctypes.c_int64),
     ]
 
 
@@ -299,6 +311,13 @@ SIGNATURES = [
     ("mhpc_export_results_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _IP,
                                                   ctypes.POINTER(ResultsOut), ctypes.c_int,
                                                   ctypes.c_void_p]),
+    ("mhpc_num_plan_steps", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_int)]),
+    ("mhpc_import_plan_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _IP, _IP, ctypes.c_int,
+                                               ctypes.c_int, ctypes.POINTER(PlanIn), ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    ("mhpc_import_plan", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _IP, _IP, ctypes.c_int,
+                                        ctypes.c_int, _DP, _DP, _DP]),
     ("mhpc_destroy", None, [ctypes.c_void_p]),
     ("mhpc_kernel_name", ctypes.c_char_p, [ctypes.c_int]),
     ("mhpc_set_profiling", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),

@@ -31,6 +31,13 @@ int api_export_plan_device(Handle* h, int n, const int32_t* problems, const int3
                            int window, const mhpc_plan_out* out, int dtype, void* stream, float* ms);
 int api_export_results_device(Handle* h, int n, const int32_t* problems,
                               const mhpc_results_out* out, int dtype, void* stream);
+int api_num_plan_steps(Handle* h, int b, int scope, int* n);
+int api_import_plan_device(Handle* h, int n, const int32_t* problems, const int32_t* first_step,
+                           int window, int scope, const mhpc_plan_in* in, int dtype, void* stream,
+                           float* ms);
+int api_import_plan(Handle* h, int n, const int32_t* problems, const int32_t* first_step,
+                    int window, int scope, const double* u_nom, const double* K,
+                    const double* x_nom);
 int api_get_cost_gradients(Handle* h, int phase, int first, int count, double* lx, double* Phix);
 int api_update_problem(Handle* h, const mhpc_gait* gait);
 int api_update_problems(Handle* h, int n_gaits, const mhpc_gait* gaits, const int32_t* gait_of,

@@ -169,6 +169,20 @@ extern "C" int mhpc_export_results_device(mhpc_handle* h, int n, const int32_t* 
                                           const mhpc_results_out* out, int dtype, void* stream) {
   FWD(export_results_device, n, problems, out, dtype, stream);
 }
+extern "C" int mhpc_num_plan_steps(mhpc_handle* h, int problem, int scope, int* n) {
+  FWD(num_plan_steps, problem, scope, n);
+}
+extern "C" int mhpc_import_plan_device(mhpc_handle* h, int n, const int32_t* problems,
+                                       const int32_t* first_step, int window, int scope,
+                                       const mhpc_plan_in* in, int dtype, void* stream,
+                                       float* ms) {
+  FWD(import_plan_device, n, problems, first_step, window, scope, in, dtype, stream, ms);
+}
+extern "C" int mhpc_import_plan(mhpc_handle* h, int n, const int32_t* problems,
+                                const int32_t* first_step, int window, int scope,
+                                const double* u_nom, const double* K, const double* x_nom) {
+  FWD(import_plan, n, problems, first_step, window, scope, u_nom, K, x_nom);
+}
 extern "C" int mhpc_get_cost_gradients(mhpc_handle* h, int phase, double* lx, double* Phix) {
   FWD(get_cost_gradients, phase, 0, batch_of(h), lx, Phix);
 }

@@ -164,6 +164,18 @@ hipError_t launch_plan_export(const SolveParams& sp, const DevBufs& d, int n, co
 hipError_t launch_results_export(const DevBufs& d, int n, const int* list, int P,
                                  void* const* arrays, int32_t* status, int dtype, hipStream_t s);
 
+// ---- mhpc_plan_import.hip -------------------------------------------------------------------
+// launch_plan_import: `window` steps from first[i] (device, null: 0) of listed problem list[i]
+// (device, null: problem i) out of block i of each given array, by the map of mhpc_import_map.h
+// under `scope`, whose kinds index arrays [NIN] = x_nom, u_nom, K of dtype (u_nom given; x_nom and
+// K both or neither: without them the window knots' gain words become +0) and ld [NIN] (elements
+// between two blocks, >= the dense block).  The host has checked the list and every first step
+// against the same map.
+hipError_t launch_plan_import(const SolveParams& sp, const DevBufs& d, int n, const int* list,
+                              const int* first, int window, int scope, int r,
+                              const void* const* arrays, const long* ld, int dtype,
+                              hipStream_t s);
+
 // ---- mhpc_bws.hip ---------------------------------------------------------------------------
 hipError_t launch_bws(const SolveParams& sp, const DevBufs& d, int al_iter, int ddp_iter, int part,
                       hipStream_t s);

@@ -743,6 +743,22 @@ class Ledger {
     set(fresh_, nfresh_, b, false);
     return no_rollout_due;
   }
+  // mhpc_import_plan(_device) wrote a guess into problem b's nominal: the controls are no longer
+  // the ones its trajectory was rolled out with, so its next solve's first forward_sweep(0) is the
+  // real rollout, as after a gait step.  Same shape as budget_raised.  no_rollout_due (the handle
+  // initialised, nothing solved, no rollout pending): that solve starts with the rollout for b and
+  // with the cost evaluation for everybody else -- all fresh, then b not -- and true is returned:
+  // the caller's solve must start with the rollout.  Otherwise -- a rollout is due anyway (after
+  // mhpc_update_problem(s), an earlier guess), or a solve ran (mhpc_tick_problems rolls out every
+  // problem that is not fresh) -- b only stops being fresh.
+  // `open` is left alone: a problem whose record has no AL iteration never rolls anything out, in
+  // the reference either (MultiPhaseDDP::solve's loop does not run), so its guess stays as written
+  // and its SRB nominal is still the one k_init left.
+  bool guessed(int b, bool no_rollout_due) {
+    if (no_rollout_due) fill(fresh_, nfresh_, true);
+    set(fresh_, nfresh_, b, false);
+    return no_rollout_due;
+  }
 };
 
 }  // namespace MHPC_NS

@@ -15,6 +15,7 @@
 #include "mhpc_control_map.h"
 #include "mhpc_devres.h"
 #include "mhpc_devtemp.h"
+#include "mhpc_import_map.h"
 #include "mhpc_launch.h"
 #include "mhpc_plan.h"
 #include "mhpc_plan_map.h"
@@ -1627,6 +1628,150 @@ int api_export_results_device(Handle* h, int n, const int32_t* problems,
   if ((rc = wait_for_caller(h, stream))) return rc;
   t.e = launch_results_export(h->d, n, dlist, h->sp.pmax, arrays, out->status, dtype, h->main.s1);
   if (t.fetch() != hipSuccess) return dev_fail("mhpc_export_results_device", t.e);  // the sync
+  return MHPC_OK;
+}
+
+// ---- device-resident plan import (k_plan_import: mhpc_plan_import.hip) -----------------------
+int api_num_plan_steps(Handle* h, int b, int scope, int* n) {
+  if (!h || !n) return fail(MHPC_ERR_INVALID, "null argument");
+  if (b < 0 || b >= h->sp.B) return fail(MHPC_ERR_INVALID, "problem out of range");
+  if (!mhpc_import_map::scope_ok(scope))
+    return fail(MHPC_ERR_INVALID, "scope must be MHPC_STEPS_CONTROL or MHPC_STEPS_ALL");
+  const Layout& L = h->plan.lays[h->plan.lid[b]];
+  *n = mhpc_import_map::n_steps(scope, L.P, L.n_wb, L.N);
+  return MHPC_OK;
+}
+// Every check of an import that needs no device: the call order (policy_ready), the list, the
+// window, the scope, each first step against the map the kernel runs on the problem's own layout,
+// which arrays are given and their leading dimensions; ld [NIN]: the strides the kernel gets.
+static int import_ready(const Handle* h, int n, const int32_t* problems, const int32_t* first_step,
+                        int window, int scope, const void* const* arrays, const int64_t* lds,
+                        long* ld) {
+  namespace im = mhpc_import_map;
+  int rc = policy_ready(h);
+  if (rc) return rc;
+  if ((rc = export_list(h, n, problems))) return rc;
+  if (window < 1 || window > MHPC_MAX_KNOTS)
+    return fail(MHPC_ERR_INVALID, "window must be 1..MHPC_MAX_KNOTS");
+  if (!im::scope_ok(scope))
+    return fail(MHPC_ERR_INVALID, "scope must be MHPC_STEPS_CONTROL or MHPC_STEPS_ALL");
+  for (int i = 0; first_step && i < n; ++i) {
+    const Layout& L = h->plan.lays[h->plan.lid[problems ? problems[i] : i]];
+    im::Knot q;
+    if (!im::knot_of(scope, L.P, L.n_wb, L.N, L.ko, first_step[i], &q))
+      return fail(MHPC_ERR_INVALID, "first step outside 0..mhpc_num_plan_steps - 1");
+  }
+  if (!arrays[im::U_NOM]) return fail(MHPC_ERR_INVALID, "null u_nom");
+  if (arrays[im::GAIN] && !arrays[im::X_NOM])
+    return fail(MHPC_ERR_INVALID, "K without x_nom: the gains act on x - x_nom");
+  if (arrays[im::X_NOM] && !arrays[im::GAIN])
+    return fail(MHPC_ERR_INVALID, "x_nom without K");
+  const int r = x0_row_of(h->plan);
+  const char* names[im::NIN] = {"x_nom", "u_nom", "K"};
+  for (int k = 0; k < im::NIN; ++k) {
+    const long dense = im::block(k, r, window);
+    ld[k] = dense;
+    if (!arrays[k]) continue;
+    if (lds[k] != 0 && lds[k] < dense)
+      return fail(MHPC_ERR_INVALID, std::string("ld_") + names[k] + " below the dense block");
+    if (lds[k] != 0) ld[k] = (long)lds[k];
+  }
+  return MHPC_OK;
+}
+// The ledger's side of a finished import (Ledger::guessed): the listed problems' next first sweep
+// is the real rollout.
+static void import_done(Handle* h, int n, const int32_t* problems) {
+  for (int i = 0; i < n; ++i)
+    if (h->led.guessed(problems ? problems[i] : i, !h->need_full && !h->solved && h->initialized))
+      h->need_full = true;
+}
+
+int api_import_plan_device(Handle* h, int n, const int32_t* problems, const int32_t* first_step,
+                           int window, int scope, const mhpc_plan_in* in, int dtype, void* stream,
+                           float* ms) {
+  namespace im = mhpc_import_map;
+  if (!h || !in) return fail(MHPC_ERR_INVALID, "null argument");
+  const void* arrays[im::NIN];
+  int64_t lds[im::NIN];
+  arrays[im::X_NOM] = in->x_nom, lds[im::X_NOM] = in->ld_x_nom;
+  arrays[im::U_NOM] = in->u_nom, lds[im::U_NOM] = in->ld_u_nom;
+  arrays[im::GAIN] = in->K, lds[im::GAIN] = in->ld_K;
+  long ld[im::NIN];
+  int rc = import_ready(h, n, problems, first_step, window, scope, arrays, lds, ld);
+  if (rc) return rc;
+  if ((rc = check_dev_dtype(dtype))) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  const char* names[im::NIN] = {"x_nom", "u_nom", "K"};
+  for (int k = 0; k < im::NIN; ++k)
+    if (arrays[k] && (rc = check_device_ptr(h, arrays[k], names[k]))) return rc;
+  // the list and the first steps: temporaries of this call, no array of the handle
+  DevTemp<int> t(h->main.s1);
+  const int* dlist = problems ? t.in(std::vector<int>(problems, problems + n)) : nullptr;
+  const int* dfirst = first_step ? t.in(std::vector<int>(first_step, first_step + n)) : nullptr;
+  if (t.e != hipSuccess) return dev_fail("mhpc_import_plan_device", t.e);
+  if ((rc = wait_for_caller(h, stream))) return rc;
+  // ---- nothing of the handle or the device has changed up to here ----
+  timed_launch(h, t, ms, [&] {
+    return launch_plan_import(h->sp, h->d, n, dlist, dfirst, window, scope, x0_row_of(h->plan),
+                              arrays, ld, dtype, h->main.s1);
+  });
+  if (t.e != hipSuccess) return dev_fail("mhpc_import_plan_device", t.e);
+  import_done(h, n, problems);
+  return MHPC_OK;
+}
+
+// Host flavour: dense double arrays staged through device temporaries of double, the same kernel.
+int api_import_plan(Handle* h, int n, const int32_t* problems, const int32_t* first_step,
+                    int window, int scope, const double* u_nom, const double* K,
+                    const double* x_nom) {
+  namespace im = mhpc_import_map;
+  if (!h) return fail(MHPC_ERR_INVALID, "null handle");
+  const void* arrays[im::NIN];
+  arrays[im::X_NOM] = x_nom, arrays[im::U_NOM] = u_nom, arrays[im::GAIN] = K;
+  const int64_t lds[im::NIN] = {0, 0, 0};
+  long ld[im::NIN];
+  int rc = import_ready(h, n, problems, first_step, window, scope, arrays, lds, ld);
+  if (rc) return rc;
+  // every entry the kernel would read is finite (rows past a problem's valid steps and columns
+  // past a step's state size are not read)
+  const int r = x0_row_of(h->plan);
+  const double* host[im::NIN] = {x_nom, u_nom, K};
+  for (int i = 0; i < n; ++i) {
+    const Layout& L = h->plan.lays[h->plan.lid[problems ? problems[i] : i]];
+    const int first = first_step ? first_step[i] : 0;
+    const int nvalid = im::valid(im::n_steps(scope, L.P, L.n_wb, L.N), first, window);
+    for (int w = 0; w < nvalid; ++w) {
+      im::Knot q;
+      im::knot_of(scope, L.P, L.n_wb, L.N, L.ko, first + w, &q);
+      for (int k = 0; k < im::NIN; ++k) {
+        if (!host[k]) continue;
+        const int nc = im::cols(k, r);
+        const double* row = host[k] + (size_t)i * ld[k] + (size_t)w * nc;
+        for (int c = 0; c < nc; ++c) {
+          const bool read = k == im::U_NOM || (k == im::X_NOM ? c : c % r) < q.n;
+          if (read && !std::isfinite(row[c]))
+            return fail(MHPC_ERR_INVALID, "u_nom, K and x_nom must be finite");
+        }
+      }
+    }
+  }
+  HIPCHK(hipSetDevice(h->device));
+  DevTemp<int> t(h->main.s1);
+  DevTemp<double> td(h->main.s1);
+  const int* dlist = problems ? t.in(std::vector<int>(problems, problems + n)) : nullptr;
+  const int* dfirst = first_step ? t.in(std::vector<int>(first_step, first_step + n)) : nullptr;
+  const void* dev[im::NIN];
+  for (int k = 0; k < im::NIN; ++k)
+    dev[k] = host[k] ? td.in(host[k], (size_t)n * ld[k]) : nullptr;
+  if (t.e != hipSuccess) return dev_fail("mhpc_import_plan", t.e);
+  if (td.e != hipSuccess) return dev_fail("mhpc_import_plan", td.e);
+  // ---- nothing of the handle or the device has changed up to here ----
+  timed_launch(h, t, nullptr, [&] {
+    return launch_plan_import(h->sp, h->d, n, dlist, dfirst, window, scope, r, dev, ld,
+                              MHPC_DEV_F64, h->main.s1);
+  });
+  if (t.e != hipSuccess) return dev_fail("mhpc_import_plan", t.e);
+  import_done(h, n, problems);
   return MHPC_OK;
 }
 

@@ -1218,6 +1218,91 @@ class MHPCLocomotion:
             "mhpc_export_results_device")
         return res
 
+    # -- device-resident plan import: warm-start listed problems from tensors --------------------
+    @staticmethod
+    def _scope_code(scope):
+        codes = {"control": capi.MHPC_STEPS_CONTROL, "all": capi.MHPC_STEPS_ALL}
+        if scope not in codes:
+            raise ValueError('scope must be "control" or "all"')
+        return codes[scope]
+
+    def num_plan_steps(self, b: int = 0, scope="control") -> int:
+        """Steps of problem b under a scope (mhpc_num_plan_steps): "control" the control steps of
+        num_control_steps, "all" every phase in order, N[p] - 1 steps a phase."""
+        import ctypes
+        n = ctypes.c_int(0)
+        capi.check(capi.lib().mhpc_num_plan_steps(self._h, int(b), self._scope_code(scope),
+                                                  ctypes.byref(n)), "mhpc_num_plan_steps")
+        return n.value
+
+    def import_plan(self, problems=None, first_step=0, u_nom=None, K=None, x_nom=None,
+                    scope="control"):
+        """Start the listed problems from a guess: u_nom [n][W][4] overwrites the nominal controls
+        of problems[i] (None: the whole batch in order) at steps first_step (an int, or one per
+        listed problem) .. first_step + W - 1 of the scope's step map; with K [n][W][4][r] and
+        x_nom [n][W][r] (both or neither) the gains and the nominal states they refer to as well,
+        without them the written knots' gains become +0 (an open-loop guess).  Rows past a
+        problem's steps and columns past a step's state size are ignored.  The next solve or tick
+        of the listed problems starts with the real rollout of the guess from x0, as after
+        update_problem(); nothing else changes.  scope "control": the steps of control() and
+        export_plan(), so an exported window goes back as it is; "all": every phase in order (6
+        columns in an SRB phase).  The arrays: torch tensors on the handle's device, float32 or
+        float64 alike, inner-contiguous views with any leading stride >= the block
+        (mhpc_import_plan_device, on the current torch stream's order; values are not inspected),
+        or numpy arrays (mhpc_import_plan; non-finite entries are refused).  The device time of a
+        tensor import is left in self.last_import_ms."""
+        import ctypes
+        code = self._scope_code(scope)
+        if u_nom is None:
+            raise ValueError("u_nom is required")
+        if (K is None) != (x_nom is None):
+            raise ValueError("K and x_nom go together: the gains act on x - x_nom")
+        lst, n = self._export_list(problems)
+        given = {"u_nom": u_nom, "K": K, "x_nom": x_nom}
+        given = {k: v for k, v in given.items() if v is not None}
+        if u_nom.ndim != 3:
+            raise ValueError("u_nom must be [n][W][4]")
+        W = int(u_nom.shape[1])
+        if W < 1 or W > capi.MHPC_MAX_KNOTS:
+            raise ValueError("window must be 1..MHPC_MAX_KNOTS")
+        fs = np.asarray(first_step)
+        if not np.issubdtype(fs.dtype, np.integer) or fs.ndim > 1:
+            raise ValueError("first_step must be an int or one int per listed problem")
+        fs = np.full(n, int(fs)) if fs.ndim == 0 else fs
+        if fs.shape != (n,):
+            raise ValueError("first_step must be an int or one int per listed problem")
+        fs = np.ascontiguousarray(fs, dtype=np.int32) if fs.any() else None  # (None: step 0)
+        r = self._x0_row()
+        shapes = {"u_nom": (n, W, 4), "K": (n, W, 4, r), "x_nom": (n, W, r)}
+        L = capi.lib()
+        if all(isinstance(v, np.ndarray) for v in given.values()):
+            host = {}
+            for k, v in given.items():
+                if v.shape != shapes[k]:
+                    raise ValueError(f"{k} must be {list(shapes[k])}")
+                host[k] = np.ascontiguousarray(v, dtype=np.float64)
+            capi.check(L.mhpc_import_plan(self._h, n, capi.iptr(lst), capi.iptr(fs), W, code,
+                                          capi.dptr(host["u_nom"]), capi.dptr(host.get("K")),
+                                          capi.dptr(host.get("x_nom"))), "mhpc_import_plan")
+            return
+        import torch
+        if not isinstance(u_nom, torch.Tensor):
+            raise ValueError("u_nom, K and x_nom must be all torch tensors or all numpy arrays")
+        if u_nom.dtype not in (torch.float32, torch.float64):
+            raise ValueError("u_nom must be float32 or float64")
+        pi = capi.PlanIn()
+        for k, v in given.items():
+            ptr, ld = self._device_block(v, shapes[k], u_nom.dtype, k)
+            setattr(pi, k, ptr)
+            setattr(pi, "ld_" + k, ld)
+        ms = ctypes.c_float(0)
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        capi.check(L.mhpc_import_plan_device(
+            self._h, n, capi.iptr(lst), capi.iptr(fs), W, code, ctypes.byref(pi),
+            capi.MHPC_DEV_F32 if u_nom.dtype == torch.float32 else capi.MHPC_DEV_F64, stream,
+            ctypes.byref(ms)), "mhpc_import_plan_device")
+        self.last_import_ms = ms.value
+
     def get_x0(self) -> np.ndarray:
         """The device's current initial states [batch][r] (mhpc_get_x0)."""
         x0 = np.zeros((self.batch, self._x0_row()))

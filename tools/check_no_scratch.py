@@ -12,7 +12,8 @@ import re
 import sys
 
 HOT = ("k_rollout", "k_bws", "k_partials", "k_init", "k_cost", "k_al_end", "k_copy_problems",
-       "k_control", "k_x0_in")  # the last two: the per-tick control I/O (mhpc_control.hip)
+       "k_control", "k_x0_in",  # these two: the per-tick control I/O (mhpc_control.hip)
+       "k_plan_import")  # the plan import (mhpc_plan_import.hip)
 COLD = ("k_cost_grad",)  # debug-info kernel (print_debugInfo), not in the solve
 
 
