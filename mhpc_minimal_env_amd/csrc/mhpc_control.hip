@@ -4,10 +4,11 @@
 //
 // k_control: one knot of forward_sweep_dynamics_only (SinglePhase.cpp:117-144),
 // u = u_nom + K (x - x_nom), for every problem at a control step of its own (the step map is
-// mhpc_control_map.h).  Exactly serial_rollout's control law (mhpc_kernels.hip) at that knot with
-// a run-time step size of +0: (u_nom[i] + eps du[i]) + fb_dot<n>(K row i, x, x_nom), the same
-// fb_dot, so the result equals, bit for bit, what a policy rollout reports for the knot when the
-// state is the one the rollout had there (tests/test_gpu_control.py).  Launched like the rollouts'
+// mhpc_step_map.h under STEPS_CONTROL).  Exactly serial_rollout's control law (mhpc_kernels.hip)
+// at that knot with a run-time step size of +0: (u_nom[i] + eps du[i]) + fb_dot<n>(K row i, x,
+// x_nom), the same fb_dot, so the result equals, bit for bit, what a policy rollout reports for
+// the knot when the state is the one the rollout had there (tests/test_gpu_control.py).  Launched
+// like the rollouts'
 // lane_item(sp, d, 4, ...): blocks group by group, lane = (problem, control row i), the layout
 // from the group record through scalar loads; the four lanes of a problem read its 56 contiguous
 // gain words and each does one fb_dot.  The optional x_nom / u_nom / K outputs are stored by the
@@ -24,15 +25,16 @@
 //
 // In its own translation unit: the neighbours of the solve's kernels stay as they are (the fp32
 // build's results are pinned to their code generation).
-#include "mhpc_control_map.h"
+#include "mhpc_step_map.h"
 #include "mhpc_device.h"
 #include "mhpc_launch.h"
 
 namespace MHPC_NS {
 
-static_assert(mhpc_ctrl::KS == KS && mhpc_ctrl::KW == 56 && mhpc_ctrl::UW == 4 &&
-                  mhpc_ctrl::XW == 14,
-              "mhpc_control_map.h restates the record widths of mhpc_solver.h");
+namespace sm = mhpc_steps;
+
+static_assert(sm::KS == KS && sm::KW == 56 && sm::UW == 4 && sm::XW == 14,
+              "mhpc_step_map.h restates the record widths of mhpc_solver.h");
 
 template <class T>
 struct ControlArgs {
@@ -62,13 +64,13 @@ __global__ __launch_bounds__(64) void k_control(SolveParams sp, DevBufs d, Contr
   int g, b, i;
   if (!lane_item(sp, d, 4, &g, &b, &i)) return;
   const Layout& L = layout_of(d, g);
-  const int n = mhpc_ctrl::state_size(L.n_wb);
-  mhpc_ctrl::Knot q;
-  if (!mhpc_ctrl::knot_of(L.P, L.n_wb, L.N, L.ko, a.step ? a.step[b] : 0, &q)) return;
-  const real* nk = d.traj + mhpc_ctrl::nom_off(sp.NK, sp.nslot, b, d.st[b].nom_slot, q.kk);
-  const real* Kk = d.K + mhpc_ctrl::gain_off(sp.NK, b, q.kk);
+  const int n = sm::control_state(L.n_wb);
+  sm::Knot q;
+  if (!sm::knot_of(sm::STEPS_CONTROL, L.P, L.n_wb, L.N, L.ko, a.step ? a.step[b] : 0, &q)) return;
+  const real* nk = d.traj + sm::nom_off(sp.NK, sp.nslot, b, d.st[b].nom_slot, q.kk);
+  const real* Kk = d.K + sm::gain_off(sp.NK, b, q.kk);
   if (a.u) {
-    const real* duk = d.du + mhpc_ctrl::du_off(sp.NK, b, q.kk);
+    const real* duk = d.du + sm::du_off(sp.NK, b, q.kk);
     const T* xr = a.x + (size_t)b * a.ldx;
     const real u = n == 14 ? control_row<14>(nk, Kk, duk, xr, a.eps, i)
                            : control_row<6>(nk, Kk, duk, xr, a.eps, i);
@@ -91,7 +93,7 @@ __global__ __launch_bounds__(256) void k_x0_in(SolveParams sp, DevBufs d, const 
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
   if (t >= (long)sp.B * 14) return;
   const int b = (int)(t / 14), c = (int)(t - (long)b * 14);
-  const int n = mhpc_ctrl::state_size(((CGroup*)d.grp + d.lid[b])->lay.n_wb);
+  const int n = sm::control_state(((CGroup*)d.grp + d.lid[b])->lay.n_wb);
   d.x0[t] = c < n ? (real)x0[(size_t)b * ld + c] : real(0.0);
 }
 

@@ -140,9 +140,9 @@ hipError_t launch_set_options(const DevBufs& d, int* oid, int n, const int* ent,
 // ---- mhpc_control.hip -----------------------------------------------------------------------
 // Control I/O through device arrays of the caller's element type (dtype MHPC_DEV_F64 / _F32).
 // launch_control: u = u_nom + K (x - x_nom) at control step step[b] of every problem (step on the
-// device, null: step 0; the step map is mhpc_control_map.h and the host has checked every step
-// against it).  x rows at a stride of ldx, u rows at ldu, in elements; x_nom [B][r], u_nom [B][4],
-// K [B][4][r] dense; every output may be null, x only when u is.
+// device, null: step 0; the step map is mhpc_step_map.h under STEPS_CONTROL and the host has
+// checked every step against it).  x rows at a stride of ldx, u rows at ldu, in elements; x_nom
+// [B][r], u_nom [B][4], K [B][4][r] dense; every output may be null, x only when u is.
 hipError_t launch_control(const SolveParams& sp, const DevBufs& d, const int* step, const void* x,
                           long ldx, void* u, long ldu, void* x_nom, void* u_nom, void* K, int r,
                           int dtype, hipStream_t s);
@@ -153,9 +153,9 @@ hipError_t launch_x0_in(const SolveParams& sp, const DevBufs& d, const void* x0,
 // ---- mhpc_plan_export.hip -------------------------------------------------------------------
 // launch_plan_export: `window` control steps from first[i] (device, null: 0) of listed problem
 // list[i] (device, null: problem i) into block i of each wanted array, by the map of
-// mhpc_plan_map.h, whose kinds index arrays [NKIND] (null: not wanted; all of dtype but mode,
-// int32) and ld [NKIND] (elements between two blocks, >= the dense block); valid [n] may be null.
-// The host has checked the list and every first step against the same map.
+// mhpc_step_map.h under STEPS_CONTROL, whose kinds index arrays [NOUT] (null: not wanted; all of
+// dtype but mode, int32) and ld [NOUT] (elements between two blocks, >= the dense block); valid
+// [n] may be null.  The host has checked the list and every first step against the same map.
 hipError_t launch_plan_export(const SolveParams& sp, const DevBufs& d, int n, const int* list,
                               const int* first, int window, int r, void* const* arrays,
                               const long* ld, int32_t* valid, int dtype, hipStream_t s);
@@ -166,7 +166,7 @@ hipError_t launch_results_export(const DevBufs& d, int n, const int* list, int P
 
 // ---- mhpc_plan_import.hip -------------------------------------------------------------------
 // launch_plan_import: `window` steps from first[i] (device, null: 0) of listed problem list[i]
-// (device, null: problem i) out of block i of each given array, by the map of mhpc_import_map.h
+// (device, null: problem i) out of block i of each given array, by the map of mhpc_step_map.h
 // under `scope`, whose kinds index arrays [NIN] = x_nom, u_nom, K of dtype (u_nom given; x_nom and
 // K both or neither: without them the window knots' gain words become +0) and ld [NIN] (elements
 // between two blocks, >= the dense block).  The host has checked the list and every first step

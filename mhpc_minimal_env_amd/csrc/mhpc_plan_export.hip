@@ -4,12 +4,13 @@
 //
 // k_plan_export: for each listed problem, W consecutive control steps from a first step of its
 // own -- x_nom, u_nom, K, du, Vx, y and the step's mode -- into the caller's [n][W][c] blocks.
-// Pure memory traffic, list-driven: a block per (listed problem, chunk of PE_CH window rows), so
+// Pure memory traffic, list-driven: a block per (listed problem, chunk of PW_CH window rows), so
 // no block spans two problems and device work follows the list, never the batch.  The problem is
-// block-uniform: its list entry, first step, group record d.grp[d.lid[b]] and nominal slot are
-// read through scalar loads.  Per wanted array the block's lanes stride over the chunk's output
-// elements, consecutive lanes storing consecutive elements (whole lines per store instruction);
-// the source of each element is what mhpc_plan_map.h names, contiguous inside a phase too (K: 4 n
+// block-uniform (window_block, mhpc_plan_window.h, shared with the import): its list entry, first
+// step, group record d.grp[d.lid[b]] and nominal slot are read through scalar loads.  Per wanted
+// array the block's lanes stride over the chunk's output elements, consecutive lanes storing
+// consecutive elements (whole lines per store instruction);
+// the source of each element is what mhpc_step_map.h names, contiguous inside a phase too (K: 4 n
 // of a knot's 56 words, knots adjacent).  The map's knot_of visits every control phase, so lanes
 // of different rows run the same instructions.  Rows past `valid` and columns past the state size
 // are stored as +0; nothing is stored outside a listed problem's [W][c] block.  The only
@@ -25,19 +26,13 @@
 //
 // In its own translation unit: the neighbours of the solve's kernels stay as they are (the fp32
 // build's results are pinned to their code generation).
-#include "mhpc_plan_map.h"
-#include "mhpc_device.h"
+#include "mhpc_plan_window.h"
 #include "mhpc_launch.h"
 
 namespace MHPC_NS {
 
-namespace pm = mhpc_plan_map;
-
-static_assert(mhpc_ctrl::KS == KS && mhpc_ctrl::KW == 56 && mhpc_ctrl::UW == 4 && pm::GW == 14,
-              "mhpc_control_map.h / mhpc_plan_map.h restate the record widths of mhpc_solver.h");
-
-constexpr int PE_CH = 16;  // window rows a block serves (K: 16 rows of 4 r elements, 3.5 passes)
-constexpr int PE_NT = 256;
+static_assert(sm::KS == KS && sm::KW == 56 && sm::UW == 4 && sm::GW == 14,
+              "mhpc_step_map.h restates the record widths of mhpc_solver.h");
 
 template <class T>
 struct PlanArgs {
@@ -45,62 +40,36 @@ struct PlanArgs {
   const int* first;  // [n] first step of each (null: 0)
   int window, r;
   T *x_nom, *u_nom, *K, *du, *Vx, *y;  // each may be null
-  long ld[pm::NKIND];                  // elements between two listed problems' blocks
+  long ld[sm::NOUT];                   // elements between two listed problems' blocks
   int32_t *mode, *valid;
 };
 
-// One kind's share of a block: output elements [w0, w1) x cols of listed problem i.
+// One kind's share of a block: output elements [w0, w1) x cols of the block's listed problem.
 template <int KIND, class T, class S>
-static __device__ __forceinline__ void export_kind(T* out, long ld, const S* src, const int* mode,
-                                                   int r, const pm::Lay& L, const pm::Dims& D,
-                                                   int i, int b, int slot, int first, int nvalid,
-                                                   int w0, int w1) {
-  const int nc = pm::cols(KIND, r);
-  T* o = out + (size_t)i * (size_t)ld;
-  for (long e = (long)w0 * nc + threadIdx.x; e < (long)w1 * nc; e += PE_NT) {
-    const pm::Elem q = pm::elem(KIND, r, L, D, b, slot, first, nvalid, e);
-    if constexpr (KIND == pm::MODE)
-      o[e] = q.zero ? T(0) : (T)mode[q.src];
-    else
-      o[e] = q.zero ? T(0) : (T)src[q.src];
+static __device__ __forceinline__ void export_kind(T* out, long ld, const S* src, int r,
+                                                   const WindowBlock& k) {
+  const int nc = sm::cols(KIND, r);
+  T* o = out + (size_t)k.i * (size_t)ld;
+  for (long e = (long)k.w0 * nc + threadIdx.x; e < (long)k.w1 * nc; e += PW_NT) {
+    const sm::Elem q =
+        sm::elem(sm::STEPS_CONTROL, KIND, r, k.L, k.D, k.b, k.slot, k.first, k.nvalid, e);
+    o[e] = q.skip ? T(0) : (T)src[q.off];
   }
 }
 
 template <class T>
-__global__ __launch_bounds__(PE_NT) void k_plan_export(SolveParams sp, DevBufs d, PlanArgs<T> a,
+__global__ __launch_bounds__(PW_NT) void k_plan_export(SolveParams sp, DevBufs d, PlanArgs<T> a,
                                                        int nch) {
-  const int i = blockIdx.x / nch, w0 = (int)(blockIdx.x % nch) * PE_CH;
-  const int w1 = min(w0 + PE_CH, a.window);
-  const int b = a.list ? a.list[i] : i;
-  const int first = a.first ? a.first[i] : 0;
-  const Layout& Ly = layout_of(d, d.lid[b]);
-  const pm::Lay L = {Ly.P, Ly.n_wb, Ly.N, Ly.ko};
-  const pm::Dims D = {sp.NK, sp.nslot};
-  const int slot = d.st[b].nom_slot;
-  const int nvalid = pm::valid(mhpc_ctrl::n_steps(L.P, L.n_wb, L.N), first, a.window);
-  if (a.valid && w0 == 0 && threadIdx.x == 0) a.valid[i] = nvalid;
+  const WindowBlock k = window_block(sp, d, a.list, a.first, a.window, sm::STEPS_CONTROL, nch);
+  if (a.valid && k.w0 == 0 && threadIdx.x == 0) a.valid[k.i] = k.nvalid;
   const int r = a.r;
-  if (a.x_nom)
-    export_kind<pm::X_NOM>(a.x_nom, a.ld[pm::X_NOM], d.traj, nullptr, r, L, D, i, b, slot, first,
-                           nvalid, w0, w1);
-  if (a.u_nom)
-    export_kind<pm::U_NOM>(a.u_nom, a.ld[pm::U_NOM], d.traj, nullptr, r, L, D, i, b, slot, first,
-                           nvalid, w0, w1);
-  if (a.K)
-    export_kind<pm::GAIN>(a.K, a.ld[pm::GAIN], d.K, nullptr, r, L, D, i, b, slot, first, nvalid,
-                          w0, w1);
-  if (a.du)
-    export_kind<pm::DU>(a.du, a.ld[pm::DU], d.du, nullptr, r, L, D, i, b, slot, first, nvalid, w0,
-                        w1);
-  if (a.Vx)
-    export_kind<pm::VX>(a.Vx, a.ld[pm::VX], d.G, nullptr, r, L, D, i, b, slot, first, nvalid, w0,
-                        w1);
-  if (a.y)
-    export_kind<pm::Y>(a.y, a.ld[pm::Y], d.traj, nullptr, r, L, D, i, b, slot, first, nvalid, w0,
-                       w1);
-  if (a.mode)
-    export_kind<pm::MODE>(a.mode, a.ld[pm::MODE], (const int*)nullptr, Ly.mode, r, L, D, i, b,
-                          slot, first, nvalid, w0, w1);
+  if (a.x_nom) export_kind<sm::X_NOM>(a.x_nom, a.ld[sm::X_NOM], d.traj, r, k);
+  if (a.u_nom) export_kind<sm::U_NOM>(a.u_nom, a.ld[sm::U_NOM], d.traj, r, k);
+  if (a.K) export_kind<sm::GAIN>(a.K, a.ld[sm::GAIN], d.K, r, k);
+  if (a.du) export_kind<sm::DU>(a.du, a.ld[sm::DU], d.du, r, k);
+  if (a.Vx) export_kind<sm::VX>(a.Vx, a.ld[sm::VX], d.G, r, k);
+  if (a.y) export_kind<sm::Y>(a.y, a.ld[sm::Y], d.traj, r, k);
+  if (a.mode) export_kind<sm::MODE>(a.mode, a.ld[sm::MODE], k.mode, r, k);
 }
 
 template <class T>
@@ -148,17 +117,17 @@ static hipError_t launch_plan_export_t(const SolveParams& sp, const DevBufs& d, 
   a.first = first;
   a.window = window;
   a.r = r;
-  a.x_nom = (T*)arrays[pm::X_NOM];
-  a.u_nom = (T*)arrays[pm::U_NOM];
-  a.K = (T*)arrays[pm::GAIN];
-  a.du = (T*)arrays[pm::DU];
-  a.Vx = (T*)arrays[pm::VX];
-  a.y = (T*)arrays[pm::Y];
-  a.mode = (int32_t*)arrays[pm::MODE];
+  a.x_nom = (T*)arrays[sm::X_NOM];
+  a.u_nom = (T*)arrays[sm::U_NOM];
+  a.K = (T*)arrays[sm::GAIN];
+  a.du = (T*)arrays[sm::DU];
+  a.Vx = (T*)arrays[sm::VX];
+  a.y = (T*)arrays[sm::Y];
+  a.mode = (int32_t*)arrays[sm::MODE];
   a.valid = valid;
-  for (int k = 0; k < pm::NKIND; ++k) a.ld[k] = ld[k];
-  const int nch = (window + PE_CH - 1) / PE_CH;
-  hipLaunchKernelGGL(k_plan_export<T>, dim3((unsigned)n * nch), dim3(PE_NT), 0, s, sp, d, a, nch);
+  for (int k = 0; k < sm::NOUT; ++k) a.ld[k] = ld[k];
+  const int nch = window_chunks(window);
+  hipLaunchKernelGGL(k_plan_export<T>, dim3((unsigned)n * nch), dim3(PW_NT), 0, s, sp, d, a, nch);
   return hipGetLastError();
 }
 

@@ -4,12 +4,13 @@
 // k_plan_import mirrors k_plan_export (mhpc_plan_export.hip) in the other direction: for each
 // listed problem, W consecutive steps from a first step of its own -- u_nom, and optionally x_nom
 // and K -- out of the caller's [n][W][c] blocks.  Pure memory traffic, list-driven: a block per
-// (listed problem, chunk of PI_CH window rows), so no block spans two problems and device work
-// follows the list, never the batch.  The problem is block-uniform: its list entry, first step,
-// group record d.grp[d.lid[b]] and nominal slot are read through scalar loads.  Per given array
+// (listed problem, chunk of PW_CH window rows), so no block spans two problems and device work
+// follows the list, never the batch.  The problem is block-uniform (window_block,
+// mhpc_plan_window.h, shared with the export): its list entry, first step, group record
+// d.grp[d.lid[b]] and nominal slot are read through scalar loads.  Per given array
 // the block's lanes stride over the chunk's input elements, consecutive lanes loading consecutive
 // elements (whole lines per load instruction); the destination of each element is what
-// mhpc_import_map.h names, contiguous inside a phase too.  The map's knot_of visits every phase of
+// mhpc_step_map.h names, contiguous inside a phase too.  The map's knot_of visits every phase of
 // the scope, so lanes of different rows run the same instructions.  Rows past `valid` and columns
 // past the step's state size are not read; nothing is stored outside the named entries of a
 // listed problem's window knots (never y, du, G, another trajectory slot, the partials or the
@@ -23,19 +24,13 @@
 //
 // In its own translation unit: the neighbours of the solve's kernels stay as they are (the fp32
 // build's results are pinned to their code generation).
-#include "mhpc_import_map.h"
-#include "mhpc_device.h"
+#include "mhpc_plan_window.h"
 #include "mhpc_launch.h"
 
 namespace MHPC_NS {
 
-namespace im = mhpc_import_map;
-
-static_assert(mhpc_ctrl::KS == KS && mhpc_ctrl::KW == 56 && mhpc_ctrl::UW == 4,
-              "mhpc_control_map.h / mhpc_import_map.h restate the record widths of mhpc_solver.h");
-
-constexpr int PI_CH = 16;  // window rows a block serves (K: 16 rows of 4 r elements, 3.5 passes)
-constexpr int PI_NT = 256;
+static_assert(sm::KS == KS && sm::KW == 56 && sm::UW == 4,
+              "mhpc_step_map.h restates the record widths of mhpc_solver.h");
 
 template <class T>
 struct ImportArgs {
@@ -43,50 +38,36 @@ struct ImportArgs {
   const int* first;  // [n] first step of each (null: 0)
   int window, r, scope;
   const T *x_nom, *u_nom, *K;  // x_nom and K may be null (together)
-  long ld[im::NIN];            // elements between two listed problems' blocks
+  long ld[sm::NIN];            // elements between two listed problems' blocks
 };
 
-// One kind's share of a block: input elements [w0, w1) x cols of listed problem i.
+// One kind's share of a block: input elements [w0, w1) x cols of the block's listed problem.
 template <int KIND, class T>
 static __device__ __forceinline__ void import_kind(const T* in, long ld, real* dst, int scope,
-                                                   int r, const im::Lay& L, const im::Dims& D,
-                                                   int i, int b, int slot, int first, int nvalid,
-                                                   int w0, int w1) {
-  const int nc = im::cols(KIND, r);
-  const T* src = KIND == im::ZGAIN ? nullptr : in + (size_t)i * (size_t)ld;
-  for (long e = (long)w0 * nc + threadIdx.x; e < (long)w1 * nc; e += PI_NT) {
-    const im::Elem q = im::elem(scope, KIND, r, L, D, b, slot, first, nvalid, e);
+                                                   int r, const WindowBlock& k) {
+  const int nc = sm::cols(KIND, r);
+  const T* src = KIND == sm::ZGAIN ? nullptr : in + (size_t)k.i * (size_t)ld;
+  for (long e = (long)k.w0 * nc + threadIdx.x; e < (long)k.w1 * nc; e += PW_NT) {
+    const sm::Elem q = sm::elem(scope, KIND, r, k.L, k.D, k.b, k.slot, k.first, k.nvalid, e);
     if (q.skip) continue;
-    if constexpr (KIND == im::ZGAIN)
-      dst[q.dst] = real(0);
+    if constexpr (KIND == sm::ZGAIN)
+      dst[q.off] = real(0);
     else
-      dst[q.dst] = (real)src[e];
+      dst[q.off] = (real)src[e];
   }
 }
 
 template <class T>
-__global__ __launch_bounds__(PI_NT) void k_plan_import(SolveParams sp, DevBufs d, ImportArgs<T> a,
+__global__ __launch_bounds__(PW_NT) void k_plan_import(SolveParams sp, DevBufs d, ImportArgs<T> a,
                                                        int nch) {
-  const int i = blockIdx.x / nch, w0 = (int)(blockIdx.x % nch) * PI_CH;
-  const int w1 = min(w0 + PI_CH, a.window);
-  const int b = a.list ? a.list[i] : i;
-  const int first = a.first ? a.first[i] : 0;
-  const Layout& Ly = layout_of(d, d.lid[b]);
-  const im::Lay L = {Ly.P, Ly.n_wb, Ly.N, Ly.ko};
-  const im::Dims D = {sp.NK, sp.nslot};
-  const int slot = d.st[b].nom_slot;
   const int scope = a.scope, r = a.r;
-  const int nvalid = im::valid(im::n_steps(scope, L.P, L.n_wb, L.N), first, a.window);
-  import_kind<im::U_NOM>(a.u_nom, a.ld[im::U_NOM], d.traj, scope, r, L, D, i, b, slot, first,
-                         nvalid, w0, w1);
+  const WindowBlock k = window_block(sp, d, a.list, a.first, a.window, scope, nch);
+  import_kind<sm::U_NOM>(a.u_nom, a.ld[sm::U_NOM], d.traj, scope, r, k);
   if (a.K) {
-    import_kind<im::X_NOM>(a.x_nom, a.ld[im::X_NOM], d.traj, scope, r, L, D, i, b, slot, first,
-                           nvalid, w0, w1);
-    import_kind<im::GAIN>(a.K, a.ld[im::GAIN], d.K, scope, r, L, D, i, b, slot, first, nvalid, w0,
-                          w1);
+    import_kind<sm::X_NOM>(a.x_nom, a.ld[sm::X_NOM], d.traj, scope, r, k);
+    import_kind<sm::GAIN>(a.K, a.ld[sm::GAIN], d.K, scope, r, k);
   } else {
-    import_kind<im::ZGAIN>((const T*)nullptr, 0, d.K, scope, r, L, D, i, b, slot, first, nvalid,
-                           w0, w1);
+    import_kind<sm::ZGAIN>((const T*)nullptr, 0, d.K, scope, r, k);
   }
 }
 
@@ -101,12 +82,12 @@ static hipError_t launch_plan_import_t(const SolveParams& sp, const DevBufs& d, 
   a.window = window;
   a.r = r;
   a.scope = scope;
-  a.x_nom = (const T*)arrays[im::X_NOM];
-  a.u_nom = (const T*)arrays[im::U_NOM];
-  a.K = (const T*)arrays[im::GAIN];
-  for (int k = 0; k < im::NIN; ++k) a.ld[k] = ld[k];
-  const int nch = (window + PI_CH - 1) / PI_CH;
-  hipLaunchKernelGGL(k_plan_import<T>, dim3((unsigned)n * nch), dim3(PI_NT), 0, s, sp, d, a, nch);
+  a.x_nom = (const T*)arrays[sm::X_NOM];
+  a.u_nom = (const T*)arrays[sm::U_NOM];
+  a.K = (const T*)arrays[sm::GAIN];
+  for (int k = 0; k < sm::NIN; ++k) a.ld[k] = ld[k];
+  const int nch = window_chunks(window);
+  hipLaunchKernelGGL(k_plan_import<T>, dim3((unsigned)n * nch), dim3(PW_NT), 0, s, sp, d, a, nch);
   return hipGetLastError();
 }
 

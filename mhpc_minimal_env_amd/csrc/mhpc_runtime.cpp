@@ -12,14 +12,12 @@
 #include <vector>
 
 #include "../../include/mhpc_capi.h"
-#include "mhpc_control_map.h"
 #include "mhpc_devres.h"
 #include "mhpc_devtemp.h"
-#include "mhpc_import_map.h"
 #include "mhpc_launch.h"
 #include "mhpc_plan.h"
-#include "mhpc_plan_map.h"
 #include "mhpc_snapshot_map.h"
+#include "mhpc_step_map.h"
 
 extern thread_local std::string mhpc_g_err;  // mhpc_capi.cpp (mhpc_last_error)
 
@@ -1409,16 +1407,88 @@ int api_get_x0(Handle* h, double* x0) {
   return MHPC_OK;
 }
 
-// ---- device-resident control I/O (k_control, k_x0_in: mhpc_control.hip) ---------------------
-// Every check of the control entry points that needs no device: the call order (policy_ready),
-// the steps against the map the kernel runs (mhpc_control_map.h) on each problem's own layout.
-static int control_ready(const Handle* h, const int32_t* step) {
-  if (int rc = policy_ready(h)) return rc;
-  for (int b = 0; step && b < h->sp.B; ++b) {
-    const Layout& L = h->plan.lays[h->plan.lid[b]];
-    mhpc_ctrl::Knot q;
-    if (!mhpc_ctrl::knot_of(L.P, L.n_wb, L.N, L.ko, step[b], &q))
-      return fail(MHPC_ERR_INVALID, "control step outside 0..mhpc_num_control_steps - 1");
+// ---- device-resident I/O: the checks and uploads its entry points share ----------------------
+// (control: k_control, k_x0_in, mhpc_control.hip; plan export: k_plan_export, k_results_export,
+// mhpc_plan_export.hip; plan import: k_plan_import, mhpc_plan_import.hip; one map for the three,
+// mhpc_step_map.h)
+namespace sm = mhpc_steps;
+static_assert((int)sm::STEPS_CONTROL == MHPC_STEPS_CONTROL && (int)sm::STEPS_ALL == MHPC_STEPS_ALL,
+              "mhpc_step_map.h restates the scopes of mhpc_capi.h");
+
+static const Layout& problem_layout(const Handle* h, int b) { return h->plan.lays[h->plan.lid[b]]; }
+// steps [n] (null: nothing to check) of problems [n] (null: problem i) against the map the
+// kernels run, each on its problem's own layout; `refusal` is the message of a step outside it
+static int check_steps(const Handle* h, int n, const int32_t* problems, const int32_t* step,
+                       int scope, const char* refusal) {
+  for (int i = 0; step && i < n; ++i) {
+    const Layout& L = problem_layout(h, problems ? problems[i] : i);
+    sm::Knot q;
+    if (!sm::knot_of(scope, L.P, L.n_wb, L.N, L.ko, step[i], &q))
+      return fail(MHPC_ERR_INVALID, refusal);
+  }
+  return MHPC_OK;
+}
+// The list of a plan / results call: problems [n] checked (ProblemList), or null for the whole
+// batch in order (n == batch).
+static int check_list(const Handle* h, int n, const int32_t* problems) {
+  if (!problems) {
+    if (n != h->sp.B) return fail(MHPC_ERR_INVALID, "n must be the batch when problems is null");
+    return MHPC_OK;
+  }
+  ProblemList listed;
+  PLANCHK(listed.begin, n, h->sp.B, false);
+  for (int i = 0; i < n; ++i) PLANCHK(listed.add, problems[i]);
+  return MHPC_OK;
+}
+// A window call, in this order: the list, the window, the scope, every first step.
+static int check_window_call(const Handle* h, int n, const int32_t* problems,
+                             const int32_t* first_step, int window, int scope,
+                             const char* step_refusal) {
+  if (int rc = check_list(h, n, problems)) return rc;
+  if (window < 1 || window > MHPC_MAX_KNOTS)
+    return fail(MHPC_ERR_INVALID, "window must be 1..MHPC_MAX_KNOTS");
+  if (!sm::scope_ok(scope))
+    return fail(MHPC_ERR_INVALID, "scope must be MHPC_STEPS_CONTROL or MHPC_STEPS_ALL");
+  return check_steps(h, n, problems, first_step, scope, step_refusal);
+}
+// The list and the first steps as temporaries of the call (no array of the handle); null for null.
+static void upload_list(DevTemp<int>& t, int n, const int32_t* problems, const int32_t* first_step,
+                        const int** dlist, const int** dfirst) {
+  *dlist = problems ? t.in(std::vector<int>(problems, problems + n)) : nullptr;
+  if (dfirst) *dfirst = first_step ? t.in(std::vector<int>(first_step, first_step + n)) : nullptr;
+}
+
+// One array of the caller's, as an entry point's table lists it: null when not given; ld the
+// elements between two listed problems' blocks (0: dense) of a window block of `kind`
+// (mhpc_step_map.h), kind < 0 for an array that is no window block.
+struct CallerArray {
+  const void* p;
+  int64_t ld;
+  int kind;
+  const char* name;
+};
+static bool any_given(const CallerArray* a, int na) {
+  for (int k = 0; k < na; ++k)
+    if (a[k].p) return true;
+  return false;
+}
+// The table's window blocks as the launchers take them: arrays [by kind].
+template <class P>
+static void arrays_by_kind(const CallerArray* a, int na, P* arrays) {
+  for (int k = 0; k < na; ++k)
+    if (a[k].kind >= 0) arrays[a[k].kind] = const_cast<P>(a[k].p);
+}
+// The strides the kernel gets, ld [by kind]: the dense block, or a given array's own ld, which is
+// at least that.
+static int check_lds(const CallerArray* a, int na, int r, int window, long* ld) {
+  for (int k = 0; k < na; ++k) {
+    if (a[k].kind < 0) continue;
+    const long dense = sm::block(a[k].kind, r, window);
+    ld[a[k].kind] = dense;
+    if (!a[k].p || a[k].ld == 0) continue;
+    if (a[k].ld < dense)
+      return fail(MHPC_ERR_INVALID, std::string("ld_") + a[k].name + " below the dense block");
+    ld[a[k].kind] = (long)a[k].ld;
   }
   return MHPC_OK;
 }
@@ -1433,6 +1503,11 @@ static int check_device_ptr(const Handle* h, const void* p, const char* what) {
   }
   if (at.type != hipMemoryTypeDevice || at.device != h->device)
     return fail(MHPC_ERR_INVALID, std::string(what) + " is not device memory of the handle's device");
+  return MHPC_OK;
+}
+static int check_device_ptrs(const Handle* h, const CallerArray* a, int na) {
+  for (int k = 0; k < na; ++k)
+    if (int rc = a[k].p ? check_device_ptr(h, a[k].p, a[k].name) : MHPC_OK) return rc;
   return MHPC_OK;
 }
 static int check_dev_dtype(int dtype) {
@@ -1461,12 +1536,26 @@ static int upload_steps(Handle* h, const int32_t* step, const int** dstep) {
   return MHPC_OK;
 }
 
-int api_num_control_steps(Handle* h, int b, int* n) {
+// ---- device-resident control I/O (k_control, k_x0_in: mhpc_control.hip) ---------------------
+// Every check of the control entry points that needs no device: the call order (policy_ready),
+// every problem's step.
+static int control_ready(const Handle* h, const int32_t* step) {
+  if (int rc = policy_ready(h)) return rc;
+  return check_steps(h, h->sp.B, nullptr, step, sm::STEPS_CONTROL,
+                     "control step outside 0..mhpc_num_control_steps - 1");
+}
+
+int api_num_plan_steps(Handle* h, int b, int scope, int* n) {
   if (!h || !n) return fail(MHPC_ERR_INVALID, "null argument");
   if (b < 0 || b >= h->sp.B) return fail(MHPC_ERR_INVALID, "problem out of range");
-  const Layout& L = h->plan.lays[h->plan.lid[b]];
-  *n = mhpc_ctrl::n_steps(L.P, L.n_wb, L.N);
+  if (!sm::scope_ok(scope))
+    return fail(MHPC_ERR_INVALID, "scope must be MHPC_STEPS_CONTROL or MHPC_STEPS_ALL");
+  const Layout& L = problem_layout(h, b);
+  *n = sm::n_steps(scope, L.P, L.n_wb, L.N);
   return MHPC_OK;
+}
+int api_num_control_steps(Handle* h, int b, int* n) {
+  return api_num_plan_steps(h, b, sm::STEPS_CONTROL, n);
 }
 
 // Host flavour: the arrays staged through device temporaries of double, the same kernel.
@@ -1505,10 +1594,10 @@ int api_control_device(Handle* h, const int32_t* step, const void* x, int64_t ld
   const int r = x0_row_of(h->plan);
   if (u && (ldx < r || ldu < 4)) return fail(MHPC_ERR_INVALID, "ldx < r or ldu < 4");
   HIPCHK(hipSetDevice(h->device));
-  const void* ptrs[] = {u ? x : nullptr, u, x_nom, u_nom, K};
-  const char* names[] = {"x", "u", "x_nom", "u_nom", "K"};
-  for (int i = 0; i < 5; ++i)
-    if (ptrs[i] && (rc = check_device_ptr(h, ptrs[i], names[i]))) return rc;
+  const CallerArray tab[] = {{u ? x : nullptr, 0, -1, "x"}, {u, 0, -1, "u"},
+                             {x_nom, 0, -1, "x_nom"},       {u_nom, 0, -1, "u_nom"},
+                             {K, 0, -1, "K"}};
+  if ((rc = check_device_ptrs(h, tab, 5))) return rc;
   const int* dstep;
   if ((rc = upload_steps(h, step, &dstep))) return rc;
   if ((rc = wait_for_caller(h, stream))) return rc;
@@ -1534,68 +1623,35 @@ int api_set_x0_device(Handle* h, const void* x0, int64_t ld, int dtype, void* st
 }
 
 // ---- device-resident plan export (k_plan_export, k_results_export: mhpc_plan_export.hip) ----
-// The list of a plan / results export: problems [n] checked (ProblemList), or null for the whole
-// batch in order (n == batch).
-static int export_list(const Handle* h, int n, const int32_t* problems) {
-  if (!problems) {
-    if (n != h->sp.B) return fail(MHPC_ERR_INVALID, "n must be the batch when problems is null");
-    return MHPC_OK;
-  }
-  ProblemList listed;
-  PLANCHK(listed.begin, n, h->sp.B, false);
-  for (int i = 0; i < n; ++i) PLANCHK(listed.add, problems[i]);
-  return MHPC_OK;
-}
-
 int api_export_plan_device(Handle* h, int n, const int32_t* problems, const int32_t* first_step,
                            int window, const mhpc_plan_out* out, int dtype, void* stream,
                            float* ms) {
-  namespace pm = mhpc_plan_map;
   if (!h || !out) return fail(MHPC_ERR_INVALID, "null argument");
   int rc = policy_ready(h);
   if (rc) return rc;
   if ((rc = check_dev_dtype(dtype))) return rc;
-  if ((rc = export_list(h, n, problems))) return rc;
-  if (window < 1 || window > MHPC_MAX_KNOTS)
-    return fail(MHPC_ERR_INVALID, "window must be 1..MHPC_MAX_KNOTS");
-  // every first step against the map the kernel runs, on each problem's own layout
-  for (int i = 0; first_step && i < n; ++i) {
-    const Layout& L = h->plan.lays[h->plan.lid[problems ? problems[i] : i]];
-    mhpc_ctrl::Knot q;
-    if (!mhpc_ctrl::knot_of(L.P, L.n_wb, L.N, L.ko, first_step[i], &q))
-      return fail(MHPC_ERR_INVALID, "first step outside 0..mhpc_num_control_steps - 1");
-  }
+  if ((rc = check_window_call(h, n, problems, first_step, window, sm::STEPS_CONTROL,
+                              "first step outside 0..mhpc_num_control_steps - 1")))
+    return rc;
   const int r = x0_row_of(h->plan);
-  void* arrays[pm::NKIND];
-  int64_t lds[pm::NKIND];
-  arrays[pm::X_NOM] = out->x_nom, lds[pm::X_NOM] = out->ld_x_nom;
-  arrays[pm::U_NOM] = out->u_nom, lds[pm::U_NOM] = out->ld_u_nom;
-  arrays[pm::GAIN] = out->K, lds[pm::GAIN] = out->ld_K;
-  arrays[pm::DU] = out->du, lds[pm::DU] = out->ld_du;
-  arrays[pm::VX] = out->Vx, lds[pm::VX] = out->ld_Vx;
-  arrays[pm::Y] = out->y, lds[pm::Y] = out->ld_y;
-  arrays[pm::MODE] = out->mode, lds[pm::MODE] = out->ld_mode;
-  const char* names[pm::NKIND] = {"x_nom", "u_nom", "K", "du", "Vx", "y", "mode"};
-  long ld[pm::NKIND];
-  bool any = out->valid != nullptr;
-  for (int k = 0; k < pm::NKIND; ++k) {
-    const long dense = pm::block(k, r, window);
-    ld[k] = dense;
-    if (!arrays[k]) continue;
-    any = true;
-    if (lds[k] != 0 && lds[k] < dense)
-      return fail(MHPC_ERR_INVALID, std::string("ld_") + names[k] + " below the dense block");
-    if (lds[k] != 0) ld[k] = (long)lds[k];
-  }
-  if (!any) return fail(MHPC_ERR_INVALID, "no array wanted");
+  const CallerArray tab[sm::NOUT + 1] = {{out->x_nom, out->ld_x_nom, sm::X_NOM, "x_nom"},
+                                         {out->u_nom, out->ld_u_nom, sm::U_NOM, "u_nom"},
+                                         {out->K, out->ld_K, sm::GAIN, "K"},
+                                         {out->du, out->ld_du, sm::DU, "du"},
+                                         {out->Vx, out->ld_Vx, sm::VX, "Vx"},
+                                         {out->y, out->ld_y, sm::Y, "y"},
+                                         {out->mode, out->ld_mode, sm::MODE, "mode"},
+                                         {out->valid, 0, -1, "valid"}};
+  long ld[sm::NOUT];
+  if ((rc = check_lds(tab, sm::NOUT + 1, r, window, ld))) return rc;
+  if (!any_given(tab, sm::NOUT + 1)) return fail(MHPC_ERR_INVALID, "no array wanted");
   HIPCHK(hipSetDevice(h->device));
-  for (int k = 0; k < pm::NKIND; ++k)
-    if (arrays[k] && (rc = check_device_ptr(h, arrays[k], names[k]))) return rc;
-  if (out->valid && (rc = check_device_ptr(h, out->valid, "valid"))) return rc;
-  // the list and the first steps: temporaries of this call, no array of the handle
+  if ((rc = check_device_ptrs(h, tab, sm::NOUT + 1))) return rc;
+  void* arrays[sm::NOUT];
+  arrays_by_kind(tab, sm::NOUT + 1, arrays);
   DevTemp<int> t(h->main.s1);
-  const int* dlist = problems ? t.in(std::vector<int>(problems, problems + n)) : nullptr;
-  const int* dfirst = first_step ? t.in(std::vector<int>(first_step, first_step + n)) : nullptr;
+  const int *dlist, *dfirst;
+  upload_list(t, n, problems, first_step, &dlist, &dfirst);
   if (t.e != hipSuccess) return dev_fail("mhpc_export_plan_device", t.e);
   if ((rc = wait_for_caller(h, stream))) return rc;
   timed_launch(h, t, ms, [&] {
@@ -1612,18 +1668,19 @@ int api_export_results_device(Handle* h, int n, const int32_t* problems,
   int rc = policy_ready(h);
   if (rc) return rc;
   if ((rc = check_dev_dtype(dtype))) return rc;
-  if ((rc = export_list(h, n, problems))) return rc;
-  void* arrays[5] = {out->J, out->dV_exp, out->viol, out->V_phase, out->dV_phase};
-  const char* names[5] = {"J", "dV_exp", "viol", "V_phase", "dV_phase"};
-  bool any = out->status != nullptr;
-  for (int k = 0; k < 5; ++k) any = any || arrays[k];
-  if (!any) return fail(MHPC_ERR_INVALID, "no array wanted");
+  if ((rc = check_list(h, n, problems))) return rc;
+  const CallerArray tab[6] = {  // the launcher's arrays [5], then status
+      {out->J, 0, -1, "J"},       {out->dV_exp, 0, -1, "dV_exp"},
+      {out->viol, 0, -1, "viol"}, {out->V_phase, 0, -1, "V_phase"},
+      {out->dV_phase, 0, -1, "dV_phase"}, {out->status, 0, -1, "status"}};
+  if (!any_given(tab, 6)) return fail(MHPC_ERR_INVALID, "no array wanted");
   HIPCHK(hipSetDevice(h->device));
-  for (int k = 0; k < 5; ++k)
-    if (arrays[k] && (rc = check_device_ptr(h, arrays[k], names[k]))) return rc;
-  if (out->status && (rc = check_device_ptr(h, out->status, "status"))) return rc;
+  if ((rc = check_device_ptrs(h, tab, 6))) return rc;
+  void* arrays[5];
+  for (int k = 0; k < 5; ++k) arrays[k] = const_cast<void*>(tab[k].p);
   DevTemp<int> t(h->main.s1);
-  const int* dlist = problems ? t.in(std::vector<int>(problems, problems + n)) : nullptr;
+  const int* dlist;
+  upload_list(t, n, problems, nullptr, &dlist, nullptr);
   if (t.e != hipSuccess) return dev_fail("mhpc_export_results_device", t.e);
   if ((rc = wait_for_caller(h, stream))) return rc;
   t.e = launch_results_export(h->d, n, dlist, h->sp.pmax, arrays, out->status, dtype, h->main.s1);
@@ -1632,51 +1689,23 @@ int api_export_results_device(Handle* h, int n, const int32_t* problems,
 }
 
 // ---- device-resident plan import (k_plan_import: mhpc_plan_import.hip) -----------------------
-int api_num_plan_steps(Handle* h, int b, int scope, int* n) {
-  if (!h || !n) return fail(MHPC_ERR_INVALID, "null argument");
-  if (b < 0 || b >= h->sp.B) return fail(MHPC_ERR_INVALID, "problem out of range");
-  if (!mhpc_import_map::scope_ok(scope))
-    return fail(MHPC_ERR_INVALID, "scope must be MHPC_STEPS_CONTROL or MHPC_STEPS_ALL");
-  const Layout& L = h->plan.lays[h->plan.lid[b]];
-  *n = mhpc_import_map::n_steps(scope, L.P, L.n_wb, L.N);
-  return MHPC_OK;
-}
-// Every check of an import that needs no device: the call order (policy_ready), the list, the
-// window, the scope, each first step against the map the kernel runs on the problem's own layout,
-// which arrays are given and their leading dimensions; ld [NIN]: the strides the kernel gets.
+// Every check of an import that needs no device: the call order (policy_ready), the window call,
+// which arrays of tab [NIN] are given and their leading dimensions; arrays [NIN] and ld [NIN], by
+// kind: what the kernel gets.
 static int import_ready(const Handle* h, int n, const int32_t* problems, const int32_t* first_step,
-                        int window, int scope, const void* const* arrays, const int64_t* lds,
+                        int window, int scope, const CallerArray* tab, const void** arrays,
                         long* ld) {
-  namespace im = mhpc_import_map;
   int rc = policy_ready(h);
   if (rc) return rc;
-  if ((rc = export_list(h, n, problems))) return rc;
-  if (window < 1 || window > MHPC_MAX_KNOTS)
-    return fail(MHPC_ERR_INVALID, "window must be 1..MHPC_MAX_KNOTS");
-  if (!im::scope_ok(scope))
-    return fail(MHPC_ERR_INVALID, "scope must be MHPC_STEPS_CONTROL or MHPC_STEPS_ALL");
-  for (int i = 0; first_step && i < n; ++i) {
-    const Layout& L = h->plan.lays[h->plan.lid[problems ? problems[i] : i]];
-    im::Knot q;
-    if (!im::knot_of(scope, L.P, L.n_wb, L.N, L.ko, first_step[i], &q))
-      return fail(MHPC_ERR_INVALID, "first step outside 0..mhpc_num_plan_steps - 1");
-  }
-  if (!arrays[im::U_NOM]) return fail(MHPC_ERR_INVALID, "null u_nom");
-  if (arrays[im::GAIN] && !arrays[im::X_NOM])
+  if ((rc = check_window_call(h, n, problems, first_step, window, scope,
+                              "first step outside 0..mhpc_num_plan_steps - 1")))
+    return rc;
+  arrays_by_kind(tab, sm::NIN, arrays);
+  if (!arrays[sm::U_NOM]) return fail(MHPC_ERR_INVALID, "null u_nom");
+  if (arrays[sm::GAIN] && !arrays[sm::X_NOM])
     return fail(MHPC_ERR_INVALID, "K without x_nom: the gains act on x - x_nom");
-  if (arrays[im::X_NOM] && !arrays[im::GAIN])
-    return fail(MHPC_ERR_INVALID, "x_nom without K");
-  const int r = x0_row_of(h->plan);
-  const char* names[im::NIN] = {"x_nom", "u_nom", "K"};
-  for (int k = 0; k < im::NIN; ++k) {
-    const long dense = im::block(k, r, window);
-    ld[k] = dense;
-    if (!arrays[k]) continue;
-    if (lds[k] != 0 && lds[k] < dense)
-      return fail(MHPC_ERR_INVALID, std::string("ld_") + names[k] + " below the dense block");
-    if (lds[k] != 0) ld[k] = (long)lds[k];
-  }
-  return MHPC_OK;
+  if (arrays[sm::X_NOM] && !arrays[sm::GAIN]) return fail(MHPC_ERR_INVALID, "x_nom without K");
+  return check_lds(tab, sm::NIN, x0_row_of(h->plan), window, ld);
 }
 // The ledger's side of a finished import (Ledger::guessed): the listed problems' next first sweep
 // is the real rollout.
@@ -1689,25 +1718,20 @@ static void import_done(Handle* h, int n, const int32_t* problems) {
 int api_import_plan_device(Handle* h, int n, const int32_t* problems, const int32_t* first_step,
                            int window, int scope, const mhpc_plan_in* in, int dtype, void* stream,
                            float* ms) {
-  namespace im = mhpc_import_map;
   if (!h || !in) return fail(MHPC_ERR_INVALID, "null argument");
-  const void* arrays[im::NIN];
-  int64_t lds[im::NIN];
-  arrays[im::X_NOM] = in->x_nom, lds[im::X_NOM] = in->ld_x_nom;
-  arrays[im::U_NOM] = in->u_nom, lds[im::U_NOM] = in->ld_u_nom;
-  arrays[im::GAIN] = in->K, lds[im::GAIN] = in->ld_K;
-  long ld[im::NIN];
-  int rc = import_ready(h, n, problems, first_step, window, scope, arrays, lds, ld);
+  const CallerArray tab[sm::NIN] = {{in->x_nom, in->ld_x_nom, sm::X_NOM, "x_nom"},
+                                    {in->u_nom, in->ld_u_nom, sm::U_NOM, "u_nom"},
+                                    {in->K, in->ld_K, sm::GAIN, "K"}};
+  const void* arrays[sm::NIN];
+  long ld[sm::NIN];
+  int rc = import_ready(h, n, problems, first_step, window, scope, tab, arrays, ld);
   if (rc) return rc;
   if ((rc = check_dev_dtype(dtype))) return rc;
   HIPCHK(hipSetDevice(h->device));
-  const char* names[im::NIN] = {"x_nom", "u_nom", "K"};
-  for (int k = 0; k < im::NIN; ++k)
-    if (arrays[k] && (rc = check_device_ptr(h, arrays[k], names[k]))) return rc;
-  // the list and the first steps: temporaries of this call, no array of the handle
+  if ((rc = check_device_ptrs(h, tab, sm::NIN))) return rc;
   DevTemp<int> t(h->main.s1);
-  const int* dlist = problems ? t.in(std::vector<int>(problems, problems + n)) : nullptr;
-  const int* dfirst = first_step ? t.in(std::vector<int>(first_step, first_step + n)) : nullptr;
+  const int *dlist, *dfirst;
+  upload_list(t, n, problems, first_step, &dlist, &dfirst);
   if (t.e != hipSuccess) return dev_fail("mhpc_import_plan_device", t.e);
   if ((rc = wait_for_caller(h, stream))) return rc;
   // ---- nothing of the handle or the device has changed up to here ----
@@ -1724,45 +1748,43 @@ int api_import_plan_device(Handle* h, int n, const int32_t* problems, const int3
 int api_import_plan(Handle* h, int n, const int32_t* problems, const int32_t* first_step,
                     int window, int scope, const double* u_nom, const double* K,
                     const double* x_nom) {
-  namespace im = mhpc_import_map;
   if (!h) return fail(MHPC_ERR_INVALID, "null handle");
-  const void* arrays[im::NIN];
-  arrays[im::X_NOM] = x_nom, arrays[im::U_NOM] = u_nom, arrays[im::GAIN] = K;
-  const int64_t lds[im::NIN] = {0, 0, 0};
-  long ld[im::NIN];
-  int rc = import_ready(h, n, problems, first_step, window, scope, arrays, lds, ld);
+  const CallerArray tab[sm::NIN] = {
+      {x_nom, 0, sm::X_NOM, "x_nom"}, {u_nom, 0, sm::U_NOM, "u_nom"}, {K, 0, sm::GAIN, "K"}};
+  const void* host[sm::NIN];
+  long ld[sm::NIN];
+  int rc = import_ready(h, n, problems, first_step, window, scope, tab, host, ld);
   if (rc) return rc;
-  // every entry the kernel would read is finite (rows past a problem's valid steps and columns
-  // past a step's state size are not read)
+  // every entry the kernel would read is finite: every column of the valid rows that the map
+  // does not skip for the row's knot
   const int r = x0_row_of(h->plan);
-  const double* host[im::NIN] = {x_nom, u_nom, K};
+  const sm::Dims D = {h->sp.NK, h->sp.nslot};
   for (int i = 0; i < n; ++i) {
-    const Layout& L = h->plan.lays[h->plan.lid[problems ? problems[i] : i]];
+    const Layout& L = problem_layout(h, problems ? problems[i] : i);
     const int first = first_step ? first_step[i] : 0;
-    const int nvalid = im::valid(im::n_steps(scope, L.P, L.n_wb, L.N), first, window);
+    const int nvalid = sm::valid(sm::n_steps(scope, L.P, L.n_wb, L.N), first, window);
     for (int w = 0; w < nvalid; ++w) {
-      im::Knot q;
-      im::knot_of(scope, L.P, L.n_wb, L.N, L.ko, first + w, &q);
-      for (int k = 0; k < im::NIN; ++k) {
+      sm::Knot q;
+      sm::knot_of(scope, L.P, L.n_wb, L.N, L.ko, first + w, &q);
+      for (int k = 0; k < sm::NIN; ++k) {
         if (!host[k]) continue;
-        const int nc = im::cols(k, r);
-        const double* row = host[k] + (size_t)i * ld[k] + (size_t)w * nc;
-        for (int c = 0; c < nc; ++c) {
-          const bool read = k == im::U_NOM || (k == im::X_NOM ? c : c % r) < q.n;
-          if (read && !std::isfinite(row[c]))
+        const int nc = sm::cols(k, r);
+        const double* row = (const double*)host[k] + (size_t)i * ld[k] + (size_t)w * nc;
+        size_t off;
+        for (int c = 0; c < nc; ++c)
+          if (sm::knot_elem(k, r, D, 0, 0, q, c, &off) && !std::isfinite(row[c]))
             return fail(MHPC_ERR_INVALID, "u_nom, K and x_nom must be finite");
-        }
       }
     }
   }
   HIPCHK(hipSetDevice(h->device));
   DevTemp<int> t(h->main.s1);
   DevTemp<double> td(h->main.s1);
-  const int* dlist = problems ? t.in(std::vector<int>(problems, problems + n)) : nullptr;
-  const int* dfirst = first_step ? t.in(std::vector<int>(first_step, first_step + n)) : nullptr;
-  const void* dev[im::NIN];
-  for (int k = 0; k < im::NIN; ++k)
-    dev[k] = host[k] ? td.in(host[k], (size_t)n * ld[k]) : nullptr;
+  const int *dlist, *dfirst;
+  upload_list(t, n, problems, first_step, &dlist, &dfirst);
+  const void* dev[sm::NIN];
+  for (int k = 0; k < sm::NIN; ++k)
+    dev[k] = host[k] ? td.in((const double*)host[k], (size_t)n * ld[k]) : nullptr;
   if (t.e != hipSuccess) return dev_fail("mhpc_import_plan", t.e);
   if (td.e != hipSuccess) return dev_fail("mhpc_import_plan", td.e);
   // ---- nothing of the handle or the device has changed up to here ----
